@@ -23,7 +23,15 @@ entries.  A step re-runs each stage's device chain on every rank plus the stage'
 (the stats counters, cc_reduce_stats over RCCL); the records exchanges and the host I/O are the
 setup pass, outside the timed region as at N = 1.
 
-cpu_baseline (rank 0, N=1, before the GPU is touched): the C++ oracle (oracle/cc_oracle.cpp, the
+A plain run does only what the headline figure needs: setup, warm-up, the timed steps, the outputs
+(`--dump-outputs DIR`) and the result line.  `--full` adds the CPU baseline, the per-kernel breakdown
+(untimed profiling steps, HIP events around the dominant kernel in the timed region), the roofline
+figures and the PMC traffic lookup.
+
+--dump-outputs DIR: what the last timed step left for a caller of each stage, as DIR/<name>.npy
+(dump_outputs below); the inputs are seeded, so two builds can be compared output for output.
+
+cpu_baseline (--full; rank 0, N=1, before the GPU is touched): the C++ oracle (oracle/cc_oracle.cpp, the
 reference's dictionary program restated in C++ and pinned to the reference's outputs) on a bounded
 sample of the same model, consensus-only time, one core and one process per core.
 """
@@ -381,6 +389,86 @@ def cpu_baseline(cfg_name, seed):
     return out
 
 
+DUMP_ROWS = 4096        # sampled records per stage (their consensus rows are the bulk of the dump)
+DUMP_SEED = 20261019
+DUMP_MAX_BYTES = 64 << 20
+
+
+def stage_outputs(tag, r, rows=DUMP_ROWS):
+    """{name: float array} of what stage `r` holds for its caller after a step (the arrays its emit()
+    fetches): the stats counters (sorted by name) and whole-output histograms in full, and a fixed,
+    seeded sample of `rows` records with their decision columns, their consensus meta (length, mapq,
+    tlen, flag, read group) and their consensus bases and qualities.  Consensus rows are gathered
+    through the records' vote slots and zeroed past the consensus length; columns a decision leaves
+    undefined are -1, so only what a caller may read is compared.  Counts and record indices are
+    float64 (exact past 2^24), bases and qualities float32."""
+    eng = r.eng
+    sc = tag == "sc"
+    g = r.gs if sc else r.g
+    c = eng.counters(g)
+    out = {"counters": np.array([c[k] for k in sorted(c)], np.float64)}
+    max_len = max(r.srec.max_len, r.xrec.max_len) if sc else r.rec.max_len
+    qstride = (max_len + 15) & ~15
+    if tag == "sscs":
+        n_rec = eng.fetch(g, "emit_n", np.int32)
+        vslot = eng.fetch(g, "emit_vslot", np.int32)
+        voted = vslot >= 0
+        cols = [n_rec, eng.fetch(g, "emit_rec", np.int32), voted]
+        ckey = np.repeat(eng.fetch(g, "emit_ckey", np.int32).reshape(-1, 9), 2, axis=0)
+        out["family_sizes"] = np.bincount(eng.fetch(g, "fam_sizes_by_creation", np.int32)).astype(np.float64)
+        out["members"] = np.bincount(n_rec).astype(np.float64)
+        out["bad_records"] = np.float64([len(eng.fetch(g, "bad_rec", np.int32))])
+    else:
+        dec = eng.fetch(g, "dec", np.int32)
+        vslot = eng.fetch(g, "vslot", np.int32)
+        voted = (dec == 0) | (dec == 1) if sc else dec == 0
+        t_rec = np.where(dec < (3 if sc else 2), eng.fetch(g, "t_rec", np.int32), -1)
+        if sc:
+            cols = [dec, t_rec]
+            ckey = np.where(voted[:, None], eng.fetch(g, "q_ckey", np.int32).reshape(-1, 9), -1)
+        else:
+            cols = [dec, t_rec, np.where(voted, eng.fetch(g, "p_rec", np.int32), -1)]
+            ckey = None
+        out["decisions"] = np.bincount(dec[dec >= 0]).astype(np.float64)
+    n = len(vslot)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(rows, n), replace=False))
+    out["rows"] = pick.astype(np.float64)
+    live = voted[pick]
+    slot = np.where(live, vslot[pick], 0).astype(np.int64)
+    meta = eng.fetch(g, "vote_meta", np.int32).reshape(-1, 5)
+    m = np.where(live[:, None], meta[slot], -1) if len(meta) else np.full((len(pick), 5), -1)
+    rec = [np.asarray(col)[pick].astype(np.float64)[:, None] for col in cols]
+    if ckey is not None:
+        rec.append(ckey[pick].astype(np.float64))
+    out["records"] = np.concatenate(rec + [m.astype(np.float64)], axis=1)
+    inside = live[:, None] & (np.arange(qstride) < m[:, :1])
+    col = np.arange(qstride)
+    # qualities: one byte per base; bases: 4-bit codes, two per byte, the first in the high nibble
+    qual = eng.fetch(g, "cons_qual", np.uint8)
+    seq = eng.fetch(g, "cons_seq", np.uint8)
+    if len(qual):
+        q = qual[np.where(inside, slot[:, None] * qstride + col, 0)]
+        s = (seq[np.where(inside, slot[:, None] * (qstride // 2) + col // 2, 0)] >> (4 * (1 - col % 2))) & 15
+    else:
+        q = s = np.zeros(inside.shape, np.uint8)
+    out["cons_qual"] = np.where(inside, q, 0).astype(np.float32)
+    out["cons_seq"] = np.where(inside, s, 0).astype(np.float32)
+    return out
+
+
+def dump_outputs(path, runs, rank=0, world=1):
+    """Writes every stage's stage_outputs as <path>/<stage>_<name>.npy (r<rank>_ in front at N > 1)."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for tag, r in runs:
+        for name, a in stage_outputs(tag, r).items():
+            total += a.nbytes
+            if total > DUMP_MAX_BYTES:
+                raise RuntimeError("--dump-outputs: more than %d bytes" % DUMP_MAX_BYTES)
+            np.save(os.path.join(path, "%s%s_%s.npy" % ("r%d_" % rank if world > 1 else "", tag, name)), a)
+    return total
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -397,8 +485,13 @@ def main():
     ap.add_argument("--config", default=None, help="c2 (default at 1 GPU), c3 (default at N > 1), c4, c5")
     ap.add_argument("--pairs", type=int, default=None, help="override the config's read-pair count (tests)")
     ap.add_argument("--cutoff", type=float, default=0.7)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=2, help="untimed steps for the per-kernel breakdown")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the per-kernel breakdown, the roofline and PMC traffic figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--profile-steps", type=int, default=2,
+                    help="untimed steps for the per-kernel breakdown (--full)")
     args = ap.parse_args()
     args.profile_steps = max(1, args.profile_steps)
 
@@ -418,7 +511,7 @@ def main():
     from consensuscruncher_amd import synth
     seed = synth.SEED_BASE + int(config[1:]) + 1000 * rank
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         t = time.time()
         cpu = cpu_baseline(config, seed + 17)
         log("cpu baseline in %.1fs: %s" % (time.time() - t, cpu))
@@ -494,29 +587,31 @@ def main():
         for i in range(args.warmup):
             step(i)
         barrier()
-        # per-kernel breakdown: untimed steps with HIP events around every kernel scope (the events
-        # add launch gaps, so these steps are not the timed ones)
-        eng.set_profiling(True)
-        # a rehearsal with several ranks on one GPU (CC_BENCH_DEVICES) profiles the ranks one after
-        # another, so each rank's per-kernel times are its own and not shared with the other ranks'
-        serial = bool(share) and world > 1
-        for i in range(args.profile_steps):
-            if serial:
-                for k in range(world):
+        ktimes, dom_name = {}, None
+        if args.full:
+            # per-kernel breakdown: untimed steps with HIP events around every kernel scope (the events
+            # add launch gaps, so these steps are not the timed ones)
+            eng.set_profiling(True)
+            # a rehearsal with several ranks on one GPU (CC_BENCH_DEVICES) profiles the ranks one after
+            # another, so each rank's per-kernel times are its own and not shared with the other ranks'
+            serial = bool(share) and world > 1
+            for i in range(args.profile_steps):
+                if serial:
+                    for k in range(world):
+                        barrier()
+                        if rank == k:
+                            step(500 + i, reduce=False)
+                            eng.synchronize()
                     barrier()
-                    if rank == k:
-                        step(500 + i, reduce=False)
-                        eng.synchronize()
-                barrier()
-            else:
-                step(500 + i)
-        eng.synchronize()
-        ktimes = eng.kernel_times()
-        eng.set_profiling(False)
-        dom_name = max(ktimes.items(), key=lambda kv: kv[1][0])[0] if ktimes else None
-        # the timed region: events only around the dominant kernel (its live launch duration)
-        eng.profile_only([dom_name] if dom_name else [])
-        eng.set_profiling(True)
+                else:
+                    step(500 + i)
+            eng.synchronize()
+            ktimes = eng.kernel_times()
+            eng.set_profiling(False)
+            dom_name = max(ktimes.items(), key=lambda kv: kv[1][0])[0] if ktimes else None
+            # the timed region: events only around the dominant kernel (its live launch duration)
+            eng.profile_only([dom_name] if dom_name else [])
+            eng.set_profiling(True)
         barrier()
         l0 = eng.launch_count()
         t0 = time.perf_counter()
@@ -525,9 +620,15 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         launches = (eng.launch_count() - l0) / float(args.steps)
-        dtimes = eng.kernel_times()
-        eng.set_profiling(False)
-        eng.profile_only([])
+        dtimes = {}
+        if args.full:
+            dtimes = eng.kernel_times()
+            eng.set_profiling(False)
+            eng.profile_only([])
+        if args.dump_outputs:
+            t = time.time()
+            nbytes = dump_outputs(args.dump_outputs, runs, rank, world)
+            log("wrote the last step's outputs (%d bytes) to %s in %.1fs" % (nbytes, args.dump_outputs, time.time() - t))
 
         total_in, max_el = float(n_in), elapsed
         if dist is not None:
@@ -542,28 +643,6 @@ def main():
             config, "-b False" if bed is None else (
                 "one hg38 sample over %d GPUs (hg38_cytoBand.txt region blocks, %d pairs per GPU, weak scaling)"
                 % (world, cfg["n_pairs"]) if sharded else "hg38_cytoBand.txt regions"), args.cutoff)))
-        # SURVEY.md §8(d), the headline: sum over the stages of B_s = N_in (L/2 + L + 16) + N_out (L/2 + L)
-        # per step, over the honest step time (every kernel of every stage, table preparation
-        # included, plus launch gaps and the end-of-pass readbacks)
-        pipe_bytes = 0.0
-        for tag, r in runs:
-            if tag == "sc":
-                n_out = int((eng.fetch(r.gs, "dec", np.int32) < 2).sum())
-            else:
-                n_out = len(eng.fetch(r.g, "emit_n" if tag == "sscs" else "dec", np.int32))
-            pipe_bytes += r.n_input * (L // 2 + L + 16) + n_out * (L // 2 + L)
-        step_s = max_el / args.steps
-        pipe_ach = pipe_bytes / step_s / 1e9
-        # secondary: the dominant kernel (HIP events on the engine's stream over the timed region)
-        alg = algorithmic_bytes(None, runs, L)
-        if dom_name is None:   # --profile-steps 0: the timed region's own scopes name it
-            dom_name = max(dtimes.items(), key=lambda kv: kv[1][0])[0] if dtimes else None
-        dom_ms, dom_n = dtimes.get(dom_name, (0.0, 0))
-        avg_s = dom_ms / 1000.0 / max(dom_n, 1)
-        bytes_per_launch = alg.get(dom_name)
-        achieved = (bytes_per_launch / avg_s / 1e9) if bytes_per_launch else None
-        traffic, traffic_src = pmc_traffic(dom_name, dom_n / float(args.steps))
-        kernel_s = sum(v[0] for v in ktimes.values()) / 1000.0 / max(args.profile_steps, 1)
         out = {
             "metric": "input reads/sec through SSCS+DCS+SC consensus",
             "value": round(value, 1),
@@ -585,31 +664,56 @@ def main():
                 "parallelism": ("cytoband-block shards x%d (sharded.py: rank-local records, foreign first mates "
                                 "routed, one RCCL stats reduction per stage)" % world) if sharded else
                                ("cytoband regions, one GPU" if bed else "single GPU, -b False")},
-            "roofline": {"bound": "hbm", "scope": "pipeline: every stage of one step (SURVEY.md 8d)",
-                         "achieved": round(pipe_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(pipe_ach / HBM_PEAK_GBS, 4), "traffic": pmc_step_traffic(),
-                         "traffic_source": (_pmc_file() + " (engine build %s): every kernel of a step (the tables' derived "
-                                            "columns included), bytes per step; reads: %s" % (
-                                                _lib_sha(), (_pmc() or {}).get("_meta", {}).get("reads")))
-                         if _pmc() is not None else "null: " + str(_pmc_status()[1]),
-                         "alg_bytes_per_step": pipe_bytes, "step_ms": round(step_s * 1000, 3),
-                         "per_unit": "%d B per input read + %d B per emitted record" % (
-                             L // 2 + L + 16, L // 2 + L)},
-            "dominant_kernel": {"kernel": dom_name, "scope_kernels": SCOPE_KERNELS.get(dom_name, [dom_name]),
-                                "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS,
-                                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
-                                "traffic": traffic, "traffic_source": traffic_src,
-                                "avg_launch_us": round(avg_s * 1e6, 2), "alg_bytes_per_launch": bytes_per_launch},
             "build": {"libccamd": os.path.relpath(native.amd_path(), ROOT), "lib_sha": _lib_sha()},
-            "device_ms_per_step": round(kernel_s * 1000, 3),
-            "kernels_ms_per_step": {k: round(v[0] / args.profile_steps, 4) for k, v in
-                                    sorted(ktimes.items(), key=lambda kv: -kv[1][0])},
             "end_to_end": {"setup_s": round(setup_t["e2e"], 2),
                            "reads_per_s": round(n_in / setup_t["e2e"], 1),
                            "breakdown_s": {k: v for k, v in setup_t.items() if k != "e2e"},
                            "note": "decode+upload+GPU+encode+sort+merge, one pass, per rank"},
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            # SURVEY.md §8(d), the headline: sum over the stages of B_s = N_in (L/2 + L + 16) + N_out (L/2 + L)
+            # per step, over the honest step time (every kernel of every stage, table preparation
+            # included, plus launch gaps and the end-of-pass readbacks)
+            pipe_bytes = 0.0
+            for tag, r in runs:
+                if tag == "sc":
+                    n_out = int((eng.fetch(r.gs, "dec", np.int32) < 2).sum())
+                else:
+                    n_out = len(eng.fetch(r.g, "emit_n" if tag == "sscs" else "dec", np.int32))
+                pipe_bytes += r.n_input * (L // 2 + L + 16) + n_out * (L // 2 + L)
+            step_s = max_el / args.steps
+            pipe_ach = pipe_bytes / step_s / 1e9
+            # secondary: the dominant kernel (HIP events on the engine's stream over the timed region)
+            alg = algorithmic_bytes(None, runs, L)
+            if dom_name is None:   # --profile-steps 0: the timed region's own scopes name it
+                dom_name = max(dtimes.items(), key=lambda kv: kv[1][0])[0] if dtimes else None
+            dom_ms, dom_n = dtimes.get(dom_name, (0.0, 0))
+            avg_s = dom_ms / 1000.0 / max(dom_n, 1)
+            bytes_per_launch = alg.get(dom_name)
+            achieved = (bytes_per_launch / avg_s / 1e9) if bytes_per_launch else None
+            traffic, traffic_src = pmc_traffic(dom_name, dom_n / float(args.steps))
+            kernel_s = sum(v[0] for v in ktimes.values()) / 1000.0 / max(args.profile_steps, 1)
+            out.update({
+                "roofline": {"bound": "hbm", "scope": "pipeline: every stage of one step (SURVEY.md 8d)",
+                             "achieved": round(pipe_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(pipe_ach / HBM_PEAK_GBS, 4), "traffic": pmc_step_traffic(),
+                             "traffic_source": (_pmc_file() + " (engine build %s): every kernel of a step (the tables' derived "
+                                                "columns included), bytes per step; reads: %s" % (
+                                                    _lib_sha(), (_pmc() or {}).get("_meta", {}).get("reads")))
+                             if _pmc() is not None else "null: " + str(_pmc_status()[1]),
+                             "alg_bytes_per_step": pipe_bytes, "step_ms": round(step_s * 1000, 3),
+                             "per_unit": "%d B per input read + %d B per emitted record" % (
+                                 L // 2 + L + 16, L // 2 + L)},
+                "dominant_kernel": {"kernel": dom_name, "scope_kernels": SCOPE_KERNELS.get(dom_name, [dom_name]),
+                                    "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS,
+                                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
+                                    "traffic": traffic, "traffic_source": traffic_src,
+                                    "avg_launch_us": round(avg_s * 1e6, 2), "alg_bytes_per_launch": bytes_per_launch},
+                "device_ms_per_step": round(kernel_s * 1000, 3),
+                "kernels_ms_per_step": {k: round(v[0] / args.profile_steps, 4) for k, v in
+                                        sorted(ktimes.items(), key=lambda kv: -kv[1][0])},
+                "cpu_baseline": cpu,
+            })
         if rank == 0:
             print(json.dumps(out), flush=True)
         for _, r in runs:

@@ -324,10 +324,10 @@ def generate(n_pairs, seed=SEED_BASE, read_len=150, contigs=(("chr1", 5_000_000)
     if nsp:
         spacer_pairs = rng.choice(P, nsp, replace=False)
         spacer_bad[np.isin(rec["pair"], spacer_pairs)] = True
-    for d, sb in extra:
+    if extra:   # (one copy of every column for all the additions: seq and qual are GBs at 10^7 reads)
         for key in rec:
-            rec[key] = np.concatenate([rec[key], d[key]])
-        spacer_bad = np.concatenate([spacer_bad, sb])
+            rec[key] = np.concatenate([rec[key]] + [d[key] for d, _ in extra])
+        spacer_bad = np.concatenate([spacer_bad] + [sb for _, sb in extra])
     if nsp:
         spacer_bad |= np.isin(rec["pair"], spacer_pairs) & (rec["pair"] < P)
 
@@ -398,14 +398,20 @@ def generate(n_pairs, seed=SEED_BASE, read_len=150, contigs=(("chr1", 5_000_000)
 
     # ---- coordinate sort (samtools key, random tie order)
     tkey = rec["tid"].astype(np.int64)
-    tkey[tkey < 0] = 1 << 40
+    tkey[tkey < 0] = len(names)   # unmapped records last
     rev = (rec["flag"] & 0x10) > 0
     tie = rng.permutation(len(tkey)) if ties == "random" else np.arange(len(tkey))
     if barcode_mode == "odd":
         # ties: (+) strand records, then (-), then chain clones, so that the reference's DCS stage
         # meets every duplex chain head first (the other orders end in its KeyError, DCS_maker.py:258)
-        tie = rec["srank"].astype(np.int64) * len(tkey) + tie
-    order = np.lexsort((tie, rev, rec["pos"].astype(np.int64) + 1, tkey))
+        by_tie = np.argsort(rec["srank"].astype(np.int64) * len(tkey) + tie, kind="stable")
+    else:   # tie is a permutation: its inverse lists the records in tie order
+        by_tie = np.empty(len(tkey), np.int64)
+        by_tie[tie] = np.arange(len(tkey))
+    # the order of (tid, pos + 1, strand, tie): the tie ranks are distinct, so one stable sort of the
+    # packed (tid, pos + 1, strand) key over the records laid out in tie order gives it
+    key = (tkey << 33) | ((rec["pos"].astype(np.int64) + 1) << 1) | rev
+    order = by_tie[np.argsort(key[by_tie], kind="stable")]
     if shuffle:
         order = rng.permutation(len(tkey))
     for key in rec:
@@ -550,31 +556,26 @@ def qname_blob(batch, delim="|"):
         np.cumsum([len(x) for x in names], out=off[1:])
         return np.frombuffer(b"".join(names), np.uint8).copy(), off
     pair = batch.pair.astype(np.int64)
-    digits = np.zeros((n, 10), np.uint8)
-    x = pair.copy()
-    for k in range(9, -1, -1):
-        digits[:, k] = 48 + (x % 10)
-        x //= 10
     bct = [s.encode() for s in batch.barcode_table]
     bclen = np.array([len(s) for s in bct], np.int64)
     this_len = np.where(batch.spacer_bad, 0, 1 + bclen[batch.bc])
     lens = 13 + this_len
     off = np.zeros(n + 1, np.int64)
     np.cumsum(lens, out=off[1:])
-    blob = np.zeros(int(off[-1]), np.uint8)
-    base = off[:-1]
-    blob[base[:, None] + np.arange(3)] = np.frombuffer(b"SYN", np.uint8)
-    blob[base[:, None] + 3 + np.arange(10)] = digits
-    good = ~batch.spacer_bad
-    blob[base[good] + 13] = ord(delim)
     maxbc = int(bclen.max())
     bcmat = np.zeros((len(bct), maxbc), np.uint8)
     for i, s in enumerate(bct):
         bcmat[i, :len(s)] = np.frombuffer(s, np.uint8)
-    gi = np.nonzero(good)[0]
-    for j in range(maxbc):
-        sel = gi[bclen[batch.bc[gi]] > j]
-        blob[base[sel] + 14 + j] = bcmat[batch.bc[sel], j]
+    # every qname laid out at full width (SYN, 10 digits, delimiter, barcode), then cut to its length
+    dec4 = np.array([b"%04d" % i for i in range(10000)], "S4").view(np.uint8).reshape(-1, 4)
+    mat = np.empty((n, 14 + maxbc), np.uint8)
+    mat[:, :3] = np.frombuffer(b"SYN", np.uint8)
+    mat[:, 3:5] = dec4[(pair // 10 ** 8) % 100, 2:]
+    mat[:, 5:9] = dec4[(pair // 10 ** 4) % 10 ** 4]
+    mat[:, 9:13] = dec4[pair % 10 ** 4]
+    mat[:, 13] = ord(delim)
+    mat[:, 14:] = bcmat[batch.bc]
+    blob = mat[np.arange(14 + maxbc) < lens[:, None]]
     return blob, off
 
 

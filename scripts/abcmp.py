@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Compare bench lines of an A/B call (gpurun_out/ab_*.json): step time and per-kernel ms per step."""
+"""Compare bench lines of an A/B call (bench_out/ab_*.json): step time and per-kernel ms per step."""
 import glob
 import json
 import sys
 
 rows = {}
-for p in sorted(glob.glob(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/ab_*.json")):
+for p in sorted(glob.glob(sys.argv[1] if len(sys.argv) > 1 else "bench_out/ab_*.json")):
     try:
         d = json.loads(open(p).read().strip().splitlines()[-1])
     except Exception as e:   # noqa: B902
