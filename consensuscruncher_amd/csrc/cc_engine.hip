@@ -37,6 +37,7 @@
 #include <atomic>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <type_traits>
 #include <string>
 #include <unordered_set>
@@ -5330,6 +5331,8 @@ constexpr int PLAN_SLOTS = 64;
 
 }  // namespace
 
+struct BgzfEnc;   // the device BGZF encoder's streams and buffers (bgzf_deflate.hip.inc)
+
 struct cc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -5352,7 +5355,7 @@ struct cc_ctx {
     uint32_t* d_err = nullptr;      // device error word
     unsigned long long* d_cnt = nullptr;
     void* h_pinned = nullptr;       // small pinned scratch for scalar readbacks
-    bool profiling = false;
+    std::atomic<bool> profiling{false};   // (the BGZF encoder reads it from the writers' threads)
     std::unordered_set<std::string> prof_only;   // when non-empty, the only scopes timed
     struct Prof { double ms = 0; int64_t n = 0; };
     std::map<std::string, Prof> prof;
@@ -5363,6 +5366,8 @@ struct cc_ctx {
     std::vector<DeferredCheck> deferred;
     uint8_t* h_defer = nullptr;           // DEFER_SLOTS pinned readback slots
     uint8_t* d_defer = nullptr;           // the same area as the device sees it (k_defer_pack)
+    BgzfEnc* bgzf = nullptr;              // made by the first cc_bgzf_deflate / hook call
+    std::mutex bgzf_mu;                   // guards its creation (the writers' threads call the hook)
 };
 
 namespace {
@@ -5935,6 +5940,7 @@ int build_fam_buckets(cc_ctx* ctx, Group& g, GroupView* v, bool* ok) {
 
 }  // namespace
 
+#include "bgzf_deflate.hip.inc"
 
 extern "C" {
 
@@ -5957,6 +5963,7 @@ int cc_destroy(cc_ctx* ctx) {
     if (!ctx) return CC_E_INVALID;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
+    bgzf_free(ctx);
     for (auto& g : ctx->groups)
         for (auto& b : g.second->buf)
             if (b.second.p) (void)hipFree(b.second.p);
@@ -5998,6 +6005,7 @@ int cc_set_profiling(cc_ctx* ctx, int on) {
     flush_prof(ctx);
     ctx->profiling = on != 0;
     if (on) ctx->prof.clear();
+    if (on) bgzf_prof(ctx, true, nullptr, nullptr);
     return 0;
 }
 
@@ -6017,6 +6025,16 @@ int cc_profile_only(cc_ctx* ctx, const char* names) {
 int cc_kernel_times(cc_ctx* ctx, char* names, int names_cap, double* ms, int64_t* launches, int cap) {
     if (!ctx) return CC_E_INVALID;
     flush_prof(ctx);
+    {   // the encoder times its kernel on its own streams
+        double bms = 0, up = 0, down = 0;
+        int64_t bn = 0;
+        bgzf_prof(ctx, false, &bms, &bn, &up, &down);
+        if (bn) {
+            ctx->prof["bgzf_deflate"] = {bms, bn};
+            ctx->prof["bgzf_upload"] = {up, bn};       // the launches' host-to-device copies
+            ctx->prof["bgzf_download"] = {down, bn};   // and the packed members' way back
+        }
+    }
     int i = 0;
     std::string all;
     for (auto& p : ctx->prof) {

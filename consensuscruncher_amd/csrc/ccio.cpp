@@ -282,6 +282,38 @@ bool bgzf_deflate_write(FILE* f, const uint8_t* data, size_t n, int level, int n
     return bgzf_deflate_blocks(f, data, n, level, nthreads, csize) && fwrite(kBgzfEof, 1, 28, f) == 28;
 }
 
+// An alternative encoder for the rounds below (ccio_set_deflate_hook): the device BGZF encoder of
+// libccamd, or any function with its contract.  libccio itself stays free of HIP.
+std::mutex g_hook_mu;
+ccio_deflate_fn g_hook_fn = nullptr;
+void* g_hook_user = nullptr;
+
+// One round through the hook: true when every member it reports is a framed BGZF member of its
+// piece (sizes and the BSIZE / ISIZE fields checked here); anything else leaves the round to the
+// host encoder.
+bool hook_round(const uint8_t* data, size_t nbytes, size_t step, uint8_t* stage, size_t slot, size_t pieces,
+                std::vector<size_t>& len) {
+    ccio_deflate_fn fn;
+    void* user;
+    {
+        std::lock_guard<std::mutex> lk(g_hook_mu);
+        fn = g_hook_fn;
+        user = g_hook_user;
+    }
+    if (!fn) return false;
+    std::vector<uint32_t> got(pieces, 0);
+    if (fn(user, data, (uint64_t)nbytes, stage, (uint64_t)slot, got.data(), (int64_t)pieces) != 0) return false;
+    for (size_t j = 0; j < pieces; ++j) {
+        const size_t ln = std::min(step, nbytes - j * step), b = got[j];
+        const uint8_t* h = stage + j * slot;
+        if (b < 28 || b > 0x10000 || h[0] != 0x1f || h[1] != 0x8b || (size_t)(h[16] | (h[17] << 8)) + 1 != b ||
+            ((uint32_t)h[b - 4] | ((uint32_t)h[b - 3] << 8) | ((uint32_t)h[b - 2] << 16) | ((uint32_t)h[b - 1] << 24)) != (uint32_t)ln)
+            return false;
+    }
+    for (size_t j = 0; j < pieces; ++j) len[j] = got[j];
+    return true;
+}
+
 // the BGZF members of data (no EOF marker): 0xff00-byte pieces compressed in parallel into one
 // staging area (a bounded slot per piece), written in order; csize gets each member's size
 bool bgzf_deflate_blocks(FILE* f, const uint8_t* data, size_t n, int level, int nthreads,
@@ -304,7 +336,9 @@ bool bgzf_deflate_blocks(FILE* f, const uint8_t* data, size_t n, int level, int 
         uint8_t* const stage = stage2[cur].get();
         std::vector<size_t>& len = len2[cur];
         std::atomic<bool> bad(false);
-        parallel_chunks((int64_t)(r1 - r0), nthreads, 8, [&](int64_t b, int64_t e) {
+        const bool hooked = level >= 1 && hook_round(data + r0 * step, std::min(n, r1 * step) - r0 * step, step, stage,
+                                                     slot, r1 - r0, len);
+        if (!hooked) parallel_chunks((int64_t)(r1 - r0), nthreads, 8, [&](int64_t b, int64_t e) {
             Codec c;
             for (int64_t j = b; j < e && !bad; ++j) {
                 const size_t i = r0 + (size_t)j;
@@ -609,6 +643,13 @@ int ccio_value_census(const int32_t* v, int64_t n, int32_t maxv, int64_t* first,
         if (count[x]++ == 0) first[x] = i;
     }
     return 0;
+}
+
+// fn compresses the writers' BGZF rounds at level >= 1 from now on (NULL: the host encoder again)
+void ccio_set_deflate_hook(ccio_deflate_fn fn, void* user) {
+    std::lock_guard<std::mutex> lk(g_hook_mu);
+    g_hook_fn = fn;
+    g_hook_user = fn ? user : nullptr;
 }
 
 // waits for every CCIO_W_ASYNC write; -1 (ccio_last_error: the first failure) when one failed

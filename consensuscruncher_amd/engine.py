@@ -279,6 +279,9 @@ def coord_sorted(records):
     return records._coord_sorted
 
 
+_BGZF_OWNER = None   # the engine whose encoder libccio's (process-wide) deflate hook points at
+
+
 class Engine(object):
     """One HIP context on one GPU (cc_ctx)."""
 
@@ -290,11 +293,67 @@ class Engine(object):
             raise N.CCError(rc, "cc_create failed (no usable GPU?)")
         self.h = h
         self.tables = {}
+        self.bgzf_device = False
+        if os.environ.get("CC_BGZF_DEVICE") == "1":   # opt-in, in the style of CC_EXTRACT_GPU
+            self.device_bgzf(True)
+
+    def device_bgzf(self, on):
+        """Wires (or unwires) this context's device BGZF encoder into libccio's writers
+        (cc_bgzf_hook -> ccio_set_deflate_hook): every BAM written at level >= 1 from now on is
+        deflated by k_bgzf_deflate instead of the host codec.  The records are the same either way;
+        the compressed bytes and the .bai virtual offsets differ.  The hook is one per process: the
+        last engine to wire it serves the writers, and the engine it took the hook from reads
+        bgzf_device False from then on (its close or unwiring leaves the new owner's hook alone).
+        Wiring and unwiring wait for the background writes first, so a file is encoded by one
+        encoder throughout.  Returns the previous state."""
+        global _BGZF_OWNER
+        was = self.bgzf_device
+        on = bool(on)
+        if on == was:
+            return was
+        io = N.io()
+        if on:
+            fn, user = N.P(), N.P()
+            self._check(self.lib.cc_bgzf_hook(self.h, C.byref(fn), C.byref(user)))
+            prev = _BGZF_OWNER
+            if prev is not None and prev is not self:
+                rc = io.ccio_flush()   # no writer thread is inside the previous owner's encoder
+                prev.bgzf_device = False
+                if rc != 0:
+                    raise IOError(N.io_error())
+            io.ccio_set_deflate_hook(fn, user)
+            _BGZF_OWNER = self
+            self.bgzf_device = True
+            return was
+        rc = io.ccio_flush()   # no writer thread is inside the hook after this
+        io.ccio_set_deflate_hook(None, None)
+        _BGZF_OWNER = None
+        self.bgzf_device = False
+        if rc != 0:
+            raise IOError(N.io_error())
+        return was
+
+    def bgzf_deflate(self, data):
+        """cc_bgzf_deflate: the framed BGZF members of data (bytes-like), one per 0xff00-byte piece,
+        as a list of bytes objects."""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        pieces = (buf.size + 0xff00 - 1) // 0xff00
+        slot = 0x10000
+        stage = np.zeros(max(pieces, 1) * slot, np.uint8)
+        lens = np.zeros(max(pieces, 1), np.uint32)
+        got = int(self.lib.cc_bgzf_deflate(self.h, N.ptr(buf) if buf.size else None, buf.size, N.ptr(stage), slot,
+                                           N.ptr(lens), pieces))
+        if got < 0:
+            raise N.CCError(got, self.lib.cc_last_error(self.h).decode(errors="replace"))
+        return [stage[j * slot:j * slot + int(lens[j])].tobytes() for j in range(got)]
 
     def close(self):
         if self.h:
-            self.lib.cc_destroy(self.h)
-            self.h = None
+            try:
+                self.device_bgzf(False)   # the hook must not outlive the context
+            finally:
+                self.lib.cc_destroy(self.h)
+                self.h = None
 
     def __del__(self):
         try:

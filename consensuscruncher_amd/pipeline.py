@@ -51,7 +51,26 @@ def cleanup(sd, identifier, scorrect):
 
 
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
-                       verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False):
+                       verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
+                       bgzf="host"):
+    """bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
+    output files: same records, other compressed bytes and .bai offsets); see _consensus_pipeline."""
+    if bgzf not in ("host", "device"):
+        raise ValueError('bgzf must be "host" or "device"')
+    if bgzf == "host":
+        return _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                   cleanup_files, all_unique_sscs)
+    engine = engine or get_engine()
+    was = engine.device_bgzf(True)
+    try:
+        return _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                   cleanup_files, all_unique_sscs)
+    finally:
+        engine.device_bgzf(was)
+
+
+def _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                        cleanup_files, all_unique_sscs):
     """ConsensusCruncher.consensus (ConsensusCruncher.py:127-346).  Each stage output the reference
     writes and then sort_index-es (X.bam -> X.sorted.bam + .bai, X.bam removed) is written sorted and
     indexed at once (engine.Sink: the same files at the end), and a stage reading the file another

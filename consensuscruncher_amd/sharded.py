@@ -618,7 +618,24 @@ def to_owners(comm, geo, parts):
 
 def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|", scorrect="True", level=6,
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
-                     cuts=None):
+                     cuts=None, bgzf="host"):
+    """bgzf: "host" (the default) or "device": this rank's output files deflated by the engine's BGZF
+    encoder (pipeline.consensus_pipeline's option); see _sharded_pipeline."""
+    if bgzf not in ("host", "device"):
+        raise ValueError('bgzf must be "host" or "device"')
+    if bgzf == "host":
+        return _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                 blocks, held, refs, keep, finalize, timings, cuts)
+    was = engine.device_bgzf(True)
+    try:
+        return _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                 blocks, held, refs, keep, finalize, timings, cuts)
+    finally:
+        engine.device_bgzf(was)
+
+
+def _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose, blocks, held,
+                      refs, keep, finalize, timings, cuts):
     """ConsensusCruncher.py:127-346 with every stage split over comm.world region shards.  Same files
     and contents as pipeline.consensus_pipeline; rank 0 returns the output paths.
 

@@ -181,6 +181,20 @@ int ccio_merge_bams(const char *out_path, const char *const *in_paths, int nin, 
  * multi-GPU driver keeps every stage output in memory and writes only the final files) */
 #define CCIO_W_MEMORY 8
 int ccio_flush(void);
+/* An alternative encoder for the writers' BGZF members (the device encoder: cc_bgzf_hook below).
+ * The writers cut a stream into pieces of at most 0xff00 bytes and compress them in rounds; with a
+ * hook set, a round at level >= 1 goes to fn first:
+ *   data, n   the round's bytes (pieces: ceil(n / 0xff00), the last one shorter);
+ *   stage     piece j's whole member (18-byte header, raw DEFLATE, CRC32, ISIZE) goes to
+ *             stage + j * slot (slot >= 65536);  out_len[j] = its size, 28..65536.
+ * fn returns 0 when every member is written.  On any other return, or a member whose size or
+ * BSIZE / ISIZE fields do not fit its piece, the host encoder compresses that round: a file is
+ * never lost or left partial.  Level 0 never reaches fn.  fn is called from the CCIO_W_ASYNC
+ * writer threads, several at once.  NULL unsets the hook; unset it before freeing what user
+ * points to (after ccio_flush). */
+typedef int (*ccio_deflate_fn)(void *user, const uint8_t *data, uint64_t n, uint8_t *stage, uint64_t slot,
+                               uint32_t *out_len, int64_t pieces);
+void ccio_set_deflate_hook(ccio_deflate_fn fn, void *user);
 /* per value 0..maxv of v[0..n): count and first index (n when absent), one pass (read_families.txt) */
 int ccio_value_census(const int32_t *v, int64_t n, int32_t maxv, int64_t *first, int64_t *count);
 int ccio_write_bam_ex(const char *path, ccio_bam *tmpl, ccio_interner *it, int64_t n, const cc_out_spec *spec,
@@ -311,6 +325,19 @@ int cc_profile_only(cc_ctx *ctx, const char *names);
 /* name, total ms, launches for every profiled kernel: returns count */
 int cc_kernel_times(cc_ctx *ctx, char *names, int names_cap, double *ms, int64_t *launches, int cap);
 int cc_synchronize(cc_ctx *ctx);
+/* BGZF members on the device (k_bgzf_deflate: one workgroup per piece; hash matching, a greedy
+ * parse, and the smallest of a stored, a fixed-Huffman and a dynamic-Huffman block).  data[0..n) is
+ * cut at every 0xff00 bytes; piece j's framed member goes to stage + j * slot (slot >= 65536) and
+ * out_len[j] gets its size (<= 65536).  Returns the member count, ceil(n / 0xff00) (0 for n == 0),
+ * or a negative CC_E_*; more pieces than cap is CC_E_INVALID.  The same bytes give the same
+ * members on every call.  The encoder has its own streams and buffers and serialises concurrent
+ * callers: it may run from any thread while the context's stream is busy.  With profiling on, the
+ * kernel's time is reported by cc_kernel_times as "bgzf_deflate", its copies as "bgzf_upload" and
+ * "bgzf_download". */
+int64_t cc_bgzf_deflate(cc_ctx *ctx, const uint8_t *data, uint64_t n, uint8_t *stage, uint64_t slot,
+                        uint32_t *out_len, int64_t cap);
+/* the pair to hand to ccio_set_deflate_hook; unset the hook before cc_destroy */
+int cc_bgzf_hook(cc_ctx *ctx, ccio_deflate_fn *fn, void **user);
 /* Deferred end-of-pass checks (no reference counterpart: the reference has no device).  With
  * deferral on, a stage call that re-runs a planned pass (cc_read_bam_rerun, cc_consensus_maker,
  * cc_duplex_consensus, cc_singleton_correction on a group that ran before) enqueues its check and
