@@ -2279,20 +2279,7 @@ struct DeepOut {   // the ranked slots k_fam_mark would have written
     uint4* mem_meta;
 };
 
-#ifdef DF_PROF   // phase timing of k_deep_fam (a measurement build: scripts/build_variant.sh NAME - -DDF_PROF)
-__device__ unsigned long long g_df_prof[8];
-#define DFP(k)                                                                      \
-    do {                                                                            \
-        __syncthreads();                                                            \
-        if (t == 0) {                                                               \
-            const unsigned long long now = wall_clock64();                          \
-            atomicAdd(&g_df_prof[k], now - tp);                                     \
-            tp = now;                                                               \
-        }                                                                           \
-    } while (0)
-#else
-#define DFP(k) __syncthreads()   // (each phase mark is a block barrier the kernel needs anyway)
-#endif
+#define DFP(k) __syncthreads()   // (k_deep_fam's phase marks: each is a block barrier the kernel needs anyway)
 
 __global__ __launch_bounds__(DF_T) void k_deep_fam(const uint32_t* __restrict__ ndeep, const int32_t* __restrict__ dlist,
                                                    const int32_t* __restrict__ gend, const int32_t* __restrict__ rec_e,
@@ -2320,9 +2307,6 @@ __global__ __launch_bounds__(DF_T) void k_deep_fam(const uint32_t* __restrict__ 
         const int64_t g0 = dlist[gi];
         const int32_t ge = gend[g0];
         const int64_t g1 = ge < 0 ? -1 - (int64_t)ge : (int64_t)ge;
-#ifdef DF_PROF
-        unsigned long long tp = wall_clock64();
-#endif
         for (int i = t; i < DF_SLOTS; i += DF_T) {
             s_key[i] = DF_EMPTY;
             s_rep[i] = INT32_MAX;
@@ -5329,6 +5313,47 @@ constexpr int CC_E_DEEPSORT = -102;   // internal: a deep family needs the sorte
 constexpr int CC_E_SCANWAIT = -103;   // internal: a look-back scan waited past its bound (re-run with two-launch scans)
 constexpr int PLAN_SLOTS = 64;
 
+// The engine's environment switches ("Engine switches"): every one there is, read by
+// read_switches() at the top of each entry point that uses one (per call: a test changes them between
+// runs on one live engine).  None changes an output.
+struct EngineSwitches {
+    int scan1 = -1;                // CC_SCAN1=1 / 0: every scan as one look-back launch / as reduce-then-scan
+    int pc_tile = 0;               // CC_PC_TILE=512 / 1024: the mate search's tile size (0: by the table's size)
+    bool resid_sort = false;       // CC_RESID_SORT: residual reads paired by the qname sort, not their table
+    bool resid_scan = false;       // CC_RESID_SCAN: residual keys compacted by the scan, not appended
+    bool qdig = true;              // CC_QDIG=0: the qname bytes hashed in every pass, not the table's digests
+    int qdig_bits = 0;             // CC_QDIG_BITS=k: k bits of the digests kept (0: all 64)
+    bool dcs_per_entry = false;    // CC_DCS_PER_ENTRY: DCS decisions per entry, not per family
+    int64_t lp_min = LP_MIN;       // CC_LP_MIN=n: planned long pairs from which the partitioned check runs (0: always)
+    bool ltab_cas = false;         // CC_LTAB_CAS: the long-pair table in every pass, never the partitioned check
+    bool group_staged = false;     // CC_GROUP_STAGED: read ends classified from staged position keys (k_group_flags)
+    bool meta_scalar = false;      // CC_META_SCALAR: fused preparation one record per thread (k_build_meta_cls)
+    bool derive_separate = false;  // CC_DERIVE_SEPARATE: cc_table_derive launches k_derive itself
+    bool gr_by_pair = false;       // CC_GR_BY_PAIR: the group ranking compares tags through the pairs
+    bool deep_sort = false;        // CC_DEEP_SORT: deep position groups ranked by the sort, not in place
+    bool trace_upload = false;     // CC_TRACE_UPLOAD: one stderr line per uploaded table
+};
+
+EngineSwitches read_switches() {
+    EngineSwitches sw;
+    if (const char* v = getenv("CC_SCAN1")) sw.scan1 = v[0] == '1' ? 1 : 0;
+    if (const char* v = getenv("CC_PC_TILE")) sw.pc_tile = atoi(v) == 512 ? 512 : 1024;
+    sw.resid_sort = getenv("CC_RESID_SORT") != nullptr;
+    sw.resid_scan = getenv("CC_RESID_SCAN") != nullptr;
+    if (const char* v = getenv("CC_QDIG")) sw.qdig = v[0] != '0';
+    if (const char* v = getenv("CC_QDIG_BITS")) sw.qdig_bits = atoi(v) > 0 && atoi(v) < 64 ? atoi(v) : 0;
+    sw.dcs_per_entry = getenv("CC_DCS_PER_ENTRY") != nullptr;
+    if (const char* v = getenv("CC_LP_MIN")) sw.lp_min = atoll(v);
+    sw.ltab_cas = getenv("CC_LTAB_CAS") != nullptr;
+    sw.group_staged = getenv("CC_GROUP_STAGED") != nullptr;
+    sw.meta_scalar = getenv("CC_META_SCALAR") != nullptr;
+    sw.derive_separate = getenv("CC_DERIVE_SEPARATE") != nullptr;
+    sw.gr_by_pair = getenv("CC_GR_BY_PAIR") != nullptr;
+    sw.deep_sort = getenv("CC_DEEP_SORT") != nullptr;
+    sw.trace_upload = getenv("CC_TRACE_UPLOAD") != nullptr;
+    return sw;
+}
+
 }  // namespace
 
 struct BgzfEnc;   // the device BGZF encoder's streams and buffers (bgzf_deflate.hip.inc)
@@ -5337,6 +5362,7 @@ struct cc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
+    EngineSwitches sw;              // as the entry point now running read them (read_switches), not kept across calls
     std::map<int32_t, DevTable> tables;
     std::map<int32_t, std::vector<void*>> table_allocs;
     std::map<int32_t, std::unique_ptr<Group>> groups;
@@ -5555,8 +5581,7 @@ int scan_launch(cc_ctx* ctx, const TIn* in, int64_t n, uint32_t* d_tot, const ch
     uintptr_t al = (uintptr_t)in;
     if constexpr (Emit::kPlain) al |= (uintptr_t)em.out;
     if (al & 15u) { ctx->err = "scan operands must be 16-B aligned"; return CC_E_INVALID; }
-    const char* force = getenv("CC_SCAN1");
-    const bool one = !ctx->scan_two && (force ? force[0] == '1' : nb <= SCAN_ONE_MAX);
+    const bool one = !ctx->scan_two && (ctx->sw.scan1 >= 0 ? ctx->sw.scan1 == 1 : nb <= SCAN_ONE_MAX);
     if (one && nb > 0) {
         if (nb > ctx->scan_cap) {
             const int64_t cap = std::max<int64_t>(nb, 1 << 14);
@@ -5659,10 +5684,19 @@ uint32_t* plan_stripes(cc_ctx* ctx, Group& g, uint32_t* slot, int* rc) {
     return st + (slot - (uint32_t*)g.buf["plan_totals"].p) * (int64_t)PSTRIPES * PSTRIDE;
 }
 
+// The plan as a planned pass sees it: whether it holds a total, and the total or a default (an exact
+// pass: never, and the default).  Neither adds a key: the plan's keys are the totals that exist.
+inline bool has_plan(const Group& g, const char* name) { return g.fast && g.plan.count(name) != 0; }
+inline int64_t plan_or(const Group& g, const char* name, int64_t dflt) {
+    if (!g.fast) return dflt;
+    const auto it = g.plan.find(name);
+    return it != g.plan.end() ? it->second : dflt;
+}
+
 // A device total: on a planned re-run the plan's value (checked at the end), otherwise read back
 // now (synchronises) and recorded in the plan.
 int planned_total(cc_ctx* ctx, Group& g, const char* name, uint32_t* d_tot, int64_t* total) {
-    if (g.fast && g.plan.count(name)) {
+    if (has_plan(g, name)) {
         *total = g.plan[name];
         g.verify.push_back(name);
         return 0;
@@ -6175,7 +6209,8 @@ extern "C" {
 int cc_table_derive(cc_ctx* ctx, int32_t table_id) {
     if (!ctx || !ctx->tables.count(table_id)) return CC_E_INVALID;
     if (ctx->tables[table_id].host_layout) return 0;   // its derived columns are part of its input
-    if (getenv("CC_DERIVE_SEPARATE")) return derive_table(ctx, ctx->tables[table_id]);
+    ctx->sw = read_switches();
+    if (ctx->sw.derive_separate) return derive_table(ctx, ctx->tables[table_id]);
     ctx->tables[table_id].derive_pending = true;   // (built by the next read_bam pass on the table)
     return 0;
 }
@@ -6183,6 +6218,7 @@ int cc_table_derive(cc_ctx* ctx, int32_t table_id) {
 int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* table_id) {
     if (!ctx || !r || !table_id) return CC_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
     int32_t id = ctx->next_id++;
     std::vector<void*>& al = ctx->table_allocs[id];
     DevTable T;
@@ -6212,11 +6248,7 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
     T.qn_bytes = r->qn_blob_bytes;
     if (!r->rdig) { ctx->err = "cc_records.rdig is required"; return CC_E_INVALID; }
     RC(upload(ctx, al, &T.rdig, r->rdig, r->n));
-    T.qdig_mask = ~0ULL;
-    if (const char* qb = getenv("CC_QDIG_BITS")) {
-        const int k = atoi(qb);
-        if (k > 0 && k < 64) T.qdig_mask = (1ULL << k) - 1;
-    }
+    T.qdig_mask = ctx->sw.qdig_bits ? (1ULL << ctx->sw.qdig_bits) - 1 : ~0ULL;
     // the decoder's layout (cc_records' derived columns) is uploaded as it is; the digest-width test
     // knob (CC_QDIG_BITS) takes the device derivation, which applies the mask
     T.host_layout = r->meta && r->rkey && r->core && r->qn_ol && r->qdig && r->rdeep && r->dlist && r->ext &&
@@ -6287,7 +6319,7 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
         }
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));   // the uploads read caller memory
-    if (getenv("CC_TRACE_UPLOAD"))
+    if (ctx->sw.trace_upload)
         fprintf(stderr, "[cc] table %d: %lld records, %lld deep groups, %s layout\n", id, (long long)T.n,
                 (long long)T.n_deep, T.host_layout ? "decoder" : "device");
     ctx->tables[id] = T;
@@ -6300,14 +6332,14 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
 namespace {
 // Per-pass table preparation (timed with the pass): the member records; on a coordinate-sorted table
 // also the position keys, the read-end map and the bucket geometry.  No host synchronisation.
-int prep_table(cc_ctx* ctx, const DevTable& T, bool coord, Fills& fill, int32_t* rec_e,
-               int32_t* dlist = nullptr, uint32_t* ndeep = nullptr, int64_t dcap = 0) {
+int prep_table(cc_ctx* ctx, const DevTable& T, Fills& fill, int32_t* rec_e) {
     RC(fill.launch());
     if (T.n <= 0) return 0;
     {
+        // (no deep-group list: that is the table's, listed by k_derive)
         ProfScope ps(ctx, "k_build_meta");
         hipLaunchKernelGGL(k_build_meta, dim3(nblk(T.n, BC_T)), dim3(BC_T), 0, ctx->stream, T, rec_e, ctx->d_err,
-                           coord ? dlist : (int32_t*)nullptr, ndeep, dcap);
+                           (int32_t*)nullptr, (uint32_t*)nullptr, (int64_t)0);
     }
     // (the bucket geometry from each tid's extent: built by the SC join that uses it, build_fam_buckets)
     return 0;
@@ -6452,60 +6484,121 @@ int vote_families(cc_ctx* ctx, Group& g, const DevTable& T, int64_t NE, uint8_t*
 // ------------------------------------------------------------------ read_bam pipeline
 namespace {
 
-int read_bam_pass(cc_ctx* ctx, int32_t gid) {
-    Group& g = *ctx->groups[gid];
-    const DevTable& T = ctx->tables[g.table];
-    const int64_t S = g.S;
-    int brc = 0;
-    int32_t* d_srec = (int32_t*)g.buf["stream_rec"].p;
-    int32_t* d_sreg = (int32_t*)g.buf["stream_region"].p;
-    int32_t* d_run = (int32_t*)g.buf["region_run"].p;
-    uint32_t* d_nresid = plan_slot(ctx, g, "n_resid", &brc);       // count-only totals (wave atomics)
-    uint32_t* d_nbig = plan_slot(ctx, g, "n_big", &brc);
-    uint32_t* d_ndrop = plan_slot(ctx, g, "n_drop", &brc);
-    if (brc) return brc;
-    const bool coord = g.coord_sorted && S > 0;             // sorted table: position-group grouping
-    const bool coord_pair = coord && !g.force_sort;         // and the mate search by coordinates
+// One read_bam pass over a group's resident stream.  The object holds what crosses the pass's phases:
+// the mode flags, the sizes each phase establishes, and views of the device buffers that more than
+// one phase reads (g.buf owns the memory; a buffer of one phase is a local of that phase).  The
+// phases run once each, in the order read_bam_pass lists them.
+struct ReadBamPass {
+    cc_ctx* ctx;
+    Group& g;
+    const DevTable& T;
+    const EngineSwitches& sw;
+    Fills fill;           // the zeroed words gathered since the last k_fill launch
+    int brc = 0;          // (GB's status)
+    const int64_t S, N;   // stream entries, table records
+    // ---- modes
+    const bool coord;        // sorted table: position-group grouping
+    const bool coord_pair;   // and the mate search by coordinates
     // the votes' member records: written as the ends are ranked by the pass whose stage votes
     // families (the SSCS stage's, the one that lists bad reads); built on demand otherwise
-    const bool members = g.badread != 0;
+    const bool members;
+    // an identity stream on a sorted table: the table preparation and the filters in one pass over
+    // the records (k_build_meta_cls); otherwise the preparation, then the stream's filters
+    const bool fused;
+    bool lpart = false;   // found pairs checked by the partitioned check (k_lp_*), not the long-pair table
+    bool pre_ends = false, pre_csn = false, drop_zeroed = false;   // in the first fill: cflag, csn_ht_key, fam_drop
+    // ---- sizes, each set by the phase that establishes it
+    int64_t NDG = 0;               // the table's deep position groups (filters)
+    int64_t P = 0, R = 0;          // completed pairs, read ends (pair_keys)
+    int64_t n_known = 0;           // mem_rec[0, n_known) written by k_group_rank (grouping)
+    int64_t n_deep = 0;            // read ends in deep position groups (grouping)
+    int64_t F = 0, V = 0, E = 0;   // families, members kept (families); csn entries (csn)
+    // ---- outcomes
+    bool deep_q = false;            // k_deep_qsort bucketed the deep groups (their extents: gend)
+    bool sorted_pairing = false;    // k_pair_mark ran (the only source of n_multi)
+    bool deep_same_group = false;   // the deep ends' sort keys are group-major (equal keys: one position group)
+    bool deep_ranked = false;       // k_deep_fam ranked them (no sort, no k_fam_mark)
+    // ---- views, by the phase that makes them.  setup: the stream, the count-only totals (wave atomics),
+    // the long-pair table or the partitioned check's found pairs, a bed stream's scattered keys
+    int32_t *d_srec = nullptr, *d_sreg = nullptr, *d_run = nullptr;
+    uint32_t *d_nresid = nullptr, *d_nbig = nullptr, *d_ndrop = nullptr, *n_long = nullptr, *d_nmulti = nullptr;
+    uint64_t lsize = 1 << 10;
+    unsigned long long* ltab = nullptr;
+    uint64_t* pkeys = nullptr;
+    uint32_t* pcount = nullptr;
+    uint32_t pcap = 0;
+    uint64_t* rq = nullptr;     // identity streams read the stream keys instead
+    int32_t* spos = nullptr;    // and a record index as the stream slot
+    int32_t* rec_e = nullptr;   // a sorted table's read end per record (k_build_meta, then EmitPairs)
+    // filters: the stream's qname keys and their sort's output, mates and pair flags
+    uint64_t *skey = nullptr, *skey2 = nullptr;
+    uint32_t *sval = nullptr, *sval2 = nullptr;
+    int32_t *mate_of = nullptr, *partner = nullptr, *claims = nullptr;
+    uint8_t* pflag = nullptr;
+    // pairing (k_deep_qsort): the deep groups' extents; per record its deep group, for the deep tag sort
+    int32_t* gend = nullptr;
+    uint32_t* deep_gid = nullptr;
+    // pair_keys: the pairs, their hashes (tags by read end on the sort path, else by record), the ranked ends
+    int32_t *pr_rec1 = nullptr, *pr_region = nullptr;
+    PairView PV{};
+    uint64_t *chash = nullptr, *thash = nullptr, *rhash = nullptr, *rs_key = nullptr;
+    uint32_t *tval = nullptr, *rs_val = nullptr, *bigE = nullptr;
+    int4* rtag = nullptr;
+    uint8_t* cflag = nullptr;
+    // grouping: the members (mem_meta only where the pass writes the member records)
+    int32_t* mem_rec = nullptr;
+    uint8_t* segf = nullptr;
+    uint32_t* mem_valid = nullptr;
+    uint4* mem_meta = nullptr;
+    // families
+    int32_t *fam_beg = nullptr, *fam_end = nullptr, *fam_first = nullptr, *fam_region = nullptr, *fam_o = nullptr;
+    int32_t *fam_by_k = nullptr, *pair_by_k = nullptr;
+
+    ReadBamPass(cc_ctx* c, Group& gr)
+        : ctx(c), g(gr), T(c->tables[gr.table]), sw(c->sw), fill(c), S(gr.S), N(T.n),
+          coord(gr.coord_sorted && S > 0), coord_pair(coord && !gr.force_sort), members(gr.badread != 0),
+          fused(gr.ident && coord_pair && S == N && N > 0) {}
+    int setup(), filters(), pairing(), pair_keys(), grouping(), families(), csn();   // the phases, in order
+    int pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_app, uint32_t* rv_app, uint32_t* n_app);
+    int pair_mark(int64_t n);
+    int rank_deep_in_place(int64_t NS, int64_t NB);
+};
+
+// The plan's slots, the long-pair check's form and size, and the pass's first fill set.
+int ReadBamPass::setup() {
+    d_srec = (int32_t*)g.buf["stream_rec"].p;
+    d_sreg = (int32_t*)g.buf["stream_region"].p;
+    d_run = (int32_t*)g.buf["region_run"].p;
+    d_nresid = plan_slot(ctx, g, "n_resid", &brc);
+    d_nbig = plan_slot(ctx, g, "n_big", &brc);
+    d_ndrop = plan_slot(ctx, g, "n_drop", &brc);
+    if (brc) return brc;
     g.members_built = false;
     // the long pairs' keys (k_pair_coord_tile, k_pair_resid): at least twice the long pairs of the last
     // exact pass (deep groups' pairs are long), an exact pass room for every pair; more long pairs
     // than fit send the pass to the sort path
-    uint32_t* n_long = plan_slot(ctx, g, "n_long", &brc);
+    n_long = plan_slot(ctx, g, "n_long", &brc);
     if (brc) return brc;
-    uint64_t lsize = 1 << 10;
     {
-        const uint64_t want = g.fast && g.plan.count("n_long") ? (uint64_t)(2 * g.plan["n_long"]) + (uint64_t)S / 16
-                                                               : (uint64_t)S;
+        const uint64_t want = has_plan(g, "n_long") ? (uint64_t)(2 * plan_or(g, "n_long", 0)) + (uint64_t)S / 16
+                                                    : (uint64_t)S;
         while (lsize < want) lsize <<= 1;
     }
-    unsigned long long* ltab = nullptr;
-    // CC_LTAB_OFF=1: measurement only (what the long-pair check costs), never for results
     // A planned pass with many long pairs (deep targeted panels, config C4: every pair spans more than
     // PD_W entries) checks for a qname in two found pairs by the partitioned check (k_lp_*) instead of
     // the long-pair table's scattered CAS; CC_LTAB_CAS=1 keeps the table
     // (CC_LP_MIN=k: from k planned long pairs; 0: every pass, exact ones too -- the tests' switch)
-    const char* lpm = getenv("CC_LP_MIN");
-    const int64_t lp_min = lpm ? atoll(lpm) : LP_MIN;
-    const bool lpart = coord_pair && !getenv("CC_LTAB_CAS") &&
-                       (lp_min == 0 || (g.fast && g.plan.count("n_long") && g.plan.count("scan_pairs") &&
-                                        g.plan["n_long"] >= lp_min));
-    if (coord_pair && !lpart && !getenv("CC_LTAB_OFF")) ltab = GB(unsigned long long, "pc_ltab", (int64_t)lsize);
-    uint64_t* pkeys = nullptr;
-    uint32_t* pcount = nullptr;
-    uint32_t pcap = 0;
+    lpart = coord_pair && !sw.ltab_cas &&
+            (sw.lp_min == 0 || (has_plan(g, "n_long") && has_plan(g, "scan_pairs") && plan_or(g, "n_long", 0) >= sw.lp_min));
+    if (coord_pair && !lpart) ltab = GB(unsigned long long, "pc_ltab", (int64_t)lsize);
     if (lpart) {
         // found pairs: at most the pass's pairs (planned), at most half the stream entries (exact)
-        pcap = (uint32_t)std::min<int64_t>((g.fast && g.plan.count("scan_pairs") ? g.plan["scan_pairs"] : S / 2) + 4096,
-                                           INT32_MAX);
+        pcap = (uint32_t)std::min<int64_t>(plan_or(g, "scan_pairs", S / 2) + 4096, INT32_MAX);
         pkeys = GB(uint64_t, "pc_pkeys", pcap);
         pcount = plan_slot(ctx, g, "lp_found", &brc);   // (a counter: zeroed with the plan totals)
         if (brc) return brc;
     }
     // the pass's zeroed words, one launch with the table preparation's
-    Fills fill(ctx);
     RC(fill.add(ctx->d_err, 4, 0u));
     RC(fill.add(ctx->d_cnt, sizeof(unsigned long long) * CC_NUM_COUNTERS * CNT_STRIPES, 0u));
     RC(fill.add(g.buf["plan_totals"].p, 4 * PLAN_SLOTS, 0u));
@@ -6516,25 +6609,24 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
     g.stripes_pending = false;
     if (ltab) RC(fill.add(ltab, sizeof(unsigned long long) * lsize, ~0u));
     // a planned pass knows its family count: the per-family drop counts are zeroed here too
-    bool drop_zeroed = false;
-    if (g.fast && g.plan.count("scan_fam") && g.plan["scan_fam"] > 0) {
-        int32_t* fd = GB(int32_t, "fam_drop", g.plan["scan_fam"]);
-        RC(fill.add(fd, sizeof(int32_t) * g.plan["scan_fam"], 0u));
+    const int64_t Fp = plan_or(g, "scan_fam", 0);
+    if (Fp > 0) {
+        int32_t* fd = GB(int32_t, "fam_drop", Fp);
+        RC(fill.add(fd, sizeof(int32_t) * Fp, 0u));
         drop_zeroed = true;
     }
     // a planned pass knows the sizes of the tables it zeroes later (the read ends' creation and deep
     // flags, csn_pair_dict's table): they are zeroed by the pass's first fill too (two launches fewer)
-    bool pre_ends = false, pre_csn = false;
-    if (g.fast && g.plan.count("scan_pairs") && g.plan.count("scan_fam")) {
-        const int64_t Rp = 2 * g.plan["scan_pairs"], Fp = g.plan["scan_fam"];
-        const bool deep_planned = !g.coord_sorted || Rp == 0 || g.plan.count("n_big");
+    if (has_plan(g, "scan_pairs") && has_plan(g, "scan_fam")) {
+        const int64_t Rp = 2 * plan_or(g, "scan_pairs", 0);
+        const bool deep_planned = !g.coord_sorted || Rp == 0 || has_plan(g, "n_big");
         if (Rp > 0 && deep_planned) {
             uint8_t* cf = GB(uint8_t, "cflag", (Rp + 15) & ~15LL);
             RC(fill.add(cf, ((size_t)Rp + 15) & ~(size_t)15, 0u));
             pre_ends = true;
         }
         if (Fp > 0 && deep_planned) {
-            const int64_t nd = g.coord_sorted && Rp > 0 ? g.plan["n_big"] : 0;
+            const int64_t nd = g.coord_sorted && Rp > 0 ? plan_or(g, "n_big", 0) : 0;
             const bool tiles = g.coord_sorted && g.ident && Rp > 0;
             uint64_t size = 1024;
             while (size < (uint64_t)(tiles ? 2 * std::min(nd, Fp) : 2 * Fp)) size <<= 1;   // (csn_table_size)
@@ -6545,47 +6637,35 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
     }
     // a bed stream's keys and slots scattered to its records (k_scatter_stream) for the mate search;
     // records outside the stream keep the all-ones fill (key ~0, slot -1)
-    uint64_t* rq = nullptr;    // identity streams read the stream keys instead
-    int32_t* spos = nullptr;   // and a record index as the stream slot
     if (coord_pair && !g.ident) {
-        rq = GB(uint64_t, "pc_rq", T.n);
-        spos = GB(int32_t, "pc_spos", T.n);
-        RC(fill.add(rq, sizeof(uint64_t) * T.n, ~0u));
-        RC(fill.add(spos, sizeof(int32_t) * T.n, ~0u));
+        rq = GB(uint64_t, "pc_rq", N);
+        spos = GB(int32_t, "pc_spos", N);
+        RC(fill.add(rq, sizeof(uint64_t) * N, ~0u));
+        RC(fill.add(spos, sizeof(int32_t) * N, ~0u));
     }
-    // ---- 0. the table's per-record cores (and position keys when sorted), part of every pass
-    int32_t* pre = nullptr;
-    if (g.coord_sorted && T.n > 0) { pre = GB(int32_t, "rec_e", T.n); }
-    // the deep position groups' first records: a property of the table's positions, listed once at
-    // upload and every step (k_derive), for the per-group sorts
-    uint32_t* d_ndg = T.ndeep;
-    const int64_t dcap = 0;
-    int32_t* dlist = nullptr;
-    if (g.coord_sorted && T.n > 0) dlist = T.dlist;
-    // ---- 1. filters + qname keys (consensus_helper.py:389-426)
-    uint64_t* skey = GB(uint64_t, "skey", S);
-    uint32_t* sval = GB(uint32_t, "sval", S);
-    uint64_t* skey2 = GB(uint64_t, "skey2", S);
-    uint32_t* sval2 = GB(uint32_t, "sval2", S);
+    if (g.coord_sorted && N > 0) rec_e = GB(int32_t, "rec_e", N);
+    return 0;
+}
+
+// ---- 0. the table's per-record cores (and position keys when sorted), part of every pass
+// ---- 1. filters + qname keys (consensus_helper.py:389-426)
+int ReadBamPass::filters() {
+    skey = GB(uint64_t, "skey", S);
+    sval = GB(uint32_t, "sval", S);
+    skey2 = GB(uint64_t, "skey2", S);
+    sval2 = GB(uint32_t, "sval2", S);
     uint8_t* badflag = GB(uint8_t, "badflag", (S + 15) & ~15LL);   // byte flags (16-B padded for the scan)
-    int32_t* mate_of = GB(int32_t, "mate_of", S);
-    uint8_t* pflag = GB(uint8_t, "pflag", (S + 15) & ~15LL);
-    const int64_t N = T.n;
-    int32_t* partner = nullptr;
-    int32_t* claims = nullptr;
+    mate_of = GB(int32_t, "mate_of", S);
+    pflag = GB(uint8_t, "pflag", (S + 15) & ~15LL);
     if (coord_pair) {
         partner = GB(int32_t, "pc_partner", S);
         claims = GB(int32_t, "pc_claims", S);
     }
     const ClassifyOut co{skey, coord_pair ? nullptr : sval, g.badread ? badflag : nullptr, mate_of,
                          g.ident ? nullptr : partner, claims, pflag};
-    // an identity stream on a sorted table: the table preparation and the filters in one pass over
-    // the records (k_build_meta_cls); otherwise the preparation, then the stream's filters
-    const bool fused = g.ident && coord_pair && S == T.n && T.n > 0;
-    const char* qd = getenv("CC_QDIG");   // "0": the qname bytes hashed in every pass (measurement)
-    const int use_dig = ctx->full_qhash.count(g.table) || (qd && qd[0] == '0') ? 0 : 1;
+    const int use_dig = ctx->full_qhash.count(g.table) || !sw.qdig ? 0 : 1;
     DevTable& Tm = ctx->tables[g.table];
-    if (Tm.derive_pending && !(fused && !co.sval && !co.partner)) {
+    if (Tm.derive_pending && !fused) {
         RC(derive_table(ctx, Tm));   // (the pass's own preparation below)
         Tm.derive_pending = false;
     }
@@ -6594,270 +6674,255 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
         RC(fill.add(Tm.ndeep, 16, 0u));
         RC(fill.launch());
         ProfScope ps(ctx, "k_derive");
-        hipLaunchKernelGGL(k_derive<true>, dim3(nblk(T.n, GT)), dim3(GT), 0, ctx->stream, T, Tm.dlist, Tm.ndeep,
-                           T.n / DEEP_MIN + 2,
+        hipLaunchKernelGGL(k_derive<true>, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, T, Tm.dlist, Tm.ndeep,
+                           N / DEEP_MIN + 2,
                            DeriveCls{(const int32_t*)d_sreg, (const int32_t*)d_run, g.delim_filter, g.badread, g.scoped,
-                                     use_dig, g.seed, co, ctx->d_cnt, pre, ctx->d_err});
+                                     use_dig, g.seed, co, ctx->d_cnt, rec_e, ctx->d_err});
         Tm.derive_pending = false;
     } else if (fused) {
         RC(fill.launch());
-        {
-            ProfScope ps(ctx, "k_build_meta_cls");
-            if (!co.sval && !co.partner && !getenv("CC_META_SCALAR"))
-                hipLaunchKernelGGL(k_build_meta_cls4, dim3(nblk(T.n, BC_T * BM4)), dim3(BC_T), 0, ctx->stream, T, pre,
-                                   ctx->d_err, (const int32_t*)d_sreg, (const int32_t*)d_run, g.delim_filter, g.badread,
-                                   g.scoped, g.seed, use_dig, co, ctx->d_cnt);
-            else
-                hipLaunchKernelGGL(k_build_meta_cls, dim3(nblk(T.n, BC_T)), dim3(BC_T), 0, ctx->stream, T, pre,
-                                   ctx->d_err, (int32_t*)nullptr, (uint32_t*)nullptr, dcap, (const int32_t*)d_sreg,
-                                   (const int32_t*)d_run, g.delim_filter, g.badread, g.scoped, g.seed, use_dig, co,
-                                   ctx->d_cnt);
-        }
+        ProfScope ps(ctx, "k_build_meta_cls");
+        if (!sw.meta_scalar)
+            hipLaunchKernelGGL(k_build_meta_cls4, dim3(nblk(N, BC_T * BM4)), dim3(BC_T), 0, ctx->stream, T, rec_e,
+                               ctx->d_err, (const int32_t*)d_sreg, (const int32_t*)d_run, g.delim_filter, g.badread,
+                               g.scoped, g.seed, use_dig, co, ctx->d_cnt);
+        else
+            hipLaunchKernelGGL(k_build_meta_cls, dim3(nblk(N, BC_T)), dim3(BC_T), 0, ctx->stream, T, rec_e,
+                               ctx->d_err, (int32_t*)nullptr, (uint32_t*)nullptr, (int64_t)0, (const int32_t*)d_sreg,
+                               (const int32_t*)d_run, g.delim_filter, g.badread, g.scoped, g.seed, use_dig, co,
+                               ctx->d_cnt);
     } else {
-        RC(prep_table(ctx, T, g.coord_sorted != 0, fill, pre));
+        RC(prep_table(ctx, T, fill, rec_e));
         if (S > 0) {
             ProfScope ps(ctx, "k_classify");
             hipLaunchKernelGGL(k_classify, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, g.ident, d_srec, d_sreg, d_run, T,
                                g.delim_filter, g.badread, g.scoped, g.seed, use_dig, co, ctx->d_cnt);
         }
     }
-    const int64_t NDG = dlist ? T.n_deep : 0;
+    // the deep position groups' first records (T.dlist, T.ndeep): a property of the table's positions,
+    // listed once at upload and every step (k_derive), for the per-group sorts
+    NDG = g.coord_sorted && N > 0 ? T.n_deep : 0;
     g.n_deepg = NDG;
-    uint32_t* deep_gid = nullptr;   // per record its deep group (k_deep_qsort), for the deep tag sort
-    bool deep_q = false;            // k_deep_qsort bucketed the deep groups (their extents: gend)
-    // ---- 2. pair_dict: mates by qname
-    uint32_t* d_nmulti = plan_slot(ctx, g, "n_multi", &brc);   // qnames seen more than twice (k_pair_mark)
+    return 0;
+}
+
+// ---- 2. pair_dict: mates by qname
+int ReadBamPass::pairing() {
+    d_nmulti = plan_slot(ctx, g, "n_multi", &brc);   // qnames seen more than twice (k_pair_mark)
     if (brc) return brc;
-    bool sorted_pairing = false;   // k_pair_mark ran (the only source of n_multi)
-    uint64_t* rk_app = nullptr;     // the residual keys in append order (k_pair_resid) and their count
+    if (!coord_pair) {
+        RC(sort_pairs(ctx, skey, skey2, sval, sval2, S, "sort_qname"));
+        return S > 0 ? pair_mark(S) : 0;
+    }
+    const uint64_t* rkey = T.rkey;   // (the table's position keys, k_derive)
+    uint8_t* resid = GB(uint8_t, "pc_resid", (S + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+    uint64_t* rk_app = nullptr;   // the residual keys in append order (k_pair_resid) and their count
     uint32_t* rv_app = nullptr;
     uint32_t* n_app = nullptr;
-    if (coord) {
-        uint64_t* rkey = T.rkey;   // (the table's position keys, k_derive)
-        int32_t* rec_e = GB(int32_t, "rec_e", N);
-        if (coord_pair) {
-            uint8_t* resid = GB(uint8_t, "pc_resid", (S + 15) & ~15LL);   // byte flags (16-B padded for the scan)
-            if (!g.ident) {
-                ProfScope ps(ctx, "k_pair_coord");
-                hipLaunchKernelGGL(k_scatter_stream, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, g.ident, d_srec, skey, spos, rq);
-            }
-            const uint64_t* qk = g.ident ? (const uint64_t*)skey : (const uint64_t*)rq;
-            // deep position groups: each group's records sorted by qname key (the search bisects there)
-            uint64_t* gq = nullptr;
-            int32_t* gend = nullptr;
-            uint32_t* boff = nullptr;
-            unsigned long long* dgk = nullptr;   // 16-B entries (dg_insert)
-            uint64_t dgsize = 64;
-            if (NDG > 0) {
-                while (dgsize < (uint64_t)(2 * NDG)) dgsize <<= 1;
-                gq = GB(uint64_t, "deep_gq", N);
-                gend = GB(int32_t, "deep_gend", N);
-                boff = GB(uint32_t, "deep_boff", N + 1);
-                // the records' deep group ids key the deep ends' sort, which a planned pass whose deep
-                // groups all ranked in place (k_deep_fam, no overflow) does not run
-                const bool ranked_plan = g.fast && g.plan.count("deep_ovf") && g.plan["deep_ovf"] == 0 &&
-                                         !g.no_deep_fam && !getenv("CC_DEEP_SORT");
-                if (!ranked_plan) deep_gid = GB(uint32_t, "deep_gid", N);
-                deep_q = true;
-                dgk = GB(unsigned long long, "deep_dgk", 2 * (int64_t)dgsize);
-                RC(fill.add(dgk, sizeof(unsigned long long) * 2 * dgsize, 0xFFFFFFFEu));
-                RC(fill.launch());
-                ProfScope pq(ctx, "k_deep_qsort");
-                hipLaunchKernelGGL(k_deep_qsort, dim3((unsigned)std::min<int64_t>(NDG, CC_DQ_GRID)), dim3(DQ_T), 0, ctx->stream,
-                                   (const uint32_t*)d_ndg, (const int32_t*)dlist, N, (const uint64_t*)rkey, qk, gq, gend,
-                                   boff, dgk, dgsize - 1, deep_gid);
-            }
-            uint32_t* lst = plan_stripes(ctx, g, n_long, &brc);
-            if (brc) return brc;
-            ProfScope ps(ctx, "k_pair_coord");   // (after k_deep_qsort's own scope: scopes do not nest)
-            // the search runs over the table's records (coordinate order) with their qname keys staged
-            // in LDS per tile: the stream keys themselves on an identity stream, else scattered to the
-            // records by k_scatter_stream (rq, and each record's stream slot spos)
-            const char* pct = getenv("CC_PC_TILE");   // 512 / 1024: force a tile size (measurements)
-            const bool small = pct ? atoi(pct) == 512 : N < PC_SMALL_N;
-            if (small)
-                hipLaunchKernelGGL(k_pair_coord_tile<512>, dim3(nblk(N, 512)), dim3(256), 0, ctx->stream, N, qk,
-                                   g.ident ? (const int32_t*)nullptr : (const int32_t*)spos, rkey, T, partner, claims,
-                                   mate_of, pflag, ltab, lsize - 1, lst, ctx->d_err, (const uint64_t*)gq,
-                                   (const int32_t*)gend, (const uint32_t*)boff, (const unsigned long long*)dgk,
-                                   dgsize - 1, pkeys, pcount, pcap);
-            else
-                hipLaunchKernelGGL(k_pair_coord_tile<1024>, dim3(nblk(N, 1024)), dim3(256), 0, ctx->stream, N, qk,
-                                   g.ident ? (const int32_t*)nullptr : (const int32_t*)spos, rkey, T, partner, claims,
-                                   mate_of, pflag, ltab, lsize - 1, lst, ctx->d_err, (const uint64_t*)gq,
-                                   (const int32_t*)gend, (const uint32_t*)boff, (const unsigned long long*)dgk,
-                                   dgsize - 1, pkeys, pcount, pcap);
-            hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, lst, n_long);
-            uint32_t* st = plan_stripes(ctx, g, d_nresid, &brc);
-            if (brc) return brc;
-            // the residual keys appended as they are flagged (the table pairing's input without the scan)
-            rk_app = GB(uint64_t, "pc_rk_app", S);
-            rv_app = GB(uint32_t, "pc_rv_app", S);
-            n_app = plan_slot(ctx, g, "resid_app", &brc);   // (zeroed with the plan totals; not checked)
-            if (brc) return brc;
-            hipLaunchKernelGGL(k_pair_resid, dim3((unsigned)((S + PD_TILE - 1) / PD_TILE)), dim3(256), 0, ctx->stream, S,
-                               skey, partner, claims, resid, st, ltab, lsize - 1, n_long, ctx->d_err, rk_app, rv_app, n_app);
-            // a planned pass leaves the count striped: the end-of-pass check folds it (k_defer_pack)
-            if (g.fast && g.plan.count("n_resid")) g.stripes_pending = true;
-            else hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, st, d_nresid);
+    {   // the coordinate search (one k_pair_coord scope from the tile search on)
+        if (!g.ident) {
+            ProfScope ps(ctx, "k_pair_coord");
+            hipLaunchKernelGGL(k_scatter_stream, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, g.ident, d_srec, skey, spos, rq);
         }
+        const uint64_t* qk = g.ident ? (const uint64_t*)skey : (const uint64_t*)rq;
+        // deep position groups: each group's records sorted by qname key (the search bisects there)
+        uint64_t* gq = nullptr;
+        uint32_t* boff = nullptr;
+        unsigned long long* dgk = nullptr;   // 16-B entries (dg_insert)
+        uint64_t dgsize = 64;
+        if (NDG > 0) {
+            while (dgsize < (uint64_t)(2 * NDG)) dgsize <<= 1;
+            gq = GB(uint64_t, "deep_gq", N);
+            gend = GB(int32_t, "deep_gend", N);
+            boff = GB(uint32_t, "deep_boff", N + 1);
+            // the records' deep group ids key the deep ends' sort, which a planned pass whose deep
+            // groups all ranked in place (k_deep_fam, no overflow) does not run
+            const bool ranked_plan = plan_or(g, "deep_ovf", 1) == 0 && !g.no_deep_fam && !sw.deep_sort;
+            if (!ranked_plan) deep_gid = GB(uint32_t, "deep_gid", N);
+            deep_q = true;
+            dgk = GB(unsigned long long, "deep_dgk", 2 * (int64_t)dgsize);
+            RC(fill.add(dgk, sizeof(unsigned long long) * 2 * dgsize, 0xFFFFFFFEu));
+            RC(fill.launch());
+            ProfScope pq(ctx, "k_deep_qsort");
+            hipLaunchKernelGGL(k_deep_qsort, dim3((unsigned)std::min<int64_t>(NDG, CC_DQ_GRID)), dim3(DQ_T), 0, ctx->stream,
+                               (const uint32_t*)T.ndeep, (const int32_t*)T.dlist, N, rkey, qk, gq, gend, boff, dgk,
+                               dgsize - 1, deep_gid);
+        }
+        uint32_t* lst = plan_stripes(ctx, g, n_long, &brc);
+        if (brc) return brc;
+        ProfScope ps(ctx, "k_pair_coord");   // (after k_deep_qsort's own scope: scopes do not nest)
+        // the search runs over the table's records (coordinate order) with their qname keys staged
+        // in LDS per tile: the stream keys themselves on an identity stream, else scattered to the
+        // records by k_scatter_stream (rq, and each record's stream slot spos)
+        const bool small = sw.pc_tile ? sw.pc_tile == 512 : N < PC_SMALL_N;   // (CC_PC_TILE: measurements)
+        const auto k_tile = small ? k_pair_coord_tile<512> : k_pair_coord_tile<1024>;
+        hipLaunchKernelGGL(k_tile, dim3(nblk(N, small ? 512 : 1024)), dim3(256), 0, ctx->stream, N, qk,
+                           g.ident ? (const int32_t*)nullptr : (const int32_t*)spos, rkey, T, partner, claims,
+                           mate_of, pflag, ltab, lsize - 1, lst, ctx->d_err, (const uint64_t*)gq,
+                           (const int32_t*)gend, (const uint32_t*)boff, (const unsigned long long*)dgk,
+                           dgsize - 1, pkeys, pcount, pcap);
+        hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, lst, n_long);
+        uint32_t* st = plan_stripes(ctx, g, d_nresid, &brc);
+        if (brc) return brc;
+        // the residual keys appended as they are flagged (the table pairing's input without the scan)
+        rk_app = GB(uint64_t, "pc_rk_app", S);
+        rv_app = GB(uint32_t, "pc_rv_app", S);
+        n_app = plan_slot(ctx, g, "resid_app", &brc);   // (zeroed with the plan totals; not checked)
+        if (brc) return brc;
+        hipLaunchKernelGGL(k_pair_resid, dim3((unsigned)((S + PD_TILE - 1) / PD_TILE)), dim3(256), 0, ctx->stream, S,
+                           skey, partner, claims, resid, st, ltab, lsize - 1, n_long, ctx->d_err, rk_app, rv_app, n_app);
+        // a planned pass leaves the count striped: the end-of-pass check folds it (k_defer_pack)
+        if (has_plan(g, "n_resid")) g.stripes_pending = true;
+        else hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, st, d_nresid);
     }
-        if (lpart) {
-            uint32_t* hist = GB(uint32_t, "lp_hist", (int64_t)LP_BUCKETS * LP_NB);
-            uint32_t* off = GB(uint32_t, "lp_off", (int64_t)LP_BUCKETS * LP_NB);
-            uint64_t* bkeys = GB(uint64_t, "lp_bkeys", pcap);
-            uint32_t* lp_tot = plan_slot(ctx, g, "lp_total", &brc);   // (the scan's total; not checked)
-            if (brc) return brc;
-            {
-                ProfScope pl(ctx, "k_lp_check");
-                hipLaunchKernelGGL(k_lp_hist, dim3(LP_NB), dim3(LP_T), 0, ctx->stream, (const uint64_t*)pkeys,
-                                   (const uint32_t*)pcount, pcap, hist);
-            }
-            RC(scan_launch<false>(ctx, (const uint32_t*)hist, (int64_t)LP_BUCKETS * LP_NB, lp_tot, "k_lp_check",
-                                  ScanStore{off}));
+    if (lpart) {   // the partitioned check for a qname in two found pairs
+        uint32_t* hist = GB(uint32_t, "lp_hist", (int64_t)LP_BUCKETS * LP_NB);
+        uint32_t* off = GB(uint32_t, "lp_off", (int64_t)LP_BUCKETS * LP_NB);
+        uint64_t* bkeys = GB(uint64_t, "lp_bkeys", pcap);
+        uint32_t* lp_tot = plan_slot(ctx, g, "lp_total", &brc);   // (the scan's total; not checked)
+        if (brc) return brc;
+        {
             ProfScope pl(ctx, "k_lp_check");
-            hipLaunchKernelGGL(k_lp_scatter, dim3(LP_NB), dim3(LP_T), 0, ctx->stream, (const uint64_t*)pkeys,
-                               (const uint32_t*)pcount, pcap, (const uint32_t*)off, bkeys);
-            hipLaunchKernelGGL(k_lp_dups, dim3(LP_BUCKETS), dim3(LP_T), 0, ctx->stream, (const uint32_t*)pcount, pcap,
-                               (const uint32_t*)off, (const uint64_t*)bkeys, ctx->d_err);
+            hipLaunchKernelGGL(k_lp_hist, dim3(LP_NB), dim3(LP_T), 0, ctx->stream, (const uint64_t*)pkeys,
+                               (const uint32_t*)pcount, pcap, hist);
         }
-    if (coord_pair) {
-        int64_t NL = 0;   // the long pairs: the next planned pass sizes its table from them
-        RC(planned_total(ctx, g, "n_long", n_long, &NL));
-        const uint8_t* resid = (const uint8_t*)g.buf["pc_resid"].p;
-        int64_t NR = 0;
-        RC(planned_total(ctx, g, "n_resid", d_nresid, &NR));
-        if (NR > 0) {
-            // residual reads (mate not found by coordinates): a qname paired by coordinates must not also
-            // be residual (3+ occurrences), then the exact sort path pairs the residual reads.  Their
-            // keys are compacted in the scan of the byte flags (EmitResid), which also fills the exact
-            // table and its Bloom filter that the other entries probe (k_resid_probe); with many residual
-            // reads (more than a quarter of the stream) the sorted keys are searched instead
-            const bool many = NR > S / 4;
-            uint64_t hsize = 1024, bsize = 1024;
-            while (!many && hsize < (uint64_t)(2 * NR)) hsize <<= 1;
-            while (!many && bsize < (uint64_t)(NR / 4 + 1)) bsize <<= 1;   // 16 filter bits per key
-            unsigned long long* rht = nullptr;
-            unsigned long long* bloom = nullptr;
-            uint32_t *hcnt = nullptr, *hmin = nullptr, *hmax = nullptr;
-            uint32_t* d_rmulti = plan_slot(ctx, g, "resid_multi", &brc);
-            if (brc) return brc;
-            if (!many) {
-                rht = GB(unsigned long long, "pc_rht", (int64_t)hsize);
-                bloom = GB(unsigned long long, "pc_bloom", (int64_t)bsize);
-                hcnt = GB(uint32_t, "pc_hcnt", (int64_t)hsize);
-                hmin = GB(uint32_t, "pc_hmin", (int64_t)hsize);
-                hmax = GB(uint32_t, "pc_hmax", (int64_t)hsize);
-                RC(fill.add(rht, sizeof(unsigned long long) * hsize, ~0u));
-                RC(fill.add(bloom, sizeof(unsigned long long) * bsize, 0u));
-                RC(fill.add(hcnt, sizeof(uint32_t) * hsize, 0u));
-                RC(fill.add(hmin, sizeof(uint32_t) * hsize, ~0u));
-                RC(fill.add(hmax, sizeof(uint32_t) * hsize, 0u));
-                RC(fill.launch());
-            }
-            uint64_t* rk = GB(uint64_t, "pc_rk", NR);
-            uint32_t* rv = GB(uint32_t, "pc_rv", NR);
-            int64_t NR2 = 0;
-            // the table from the appended keys (no scan); the sort path (many residual reads, or a key
-            // seen three times or more) takes them compacted in stream order by the scan below
-            const bool appended = !many && rk_app && !getenv("CC_RESID_SCAN");
-            if (appended) {
-                ProfScope ps(ctx, "k_pair_resid");
-                hipLaunchKernelGGL(k_resid_insert, dim3(nblk(NR)), dim3(256), 0, ctx->stream, (const uint32_t*)n_app, NR,
-                                   (const uint64_t*)rk_app, (const uint32_t*)rv_app, rht, hsize - 1, bloom, bsize - 1,
-                                   hcnt, hmin, hmax, d_rmulti, ctx->d_err);
-            } else {
-                RC(scan_emit(ctx, g, resid, S, &NR2, "scan_resid",
-                             EmitResid{skey, rk, rv, NR, rht, hsize - 1, bloom, bsize - 1, ctx->d_err, hcnt, hmin, hmax,
-                                       d_rmulti}));
-            }
-            if (!many) {
-                ProfScope ps(ctx, "k_pair_resid");
-                hipLaunchKernelGGL(k_resid_probe, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, skey, resid,
-                                   (const unsigned long long*)rht, hsize - 1, (const unsigned long long*)bloom, bsize - 1,
-                                   ctx->d_err);
-            }
-            int64_t nmulti_r = 1;
-            if (!many) RC(planned_total(ctx, g, "resid_multi", d_rmulti, &nmulti_r));
-            if (!many && nmulti_r == 0 && !getenv("CC_RESID_SORT")) {
-                // every residual key seen once or twice: paired through the table, no sort
-                ProfScope ps(ctx, "k_pair_mark");
-                hipLaunchKernelGGL(k_resid_pair, dim3(nblk(NR)), dim3(256), 0, ctx->stream, NR,
-                                   (const uint64_t*)(appended ? rk_app : rk), (const uint32_t*)(appended ? rv_app : rv),
-                                   (const unsigned long long*)rht, hsize - 1, (const uint32_t*)hcnt,
-                                   (const uint32_t*)hmin, (const uint32_t*)hmax, g.ident, d_srec, T, mate_of, pflag,
-                                   ctx->d_err, ctx->d_cnt);
-            } else {
-            if (appended)   // (stream order for the sort: the scan's compaction, without the table again)
-                RC(scan_emit(ctx, g, resid, S, &NR2, "scan_resid",
-                             EmitResid{skey, rk, rv, NR, nullptr, 0, nullptr, 0, ctx->d_err, nullptr, nullptr, nullptr,
-                                       nullptr}));
-            RC(sort_pairs(ctx, rk, skey2, rv, sval2, NR, "sort_qname_resid"));
-            if (many) {
-                ProfScope ps(ctx, "k_pair_resid");
-                hipLaunchKernelGGL(k_resid_probe_sorted, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, skey, resid,
-                                   (const uint64_t*)skey2, NR, ctx->d_err);
-            }
-            ProfScope ps(ctx, "k_pair_mark");
-            uint32_t* mst = plan_stripes(ctx, g, d_nmulti, &brc);
-            if (brc) return brc;
-            hipLaunchKernelGGL(k_pair_mark, dim3(nblk(NR)), dim3(256), 0, ctx->stream, NR, skey2, sval2, g.ident, d_srec, T,
-                               mate_of, pflag, ctx->d_err, ctx->d_cnt, mst);
-            sorted_pairing = true;
-            hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, mst, d_nmulti);
-            }
-        }
-    } else {
-        RC(sort_pairs(ctx, skey, skey2, sval, sval2, S, "sort_qname"));
-        if (S > 0) {
-            ProfScope ps(ctx, "k_pair_mark");
-            uint32_t* mst = plan_stripes(ctx, g, d_nmulti, &brc);
-            if (brc) return brc;
-            hipLaunchKernelGGL(k_pair_mark, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, skey2, sval2, g.ident, d_srec, T,
-                               mate_of, pflag, ctx->d_err, ctx->d_cnt, mst);
-            sorted_pairing = true;
-            hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, mst, d_nmulti);
-        }
+        RC(scan_launch<false>(ctx, (const uint32_t*)hist, (int64_t)LP_BUCKETS * LP_NB, lp_tot, "k_lp_check",
+                              ScanStore{off}));
+        ProfScope pl(ctx, "k_lp_check");
+        hipLaunchKernelGGL(k_lp_scatter, dim3(LP_NB), dim3(LP_T), 0, ctx->stream, (const uint64_t*)pkeys,
+                           (const uint32_t*)pcount, pcap, (const uint32_t*)off, bkeys);
+        hipLaunchKernelGGL(k_lp_dups, dim3(LP_BUCKETS), dim3(LP_T), 0, ctx->stream, (const uint32_t*)pcount, pcap,
+                           (const uint32_t*)off, (const uint64_t*)bkeys, ctx->d_err);
     }
-    // ---- 3. completed pairs (records, region, read ends) and their unique_tag / sscs_qname hashes
-    int64_t P = 0;
-    int32_t* pr_rec1 = GB(int32_t, "pr_rec1", S);   // capacity; sized P below
+    int64_t NL = 0;   // the long pairs: the next planned pass sizes its table from them
+    RC(planned_total(ctx, g, "n_long", n_long, &NL));
+    int64_t NR = 0;
+    RC(planned_total(ctx, g, "n_resid", d_nresid, &NR));
+    return NR > 0 ? pair_residual(NR, resid, rk_app, rv_app, n_app) : 0;
+}
+
+// The exact pairing (k_pair_mark) of n sorted keys in skey2 / sval2, and its count of qnames seen more
+// than twice.
+int ReadBamPass::pair_mark(int64_t n) {
+    ProfScope ps(ctx, "k_pair_mark");
+    uint32_t* mst = plan_stripes(ctx, g, d_nmulti, &brc);
+    if (brc) return brc;
+    hipLaunchKernelGGL(k_pair_mark, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, skey2, sval2, g.ident, d_srec, T,
+                       mate_of, pflag, ctx->d_err, ctx->d_cnt, mst);
+    sorted_pairing = true;
+    hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, mst, d_nmulti);
+    return 0;
+}
+
+// The NR residual reads (mate not found by coordinates): a qname paired by coordinates must not also
+// be residual (3+ occurrences), then the exact sort path pairs the residual reads.  Their
+// keys are compacted in the scan of the byte flags (EmitResid), which also fills the exact
+// table and its Bloom filter that the other entries probe (k_resid_probe); with many residual
+// reads (more than a quarter of the stream) the sorted keys are searched instead
+int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_app, uint32_t* rv_app, uint32_t* n_app) {
+    const bool many = NR > S / 4;
+    uint64_t hsize = 1024, bsize = 1024;
+    while (!many && hsize < (uint64_t)(2 * NR)) hsize <<= 1;
+    while (!many && bsize < (uint64_t)(NR / 4 + 1)) bsize <<= 1;   // 16 filter bits per key
+    unsigned long long* rht = nullptr;
+    unsigned long long* bloom = nullptr;
+    uint32_t *hcnt = nullptr, *hmin = nullptr, *hmax = nullptr;
+    uint32_t* d_rmulti = plan_slot(ctx, g, "resid_multi", &brc);
+    if (brc) return brc;
+    if (!many) {
+        rht = GB(unsigned long long, "pc_rht", (int64_t)hsize);
+        bloom = GB(unsigned long long, "pc_bloom", (int64_t)bsize);
+        hcnt = GB(uint32_t, "pc_hcnt", (int64_t)hsize);
+        hmin = GB(uint32_t, "pc_hmin", (int64_t)hsize);
+        hmax = GB(uint32_t, "pc_hmax", (int64_t)hsize);
+        RC(fill.add(rht, sizeof(unsigned long long) * hsize, ~0u));
+        RC(fill.add(bloom, sizeof(unsigned long long) * bsize, 0u));
+        RC(fill.add(hcnt, sizeof(uint32_t) * hsize, 0u));
+        RC(fill.add(hmin, sizeof(uint32_t) * hsize, ~0u));
+        RC(fill.add(hmax, sizeof(uint32_t) * hsize, 0u));
+        RC(fill.launch());
+    }
+    uint64_t* rk = GB(uint64_t, "pc_rk", NR);
+    uint32_t* rv = GB(uint32_t, "pc_rv", NR);
+    int64_t NR2 = 0;
+    // the table from the appended keys (no scan); the sort path (many residual reads, or a key
+    // seen three times or more) takes them compacted in stream order by the scan below
+    const bool appended = !many && !sw.resid_scan;
+    if (appended) {
+        ProfScope ps(ctx, "k_pair_resid");
+        hipLaunchKernelGGL(k_resid_insert, dim3(nblk(NR)), dim3(256), 0, ctx->stream, (const uint32_t*)n_app, NR,
+                           (const uint64_t*)rk_app, (const uint32_t*)rv_app, rht, hsize - 1, bloom, bsize - 1,
+                           hcnt, hmin, hmax, d_rmulti, ctx->d_err);
+    } else {
+        RC(scan_emit(ctx, g, resid, S, &NR2, "scan_resid",
+                     EmitResid{skey, rk, rv, NR, rht, hsize - 1, bloom, bsize - 1, ctx->d_err, hcnt, hmin, hmax,
+                               d_rmulti}));
+    }
+    if (!many) {
+        ProfScope ps(ctx, "k_pair_resid");
+        hipLaunchKernelGGL(k_resid_probe, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, skey, resid,
+                           (const unsigned long long*)rht, hsize - 1, (const unsigned long long*)bloom, bsize - 1,
+                           ctx->d_err);
+    }
+    int64_t nmulti_r = 1;
+    if (!many) RC(planned_total(ctx, g, "resid_multi", d_rmulti, &nmulti_r));
+    if (!many && nmulti_r == 0 && !sw.resid_sort) {
+        // every residual key seen once or twice: paired through the table, no sort
+        ProfScope ps(ctx, "k_pair_mark");
+        hipLaunchKernelGGL(k_resid_pair, dim3(nblk(NR)), dim3(256), 0, ctx->stream, NR,
+                           (const uint64_t*)(appended ? rk_app : rk), (const uint32_t*)(appended ? rv_app : rv),
+                           (const unsigned long long*)rht, hsize - 1, (const uint32_t*)hcnt,
+                           (const uint32_t*)hmin, (const uint32_t*)hmax, g.ident, d_srec, T, mate_of, pflag,
+                           ctx->d_err, ctx->d_cnt);
+        return 0;
+    }
+    if (appended)   // (stream order for the sort: the scan's compaction, without the table again)
+        RC(scan_emit(ctx, g, resid, S, &NR2, "scan_resid",
+                     EmitResid{skey, rk, rv, NR, nullptr, 0, nullptr, 0, ctx->d_err, nullptr, nullptr, nullptr,
+                               nullptr}));
+    RC(sort_pairs(ctx, rk, skey2, rv, sval2, NR, "sort_qname_resid"));
+    if (many) {
+        ProfScope ps(ctx, "k_pair_resid");
+        hipLaunchKernelGGL(k_resid_probe_sorted, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, skey, resid,
+                           (const uint64_t*)skey2, NR, ctx->d_err);
+    }
+    return pair_mark(NR);
+}
+
+// ---- 3. completed pairs (records, region, read ends) and their unique_tag / sscs_qname hashes
+int ReadBamPass::pair_keys() {
+    pr_rec1 = GB(int32_t, "pr_rec1", S);   // capacity; sized P below
     int32_t* pr_rec2 = GB(int32_t, "pr_rec2", S);
-    int32_t* pr_region = GB(int32_t, "pr_region", S);
+    pr_region = GB(int32_t, "pr_region", S);
     RC(scan_emit(ctx, g, pflag, S, &P, "scan_pairs",
-                 EmitPairs{mate_of, g.ident, d_srec, d_sreg, pr_rec1, pr_rec2, pr_region,
-                           g.coord_sorted ? (int32_t*)g.buf["rec_e"].p : nullptr}));
+                 EmitPairs{mate_of, g.ident, d_srec, d_sreg, pr_rec1, pr_rec2, pr_region, rec_e}));
     g.P = P;
     pr_rec1 = GB(int32_t, "pr_rec1", P);
     pr_rec2 = GB(int32_t, "pr_rec2", P);
     pr_region = GB(int32_t, "pr_region", P);
     int4* pr_tag = GB(int4, "pr_tag", P);
-    const PairView PV{pr_rec1, pr_rec2, pr_region, d_run, g.scoped, pr_tag};
-    const int64_t R = 2 * P;
+    PV = PairView{pr_rec1, pr_rec2, pr_region, d_run, g.scoped, pr_tag};
+    R = 2 * P;
     g.R = R;
-    uint64_t* chash = GB(uint64_t, "chash", P);
-    uint64_t* thash = nullptr, *rhash = nullptr;   // tag hashes by read end (sort path) or by record
-    // (sorted tables whose read ends lie mostly in small position groups) per record its tag fields
+    chash = GB(uint64_t, "chash", P);
+    // rtag (sorted tables whose read ends lie mostly in small position groups) per record its tag fields
     // but the coordinates, for k_group_rank's compare in LDS.  Where most ends sit in deep groups (deep
     // panels: C4) the mates lie in other groups, the scattered copy costs more than the ranking's few
     // gathers by pair (C4 k_pair_keys +0.33 ms), and the ranking's compare takes those gathers.  The
     // deep ends' count: the plan of a repeated pass, else whether the table has deep groups at all.
-    int4* rtag = nullptr;
     if (g.coord_sorted) {
         rhash = GB(uint64_t, "rec_thash", N);
-        const auto nb = g.plan.find("n_big");
+        const auto nb = g.plan.find("n_big");   // (of the last pass, exact or planned)
         const bool by_rec = nb != g.plan.end() ? nb->second * 8 <= R : NDG == 0;
-        if (by_rec && !getenv("CC_GR_BY_PAIR")) rtag = GB(int4, "rec_tag", N);
+        if (by_rec && !sw.gr_by_pair) rtag = GB(int4, "rec_tag", N);
+    } else {
+        thash = GB(uint64_t, "thash", R);
+        tval = GB(uint32_t, "tval", R);   // the tag sort's values
     }
-    else { thash = GB(uint64_t, "thash", R); }
-    uint32_t* tval = g.coord_sorted ? nullptr : GB(uint32_t, "tval", R);   // the tag sort's values
-    uint64_t* rs_key = GB(uint64_t, "rs_key", R);
-    uint32_t* rs_val = GB(uint32_t, "rs_val", R);
-    uint8_t* cflag = GB(uint8_t, "cflag", (R + 15) & ~15LL);
-    uint32_t* bigE = nullptr;
-    if (g.coord_sorted && R > 0) {
-        bigE = GB(uint32_t, "grp_bigE", R);   // (every entry written by k_pair_keys)
-    }
+    rs_key = GB(uint64_t, "rs_key", R);
+    rs_val = GB(uint32_t, "rs_val", R);
+    cflag = GB(uint8_t, "cflag", (R + 15) & ~15LL);
+    if (g.coord_sorted && R > 0) bigE = GB(uint32_t, "grp_bigE", R);   // (every entry written by k_pair_keys)
     if (R > 0 && !pre_ends) RC(fill.add(cflag, ((size_t)R + 15) & ~(size_t)15, 0u));
     RC(fill.launch());
     if (P > 0) {
@@ -6865,184 +6930,163 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
         hipLaunchKernelGGL(k_pair_keys, dim3(nblk(P)), dim3(256), 0, ctx->stream, P, PV, T, g.seed, chash, thash,
                            tval, pr_tag, rhash, (uint2*)bigE, rtag);
     }
-    // ---- 4. read_dict / tag_dict: group read ends by exact tag
+    return 0;
+}
+
+// ---- 4. read_dict / tag_dict: group read ends by exact tag
+int ReadBamPass::grouping() {
     g.local_groups = false;
-    int32_t* mem_rec = GB(int32_t, "mem_rec", R);
-    int64_t n_known = 0;   // mem_rec[0, n_known) written by k_group_rank
-    int64_t n_deep = 0;    // read ends in deep position groups
-    bool deep_same_group = false;   // their sort keys are group-major (equal keys: one position group)
-    bool deep_ranked = false;       // k_deep_fam ranked them (no sort, no k_fam_mark)
-    if (g.coord_sorted && R > 0) {
-        int32_t* rec_e = (int32_t*)g.buf["rec_e"].p;      // initialised by k_build_meta
-        const uint64_t* rkey = (const uint64_t*)T.rkey;   // the table's position keys (k_derive)
-        const int64_t NT = (N + GT - 1) / GT;
-        uint32_t* tsmall = GB(uint32_t, "grp_tile_small", NT);
-        {
-            ProfScope ps(ctx, "k_group");
-            uint32_t* st = plan_stripes(ctx, g, d_nbig, &brc);
-            if (brc) return brc;
-            if (getenv("CC_GROUP_STAGED"))   // (the staged classification: a measurement / test switch)
-                hipLaunchKernelGGL(k_group_flags, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, N, rkey, rec_e, tsmall, st);
-            else
-                hipLaunchKernelGGL(k_group_count, dim3(nblk(N, GT * GC_TILES)), dim3(GT), 0, ctx->stream, N, (const int32_t*)rec_e,
-                                   (const uint8_t*)T.rdeep, tsmall, st);
-            if (g.fast && g.plan.count("n_big")) g.stripes_pending = true;
-            else hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, st, d_nbig);
-        }
-        int64_t NS = 0, NB = 0;
-        uint32_t* tpre = GB(uint32_t, "grp_tile_pre", NT);
-        RC(scan_total(ctx, g, tsmall, tpre, NT, &NS, "scan_small"));
-        if (NS > 0) {
-            ProfScope ps(ctx, "k_group_rank");
-            uint8_t* segf0 = GB(uint8_t, "segf", (R + 15) & ~15LL);
-            uint32_t* valid0 = GB(uint32_t, "mem_valid", R);
-            uint4* meta0 = nullptr;
-            if (members) { meta0 = GB(uint4, "mem_meta", R); }
-            if (rtag)
-                hipLaunchKernelGGL(k_group_rank<true>, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, N, rkey, rec_e,
-                                   (const uint64_t*)rhash, (const uint32_t*)tpre, rs_key, rs_val, mem_rec, PV,
-                                   (const int4*)rtag, T, segf0, valid0, meta0, ctx->d_err);
-            else
-                hipLaunchKernelGGL(k_group_rank<false>, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, N, rkey, rec_e,
-                                   (const uint64_t*)rhash, (const uint32_t*)tpre, rs_key, rs_val, mem_rec, PV,
-                                   (const int4*)nullptr, T, segf0, valid0, meta0, ctx->d_err);
-        }
-        n_known = NS;
-        RC(planned_total(ctx, g, "n_big", d_nbig, &NB));
-        n_deep = NB;
-        if (NS + NB != R) {
-            // inconsistent coordinate pairs (a record paired twice) lose read ends here; the qname
-            // check that sends such a pass to the sort path has flagged it by now
-            uint32_t eb = 0;
-            RC(read_err(ctx, &eb));
-            if (eb & EB_NEEDSORT) return CC_E_NEEDSORT;
-            ctx->err = "position-group partition lost read ends";
-            return CC_E_INVALID;
-        }
-        g.local_groups = NB == 0;
-        if (NB > 0 && deep_q && NDG > 0 && !g.no_deep_fam && !getenv("CC_DEEP_SORT")) {
-            // the deep groups ranked in place (k_deep_fam, k_deep_emit, k_deep_sortfam): no global sort
-            const int32_t* gend = (const int32_t*)g.buf["deep_gend"].p;
-            uint32_t* gcnt = GB(uint32_t, "deep_gcnt", NDG);
-            uint32_t* goff = GB(uint32_t, "deep_goff", NDG);
-            uint32_t* se = GB(uint32_t, "deep_se", N);
-            int4* items = GB(int4, "deep_items", NB);
-            int4* bigit = GB(int4, "deep_big", NB / 65 + 1);
-            uint32_t* d_ovf = plan_slot(ctx, g, "deep_ovf", &brc);
-            if (brc) return brc;
-            uint32_t* d_items = plan_slot(ctx, g, "deep_items", &brc);
-            if (brc) return brc;
-            uint32_t* d_big = plan_slot(ctx, g, "deep_big", &brc);
-            if (brc) return brc;
-            uint8_t* segf1 = GB(uint8_t, "segf", (R + 15) & ~15LL);
-            uint32_t* valid1 = GB(uint32_t, "mem_valid", R);
-            uint4* meta1 = nullptr;
-            if (members) { meta1 = GB(uint4, "mem_meta", R); }
-            const DeepOut dout{R, rs_val, mem_rec, segf1, valid1, meta1};
-            {
-                ProfScope ps(ctx, "k_deep_count");
-                hipLaunchKernelGGL(k_deep_count, dim3((unsigned)std::min<int64_t>(NDG, 4096)), dim3(256), 0, ctx->stream,
-                                   (const uint32_t*)d_ndg, (const int32_t*)dlist, gend, (const int32_t*)rec_e, gcnt);
-            }
-            int64_t nd = 0;
-            RC(scan_total(ctx, g, gcnt, goff, NDG, &nd, "scan_deep"));
-            if (nd != NB) {
-                ctx->err = "deep position groups: end count differs from the group partition";
-                return CC_E_INVALID;
-            }
-            {
-                ProfScope ps(ctx, "k_deep_fam");
-                hipLaunchKernelGGL(k_deep_fam, dim3((unsigned)std::min<int64_t>(NDG, CC_DF_GRID)), dim3(DF_T), 0, ctx->stream,
-                                   (const uint32_t*)d_ndg, (const int32_t*)dlist, gend, (const int32_t*)rec_e,
-                                   (const uint64_t*)rhash, (const uint32_t*)goff, NS, PV, T, se, items, d_items, bigit,
-                                   d_big, d_ovf, ctx->d_err);
-            }
-#ifdef DF_PROF
-            {
-                unsigned long long hp[8];
-                HIPCHK(hipStreamSynchronize(ctx->stream));
-                HIPCHK(hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_df_prof), sizeof(hp)));
-                fprintf(stderr, "[deep_fam] NDG %lld  block-us: table %.0f numbering %.0f place %.0f\n", (long long)NDG,
-                        hp[0] / 100.0, hp[1] / 100.0, hp[2] / 100.0);
-                memset(hp, 0, sizeof(hp));
-                HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_df_prof), hp, sizeof(hp)));
-            }
-#endif
-            int64_t novf = 0;
-            RC(planned_total(ctx, g, "deep_ovf", d_ovf, &novf));
-            if (novf == 0) {
-                {
-                    ProfScope ps(ctx, "k_deep_emit");
-                    hipLaunchKernelGGL(k_deep_emit, dim3((unsigned)std::min<int64_t>(NB / 256 + 1, 8192)), dim3(256), 0,
-                                       ctx->stream, (const int4*)items, (const uint32_t*)d_items, (const uint32_t*)se, PV,
-                                       T, dout, ctx->d_err);
-                }
-                int64_t nbig = 0;
-                RC(planned_total(ctx, g, "deep_big", d_big, &nbig));
-                if (nbig > 0) {
-                    ProfScope ps(ctx, "k_deep_sortfam");
-                    hipLaunchKernelGGL(k_deep_sortfam, dim3((unsigned)std::min<int64_t>(nbig, CC_DS_GRID)), dim3(DF_ST), 0,
-                                       ctx->stream, (const int4*)bigit, (const uint32_t*)d_big, (const uint32_t*)se, PV, T,
-                                       dout, ctx->d_err);
-                }
-                deep_ranked = true;
-            }
-        }
-        if (NB > 0 && !deep_ranked) {
-            uint32_t* bx = GB(uint32_t, "grp_bx", R);
-            RC(scan_total(ctx, g, bigE, bx, R, &NB, "scan_bigE"));
-            uint64_t* bkey = GB(uint64_t, "grp_bkey", NB);
-            uint32_t* bval = GB(uint32_t, "grp_bval", NB);
-            // group-major keys when this pass's coordinate search numbered the deep groups
-            // (k_deep_qsort), else the full tag hash.  (The same keys with the hash bits in 16..63 and
-            // a sort over bits 16..63 split c4 families on the GPU: rocPRIM's begin_bit is not used.)
-            int gbits = 1;
-            while ((1LL << gbits) < NDG) ++gbits;
-            const char* kbe = getenv("CC_DEEP_KEYBITS");
-            const int kb = kbe ? atoi(kbe) : 48;
-            const bool by_group = deep_gid != nullptr && kb > 0 && gbits <= 24;
-            deep_same_group = by_group;
-            hipLaunchKernelGGL(k_big_keys, dim3(nblk(R)), dim3(256), 0, ctx->stream, R, bigE, bx,
-                               (const uint64_t*)rhash, PV, (const uint32_t*)(by_group ? deep_gid : nullptr), gbits,
-                               by_group ? kb : 64, bkey, bval);
-            RC(sort_pairs(ctx, bkey, rs_key + NS, bval, rs_val + NS, NB, "sort_tags_big", 0u, by_group ? (unsigned)kb : 64u));
-        }
-    } else {
-        RC(sort_pairs(ctx, thash, rs_key, tval, rs_val, R, "sort_tags"));
+    mem_rec = GB(int32_t, "mem_rec", R);
+    segf = GB(uint8_t, "segf", (R + 15) & ~15LL);
+    mem_valid = GB(uint32_t, "mem_valid", R);
+    if (members) mem_meta = GB(uint4, "mem_meta", R);
+    if (!g.coord_sorted) return sort_pairs(ctx, thash, rs_key, tval, rs_val, R, "sort_tags");
+    if (R <= 0) return 0;
+    const uint64_t* rkey = (const uint64_t*)T.rkey;   // the table's position keys (k_derive)
+    const int64_t NT = (N + GT - 1) / GT;
+    uint32_t* tsmall = GB(uint32_t, "grp_tile_small", NT);
+    {
+        ProfScope ps(ctx, "k_group");
+        uint32_t* st = plan_stripes(ctx, g, d_nbig, &brc);
+        if (brc) return brc;
+        if (sw.group_staged)   // (the staged classification: a measurement / test switch)
+            hipLaunchKernelGGL(k_group_flags, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, N, rkey, rec_e, tsmall, st);
+        else
+            hipLaunchKernelGGL(k_group_count, dim3(nblk(N, GT * GC_TILES)), dim3(GT), 0, ctx->stream, N, (const int32_t*)rec_e,
+                               (const uint8_t*)T.rdeep, tsmall, st);
+        if (has_plan(g, "n_big")) g.stripes_pending = true;
+        else hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, st, d_nbig);
     }
-    uint8_t* segf = GB(uint8_t, "segf", (R + 15) & ~15LL);
-    uint32_t* validf = GB(uint32_t, "mem_valid", R);
-    uint4* mem_meta = nullptr;
-    if (members) { mem_meta = GB(uint4, "mem_meta", R); }
+    int64_t NS = 0, NB = 0;
+    uint32_t* tpre = GB(uint32_t, "grp_tile_pre", NT);
+    RC(scan_total(ctx, g, tsmall, tpre, NT, &NS, "scan_small"));
+    if (NS > 0) {
+        ProfScope ps(ctx, "k_group_rank");
+        const auto k_rank = rtag ? k_group_rank<true> : k_group_rank<false>;   // (the compare's fields by record, or by pair)
+        hipLaunchKernelGGL(k_rank, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, N, rkey, rec_e,
+                           (const uint64_t*)rhash, (const uint32_t*)tpre, rs_key, rs_val, mem_rec, PV,
+                           (const int4*)rtag, T, segf, mem_valid, mem_meta, ctx->d_err);
+    }
+    n_known = NS;
+    RC(planned_total(ctx, g, "n_big", d_nbig, &NB));
+    n_deep = NB;
+    if (NS + NB != R) {
+        // inconsistent coordinate pairs (a record paired twice) lose read ends here; the qname
+        // check that sends such a pass to the sort path has flagged it by now
+        uint32_t eb = 0;
+        RC(read_err(ctx, &eb));
+        if (eb & EB_NEEDSORT) return CC_E_NEEDSORT;
+        ctx->err = "position-group partition lost read ends";
+        return CC_E_INVALID;
+    }
+    g.local_groups = NB == 0;
+    if (NB > 0 && deep_q && NDG > 0 && !g.no_deep_fam && !sw.deep_sort) RC(rank_deep_in_place(NS, NB));
+    if (NB > 0 && !deep_ranked) {
+        uint32_t* bx = GB(uint32_t, "grp_bx", R);
+        RC(scan_total(ctx, g, bigE, bx, R, &NB, "scan_bigE"));
+        uint64_t* bkey = GB(uint64_t, "grp_bkey", NB);
+        uint32_t* bval = GB(uint32_t, "grp_bval", NB);
+        // group-major keys when this pass's coordinate search numbered the deep groups
+        // (k_deep_qsort), else the full tag hash.  (The same keys with the hash bits in 16..63 and
+        // a sort over bits 16..63 split c4 families on the GPU: rocPRIM's begin_bit is not used.)
+        constexpr int KEY_BITS = 48;   // the group-major keys' width (k_big_keys): six radix passes, not eight
+        int gbits = 1;
+        while ((1LL << gbits) < NDG) ++gbits;
+        const bool by_group = deep_gid != nullptr && gbits <= 24;
+        deep_same_group = by_group;
+        hipLaunchKernelGGL(k_big_keys, dim3(nblk(R)), dim3(256), 0, ctx->stream, R, bigE, bx,
+                           (const uint64_t*)rhash, PV, (const uint32_t*)(by_group ? deep_gid : nullptr), gbits,
+                           by_group ? KEY_BITS : 64, bkey, bval);
+        RC(sort_pairs(ctx, bkey, rs_key + NS, bval, rs_val + NS, NB, "sort_tags_big", 0u, by_group ? (unsigned)KEY_BITS : 64u));
+    }
+    return 0;
+}
+
+// The NB ends of the deep groups ranked in place behind the NS small-group ends (k_deep_fam,
+// k_deep_emit, k_deep_sortfam): no global sort.  deep_ranked stays false when a group overflowed
+// k_deep_fam's table (the sorted path ranks them then).
+int ReadBamPass::rank_deep_in_place(int64_t NS, int64_t NB) {
+    uint32_t* gcnt = GB(uint32_t, "deep_gcnt", NDG);
+    uint32_t* goff = GB(uint32_t, "deep_goff", NDG);
+    uint32_t* se = GB(uint32_t, "deep_se", N);
+    int4* items = GB(int4, "deep_items", NB);
+    int4* bigit = GB(int4, "deep_big", NB / 65 + 1);
+    uint32_t* d_ovf = plan_slot(ctx, g, "deep_ovf", &brc);
+    uint32_t* d_items = plan_slot(ctx, g, "deep_items", &brc);
+    uint32_t* d_big = plan_slot(ctx, g, "deep_big", &brc);
+    if (brc) return brc;
+    const DeepOut dout{R, rs_val, mem_rec, segf, mem_valid, mem_meta};
+    {
+        ProfScope ps(ctx, "k_deep_count");
+        hipLaunchKernelGGL(k_deep_count, dim3((unsigned)std::min<int64_t>(NDG, 4096)), dim3(256), 0, ctx->stream,
+                           (const uint32_t*)T.ndeep, (const int32_t*)T.dlist, (const int32_t*)gend, (const int32_t*)rec_e,
+                           gcnt);
+    }
+    int64_t nd = 0;
+    RC(scan_total(ctx, g, gcnt, goff, NDG, &nd, "scan_deep"));
+    if (nd != NB) {
+        ctx->err = "deep position groups: end count differs from the group partition";
+        return CC_E_INVALID;
+    }
+    {
+        ProfScope ps(ctx, "k_deep_fam");
+        hipLaunchKernelGGL(k_deep_fam, dim3((unsigned)std::min<int64_t>(NDG, CC_DF_GRID)), dim3(DF_T), 0, ctx->stream,
+                           (const uint32_t*)T.ndeep, (const int32_t*)T.dlist, (const int32_t*)gend, (const int32_t*)rec_e,
+                           (const uint64_t*)rhash, (const uint32_t*)goff, NS, PV, T, se, items, d_items, bigit,
+                           d_big, d_ovf, ctx->d_err);
+    }
+    int64_t novf = 0;
+    RC(planned_total(ctx, g, "deep_ovf", d_ovf, &novf));
+    if (novf != 0) return 0;
+    {
+        ProfScope ps(ctx, "k_deep_emit");
+        hipLaunchKernelGGL(k_deep_emit, dim3((unsigned)std::min<int64_t>(NB / 256 + 1, 8192)), dim3(256), 0,
+                           ctx->stream, (const int4*)items, (const uint32_t*)d_items, (const uint32_t*)se, PV,
+                           T, dout, ctx->d_err);
+    }
+    int64_t nbig = 0;
+    RC(planned_total(ctx, g, "deep_big", d_big, &nbig));
+    if (nbig > 0) {
+        ProfScope ps(ctx, "k_deep_sortfam");
+        hipLaunchKernelGGL(k_deep_sortfam, dim3((unsigned)std::min<int64_t>(nbig, CC_DS_GRID)), dim3(DF_ST), 0,
+                           ctx->stream, (const int4*)bigit, (const uint32_t*)d_big, (const uint32_t*)se, PV, T,
+                           dout, ctx->d_err);
+    }
+    deep_ranked = true;
+    return 0;
+}
+
+// k_fam_mark and k_fam_dedup, the family starts and records (k_fam_build), then
+// ---- 5. tag_dict insertion order (family creation order)
+int ReadBamPass::families() {
     if (R > 0) {
         ProfScope ps(ctx, "k_fam_mark");
         // the small groups' slots [0, n_known) were marked by k_group_rank
         if (R > n_known && !deep_ranked)
             hipLaunchKernelGGL(k_fam_mark, dim3(nblk(R - n_known)), dim3(256), 0, ctx->stream, R, n_known, n_known, rs_key,
-                               rs_val, PV, T, segf, validf, mem_rec, mem_meta, ctx->d_err, deep_same_group ? 1 : 0);
+                               rs_val, PV, T, segf, mem_valid, mem_rec, mem_meta, ctx->d_err, deep_same_group ? 1 : 0);
         // qnames seen more than twice exist only where the exact pairing (k_pair_mark) ran this pass
         if (sorted_pairing)
-        hipLaunchKernelGGL(k_fam_dedup, dim3(std::min<unsigned>(nblk(R), 1024u)), dim3(256), 0, ctx->stream, R,
-                           (const uint32_t*)d_nmulti, (const uint8_t*)segf, validf, (const int32_t*)mem_rec,
-                           (const uint32_t*)rs_val, (const int32_t*)pr_rec1, (const uint64_t*)T.rdig, mem_meta);
+            hipLaunchKernelGGL(k_fam_dedup, dim3(std::min<unsigned>(nblk(R), 1024u)), dim3(256), 0, ctx->stream, R,
+                               (const uint32_t*)d_nmulti, (const uint8_t*)segf, mem_valid, (const int32_t*)mem_rec,
+                               (const uint32_t*)rs_val, (const int32_t*)pr_rec1, (const uint64_t*)T.rdig, mem_meta);
     }
     // family starts compacted in the scan's store phase (EmitFamStarts): fam_beg and fam_drop take
     // their capacity first (F is the scan's total)
-    int64_t F = 0, V = 0;
-    const int64_t Fcap = g.fast && g.plan.count("scan_fam") ? g.plan["scan_fam"] : R;
-    int32_t* fam_beg = GB(int32_t, "fam_beg", Fcap);
+    const int64_t Fcap = plan_or(g, "scan_fam", R);
+    fam_beg = GB(int32_t, "fam_beg", Fcap);
     int32_t* fam_drop = GB(int32_t, "fam_drop", Fcap);
     if (Fcap > 0 && !drop_zeroed) HIPCHK(hipMemsetAsync(fam_drop, 0, sizeof(int32_t) * Fcap, ctx->stream));
-    RC(scan_emit(ctx, g, segf, R, &F, "scan_fam", EmitFamStarts{validf, fam_beg, fam_drop, d_ndrop, Fcap, ctx->d_err}));
+    RC(scan_emit(ctx, g, segf, R, &F, "scan_fam", EmitFamStarts{mem_valid, fam_beg, fam_drop, d_ndrop, Fcap, ctx->d_err}));
     g.F = F;
     fam_beg = GB(int32_t, "fam_beg", F);
-    int32_t* fam_end = GB(int32_t, "fam_end", F);
+    fam_end = GB(int32_t, "fam_end", F);
     int32_t* fam_n = GB(int32_t, "fam_n", F);
-    int32_t* fam_first = GB(int32_t, "fam_first", F);
-    int32_t* fam_region = GB(int32_t, "fam_region", F);
+    fam_first = GB(int32_t, "fam_first", F);
+    fam_region = GB(int32_t, "fam_region", F);
     uint64_t* fam_hash = GB(uint64_t, "fam_hash", F);
     int32_t* cfam = GB(int32_t, "cfam", R);
-    int32_t* fam_o = GB(int32_t, "fam_o", F);
+    fam_o = GB(int32_t, "fam_o", F);
     // the passes whose stage joins the grouping (DCS, SC: no bad-read list) build the family tags
     // here; the SSCS pass never joins
     g.fam_tags_built = false;
@@ -7056,7 +7100,7 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
         ProfScope ps(ctx, "k_fam_build");
         hipLaunchKernelGGL(k_fam_build, dim3(nblk(F)), dim3(256), 0, ctx->stream, F, R, n_known,
                            (int)(g.n_regions == 1), fam_beg, fam_drop,
-                           rs_val, rs_key, pr_region, (const uint64_t*)(g.coord_sorted ? g.buf["rec_thash"].p : nullptr),
+                           rs_val, rs_key, pr_region, (const uint64_t*)rhash,
                            (const int32_t*)mem_rec, fam_end, fam_n, fam_first, fam_region, fam_hash, cflag,
                            cfam, fam_o, PV, T, fam_tag, fam_rec);
     }
@@ -7065,12 +7109,15 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
     V = R - V;   // members kept
     // ---- 5. tag_dict insertion order (family creation order)
     int64_t F2 = 0;
-    int32_t* fam_by_k = GB(int32_t, "fam_by_k", F);
+    fam_by_k = GB(int32_t, "fam_by_k", F);
     int32_t* fam_k = GB(int32_t, "fam_k", F);
-    int32_t* pair_by_k = GB(int32_t, "pair_by_k", F);
+    pair_by_k = GB(int32_t, "pair_by_k", F);
     int32_t* fsz = GB(int32_t, "fam_sizes_by_creation", F);
-    RC(scan_emit(ctx, g, cflag, R, &F2, "scan_creation", EmitCreation{cfam, fam_n, fam_by_k, fam_k, pair_by_k, fsz}));
-    // ---- 6. csn_pair_dict: group creation events by consensus tag
+    return scan_emit(ctx, g, cflag, R, &F2, "scan_creation", EmitCreation{cfam, fam_n, fam_by_k, fam_k, pair_by_k, fsz});
+}
+
+// ---- 6. csn_pair_dict: group creation events by consensus tag
+int ReadBamPass::csn() {
     uint32_t* csegf = GB(uint32_t, "csegf", F);
     uint8_t* emark = GB(uint8_t, "emark", (F + 15) & ~15LL);
     int32_t* e1k = GB(int32_t, "e1k", F);
@@ -7113,7 +7160,6 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
                            fam_region, g.badread ? 0 : 1, emark, e1k, ctx->d_cnt);
     }
     g.csn_fast = fast_ok;
-    int64_t E = 0;
     int32_t* ent_f = GB(int32_t, "ent_f", 2 * F);   // capacity; sized E below
     int32_t* ent_pair = GB(int32_t, "ent_pair", F);
     uint8_t* has2 = GB(uint8_t, "has2", (F + 15) & ~15LL);   // byte flags (16-B padded for the scan)
@@ -7130,20 +7176,33 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
         hipLaunchKernelGGL(k_overlap_keyerror, dim3(nblk(E)), dim3(256), 0, ctx->stream, E, (const int32_t*)ent_f,
                            (const int32_t*)fam_beg, (const int32_t*)fam_end, (const int32_t*)fam_region,
                            (const uint32_t*)rs_val, (const int32_t*)pr_region, ctx->d_err);
-    // ---- counters + error word
+    return 0;
+}
+
+// One pass: its phases, then the one readback (counters + error word) and its judgement.
+int read_bam_pass(cc_ctx* ctx, int32_t gid) {
+    ReadBamPass p(ctx, *ctx->groups[gid]);
+    RC(p.setup());        // plan slots, long-pair check sizing, the first fill set
+    RC(p.filters());      // 0-1. table preparation, filters + qname keys
+    RC(p.pairing());      // 2. pair_dict: mates by coordinates, residual reads, or the qname sort
+    RC(p.pair_keys());    // 3. completed pairs and their tag / consensus-tag hashes
+    RC(p.grouping());     // 4. read ends ranked by tag: position groups, deep groups, or the tag sort
+    RC(p.families());     //    family starts and records; 5. creation order
+    RC(p.csn());          // 6. csn_pair_dict entries
+    Group& g = p.g;
     uint32_t bits = 0;
     bool plan_ok = true;
     RC(finish_pass(ctx, g, &bits, true, &plan_ok));
     if (bits & EB_NEEDSORT) return CC_E_NEEDSORT;   // before the plan check: the re-run is exact
     if (bits & EB_DEEPSORT) return CC_E_DEEPSORT;
     if (!plan_ok) return CC_E_PLAN;
-    g.counters[CC_CNT_COUNTER] = S - g.counters[CC_CNT_FOREIGN] - g.counters[CC_CNT_UNMAPPED];
-    g.counters[CC_CNT_PAIRS] = P;
-    g.counters[CC_CNT_READ_ENDS] = R;
-    g.counters[CC_CNT_FAMILIES] = F;
-    g.counters[CC_CNT_ENTRIES] = E;
-    g.counters[CC_CNT_DROPPED] = R - V;
-    g.members_built = members;
+    g.counters[CC_CNT_COUNTER] = p.S - g.counters[CC_CNT_FOREIGN] - g.counters[CC_CNT_UNMAPPED];
+    g.counters[CC_CNT_PAIRS] = p.P;
+    g.counters[CC_CNT_READ_ENDS] = p.R;
+    g.counters[CC_CNT_FAMILIES] = p.F;
+    g.counters[CC_CNT_ENTRIES] = p.E;
+    g.counters[CC_CNT_DROPPED] = p.R - p.V;
+    g.members_built = p.members;
     return err_code(ctx, bits);
 }
 
@@ -7181,6 +7240,7 @@ int cc_read_bam(cc_ctx* ctx, int32_t table_id, int64_t S, const int32_t* stream_
                 int32_t n_regions, const int32_t* region_run, const cc_read_bam_params* prm, int32_t* group_id) {
     if (!ctx || !prm || !group_id || !ctx->tables.count(table_id) || S < 0 || S >= INT32_MAX / 2) return CC_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
     int32_t gid = ctx->next_id++;
     ctx->groups[gid].reset(new Group());
     Group& g = *ctx->groups[gid];
@@ -7223,6 +7283,7 @@ int cc_read_bam(cc_ctx* ctx, int32_t table_id, int64_t S, const int32_t* stream_
 // Re-run read_bam on a group whose stream is already resident (bench steps), with a new seed.
 int cc_read_bam_rerun(cc_ctx* ctx, int32_t group_id, uint64_t seed) {
     if (!ctx || !ctx->groups.count(group_id)) return CC_E_INVALID;
+    ctx->sw = read_switches();
     ctx->groups[group_id]->seed = seed;
     return read_bam_run(ctx, group_id);
 }
@@ -7254,6 +7315,7 @@ int cc_group_free(cc_ctx* ctx, int32_t group_id) {
 int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_out) {
     if (!ctx || !ctx->groups.count(group_id)) return CC_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
     Group& g = *ctx->groups[group_id];
     auto pass = [&]() -> int {
         RC(flush_derive(ctx, g.table));
@@ -7327,6 +7389,7 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
 int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, int32_t n_bc, int64_t* n_out) {
     if (!ctx || !ctx->groups.count(group_id) || (!bc_swap && n_bc > 0)) return CC_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
     Group& g = *ctx->groups[group_id];
     auto pass = [&]() -> int {
         RC(flush_derive(ctx, g.table));
@@ -7347,7 +7410,7 @@ int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, i
         if (Q > 0) {
             ProfScope ps(ctx, "k_dcs_decide");
             // a local grouping: per family, its position group staged in LDS; otherwise per entry
-            if (G.local && !getenv("CC_DCS_PER_ENTRY"))
+            if (G.local && !ctx->sw.dcs_per_entry)
                 hipLaunchKernelGGL(k_dcs_decide_fam, dim3((unsigned)((std::max<int64_t>(g.F, Q) + DD_T - 1) / DD_T)),
                                    dim3(DD_T), 0, ctx->stream, Q, G, d_swap, n_bc, dec, t_rec, p_rec, fl_dcs, ctx->d_err);
             else
@@ -7392,6 +7455,7 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
     if (!ctx || !ctx->groups.count(sgroup) || !ctx->groups.count(ssgroup) || (!bc_swap && n_bc > 0))
         return CC_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
     Group& g = *ctx->groups[sgroup];
     Group& s = *ctx->groups[ssgroup];
     auto pass = [&]() -> int {
@@ -7545,6 +7609,7 @@ int cc_sscs_vote(cc_ctx* ctx, int32_t table_id, const int32_t* member_index, con
         return CC_E_INVALID;
     if (nfam > 0 && fam_offsets[nfam] > 0 && !member_index) return CC_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
     RC(flush_derive(ctx, table_id));
     const DevTable T = ctx->tables[table_id];
     if (out_stride < T.max_len || (out_stride & 1)) {
@@ -7914,6 +7979,7 @@ int cc_group(cc_ctx* ctx, int64_t n, const void* keys, int32_t key_bytes, int32_
         return CC_E_INVALID;
     if (!key_args_ok(ctx, key_bytes)) return CC_E_INVALID;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
     *out_nfam = 0;
     if (n == 0) {
         if (out_fam_offsets) out_fam_offsets[0] = 0;
