@@ -362,9 +362,12 @@ uint32_t bg_crc_table(uint32_t crc, const uint8_t* p, size_t n) {   // when neit
 
 }  // namespace
 
+struct BgzfDec;   // the inflater's buffers (bgzf_inflate.hip.inc): same streams, mutex and latch
+
 struct BgzfEnc {
-    std::mutex mu;          // one caller at a time (the writers' threads call concurrently)
-    bool ready = false, broken = false;
+    std::mutex mu;          // one caller at a time (the writers' and readers' threads call concurrently)
+    bool ready = false, broken = false, streams = false;
+    BgzfDec* dec = nullptr;
     std::string err;
     hipStream_t st[2] = {nullptr, nullptr};
     uint8_t* h_in[2] = {nullptr, nullptr};
@@ -400,10 +403,20 @@ namespace {
         }                                                                                    \
     } while (0)
 
+// the two streams the encoder and the inflater share (no others are opened)
+int bgzf_streams(BgzfEnc* E) {
+    if (E->streams) return 0;
+    for (int b = 0; b < 2; ++b) BGCHK(hipStreamCreateWithFlags(&E->st[b], hipStreamNonBlocking));
+    E->streams = true;
+    return 0;
+}
+
+void bgzf_dec_free(BgzfDec* D);
+
 int bgzf_init(BgzfEnc* E) {
     constexpr size_t in_bytes = (size_t)BG_CHUNK * BG_PIECE, out_bytes = (size_t)BG_CHUNK * BG_OSLOT;
+    RC(bgzf_streams(E));
     for (int b = 0; b < 2; ++b) {
-        BGCHK(hipStreamCreateWithFlags(&E->st[b], hipStreamNonBlocking));
         BGCHK(hipHostMalloc((void**)&E->h_in[b], in_bytes));
         BGCHK(hipHostMalloc((void**)&E->h_out[b], out_bytes));
         BGCHK(hipHostMalloc((void**)&E->h_len[b], BG_CHUNK * sizeof(uint32_t)));
@@ -426,8 +439,10 @@ int bgzf_init(BgzfEnc* E) {
 void bgzf_free(cc_ctx* ctx) {
     BgzfEnc* E = ctx->bgzf;
     if (!E) return;
-    for (int b = 0; b < 2; ++b) {
+    for (int b = 0; b < 2; ++b)
         if (E->st[b]) (void)hipStreamSynchronize(E->st[b]);
+    bgzf_dec_free(E->dec);
+    for (int b = 0; b < 2; ++b) {
         if (E->h_in[b]) (void)hipHostFree(E->h_in[b]);
         if (E->h_out[b]) (void)hipHostFree(E->h_out[b]);
         if (E->h_len[b]) (void)hipHostFree(E->h_len[b]);

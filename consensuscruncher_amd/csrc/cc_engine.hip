@@ -5975,6 +5975,7 @@ int build_fam_buckets(cc_ctx* ctx, Group& g, GroupView* v, bool* ok) {
 }  // namespace
 
 #include "bgzf_deflate.hip.inc"
+#include "bgzf_inflate.hip.inc"
 
 extern "C" {
 
@@ -6040,6 +6041,7 @@ int cc_set_profiling(cc_ctx* ctx, int on) {
     ctx->profiling = on != 0;
     if (on) ctx->prof.clear();
     if (on) bgzf_prof(ctx, true, nullptr, nullptr);
+    if (on) bgzf_dec_prof(ctx, true, nullptr, nullptr, nullptr, nullptr);
     return 0;
 }
 
@@ -6067,6 +6069,16 @@ int cc_kernel_times(cc_ctx* ctx, char* names, int names_cap, double* ms, int64_t
             ctx->prof["bgzf_deflate"] = {bms, bn};
             ctx->prof["bgzf_upload"] = {up, bn};       // the launches' host-to-device copies
             ctx->prof["bgzf_download"] = {down, bn};   // and the packed members' way back
+        }
+    }
+    {   // so does the inflater
+        double ims = 0, up = 0, down = 0;
+        int64_t in = 0;
+        bgzf_dec_prof(ctx, false, &ims, &in, &up, &down);
+        if (in) {
+            ctx->prof["bgzf_inflate"] = {ims, in};
+            ctx->prof["bgzf_in_upload"] = {up, in};
+            ctx->prof["bgzf_in_download"] = {down, in};
         }
     }
     int i = 0;

@@ -225,6 +225,52 @@ void parallel_chunks(int64_t n, int nthreads, int64_t grain, const std::function
     for (auto& x : th) x.join();
 }
 
+// An alternative inflater for the readers (ccio_set_inflate_hook): the device BGZF inflater of
+// libccamd, or any function with its contract.  libccio itself stays free of HIP.
+std::mutex g_ihook_mu;
+ccio_inflate_fn g_ihook_fn = nullptr;
+void* g_ihook_user = nullptr;
+
+// The non-empty members of blk (fields coff / clen / doff / dlen by the accessors) through the hook.
+// done[i] = 1 for every member the hook reports inflated AND whose bytes have the CRC32 the member
+// carries (the word behind its payload); every other member is left to the host codec.
+template <class Blk, class C, class L, class U, class N>
+void hook_inflate(const uint8_t* comp, uint8_t* out, const std::vector<Blk>& blk, C coff, L clen, U doff, N dlen,
+                  int nthreads, std::vector<uint8_t>& done) {
+    done.assign(blk.size(), 0);
+    ccio_inflate_fn fn;
+    void* user;
+    {
+        std::lock_guard<std::mutex> lk(g_ihook_mu);
+        fn = g_ihook_fn;
+        user = g_ihook_user;
+    }
+    if (!fn) return;
+    std::vector<size_t> which;
+    std::vector<uint64_t> co, uo;
+    std::vector<uint32_t> cl, ul;
+    for (size_t i = 0; i < blk.size(); ++i) {
+        if (!dlen(blk[i]) || dlen(blk[i]) > 0xffffffffull || clen(blk[i]) > 0xffffffffull) continue;
+        which.push_back(i);
+        co.push_back((uint64_t)coff(blk[i]));
+        cl.push_back((uint32_t)clen(blk[i]));
+        uo.push_back((uint64_t)doff(blk[i]));
+        ul.push_back((uint32_t)dlen(blk[i]));
+    }
+    if (which.empty()) return;
+    std::vector<uint8_t> ok(which.size(), 0);
+    if (fn(user, comp, co.data(), cl.data(), uo.data(), ul.data(), (int64_t)which.size(), out, ok.data()) != 0) return;
+    parallel_chunks((int64_t)which.size(), nthreads, 64, [&](int64_t b, int64_t e) {
+        Codec c;
+        for (int64_t j = b; j < e; ++j) {
+            if (!ok[(size_t)j]) continue;
+            const uint8_t* t = comp + co[(size_t)j] + cl[(size_t)j];
+            const uint32_t want = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+            if (c.crc32_of(out + uo[(size_t)j], ul[(size_t)j]) == want) done[which[(size_t)j]] = 1;
+        }
+    });
+}
+
 template <class CVec, class Vec>
 bool bgzf_inflate_all(const CVec& comp, Vec& out, int nthreads, std::string& err) {
     struct Blk { size_t coff, clen, doff, dlen; };
@@ -258,12 +304,16 @@ bool bgzf_inflate_all(const CVec& comp, Vec& out, int nthreads, std::string& err
         off += bsize;
     }
     out.resize(total);   // Vec's allocator leaves bytes uninitialised: every one is inflated below
+    std::vector<uint8_t> done;
+    hook_inflate((const uint8_t*)comp.data(), (uint8_t*)out.data(), blocks, [](const Blk& k) { return k.coff; },
+                 [](const Blk& k) { return k.clen; }, [](const Blk& k) { return k.doff; },
+                 [](const Blk& k) { return k.dlen; }, nthreads, done);
     std::atomic<bool> bad(false);
     parallel_chunks((int64_t)blocks.size(), nthreads, 16, [&](int64_t b, int64_t e) {
         Codec c;
         for (int64_t i = b; i < e && !bad; ++i) {
             const Blk& k = blocks[i];
-            if (k.dlen == 0) continue;
+            if (k.dlen == 0 || done[(size_t)i]) continue;
             if (!c.inflate_raw(comp.data() + k.coff, k.clen, out.data() + k.doff, k.dlen)) bad = true;
         }
     });
@@ -650,6 +700,13 @@ void ccio_set_deflate_hook(ccio_deflate_fn fn, void* user) {
     std::lock_guard<std::mutex> lk(g_hook_mu);
     g_hook_fn = fn;
     g_hook_user = fn ? user : nullptr;
+}
+
+// fn inflates the readers' BGZF members first from now on (NULL: the host codec alone again)
+void ccio_set_inflate_hook(ccio_inflate_fn fn, void* user) {
+    std::lock_guard<std::mutex> lk(g_ihook_mu);
+    g_ihook_fn = fn;
+    g_ihook_user = fn ? user : nullptr;
 }
 
 // waits for every CCIO_W_ASYNC write; -1 (ccio_last_error: the first failure) when one failed
@@ -2192,11 +2249,14 @@ bool inflate_members(const std::vector<uint8_t>& comp, uint64_t base, Vec& out,
     coff.push_back(base + o);
     uoff.push_back(u);
     out.resize(u);
+    std::vector<uint8_t> done;
+    hook_inflate(comp.data(), (uint8_t*)out.data(), bl, [](const Blk& k) { return k.c; }, [](const Blk& k) { return k.clen; },
+                 [](const Blk& k) { return k.u; }, [](const Blk& k) { return k.ulen; }, nthreads, done);
     std::atomic<bool> bad(false);
     parallel_chunks((int64_t)bl.size(), nthreads, 16, [&](int64_t b, int64_t e) {
         Codec c;
         for (int64_t i = b; i < e && !bad; ++i) {
-            if (!bl[i].ulen) continue;
+            if (!bl[i].ulen || done[(size_t)i]) continue;
             if (!c.inflate_raw(comp.data() + bl[i].c, bl[i].clen, out.data() + bl[i].u, bl[i].ulen)) bad = true;
         }
     });

@@ -280,6 +280,7 @@ def coord_sorted(records):
 
 
 _BGZF_OWNER = None   # the engine whose encoder libccio's (process-wide) deflate hook points at
+_INFLATE_OWNER = None   # likewise for the inflate hook
 
 
 class Engine(object):
@@ -294,8 +295,11 @@ class Engine(object):
         self.h = h
         self.tables = {}
         self.bgzf_device = False
+        self.inflate_device = False
         if os.environ.get("CC_BGZF_DEVICE") == "1":   # opt-in, in the style of CC_EXTRACT_GPU
             self.device_bgzf(True)
+        if os.environ.get("CC_INFLATE_DEVICE") == "1":
+            self.device_inflate(True)
 
     def device_bgzf(self, on):
         """Wires (or unwires) this context's device BGZF encoder into libccio's writers
@@ -333,6 +337,75 @@ class Engine(object):
             raise IOError(N.io_error())
         return was
 
+    def device_inflate(self, on):
+        """Wires (or unwires) this context's device BGZF inflater into libccio's readers
+        (cc_bgzf_inflate_hook -> ccio_set_inflate_hook): every BAM opened from now on (whole file,
+        regions, header) has its members inflated by k_bgzf_inflate first; libccio checks each
+        member's CRC32 and inflates whatever the device refused, or got wrong, with the host codec,
+        so the bytes read are the same either way.  The hook is one per process, with device_bgzf's
+        ownership rules: the last engine to wire it serves the readers, the engine it took the hook
+        from reads inflate_device False from then on, and that engine's close or unwiring leaves the
+        new owner's hook alone.  Reads are synchronous, so there is nothing to wait for.  Returns the
+        previous state."""
+        global _INFLATE_OWNER
+        was = self.inflate_device
+        on = bool(on)
+        if on == was:
+            return was
+        io = N.io()
+        if on:
+            fn, user = N.P(), N.P()
+            self._check(self.lib.cc_bgzf_inflate_hook(self.h, C.byref(fn), C.byref(user)))
+            prev = _INFLATE_OWNER
+            if prev is not None and prev is not self:
+                prev.inflate_device = False
+            io.ccio_set_inflate_hook(fn, user)
+            _INFLATE_OWNER = self
+            self.inflate_device = True
+            return was
+        io.ccio_set_inflate_hook(None, None)
+        _INFLATE_OWNER = None
+        self.inflate_device = False
+        return was
+
+    def bgzf_inflate(self, raw):
+        """cc_bgzf_inflate over the bytes of a BGZF file or run of members: (data, ok_list), data the
+        members' inflated bytes side by side (ISIZE bytes each; a refused member's are unspecified),
+        ok_list one bool per member."""
+        raw = bytes(raw)
+        coff, clen, uoff, ulen = [], [], [], []
+        off = total = 0
+        while off < len(raw):
+            if off + 18 > len(raw) or raw[off:off + 4] != b"\x1f\x8b\x08\x04":
+                raise ValueError("not a BGZF member at byte %d" % off)
+            xlen = int.from_bytes(raw[off + 10:off + 12], "little")
+            x, bsize = off + 12, 0
+            while x + 4 <= off + 12 + xlen and x + 4 <= len(raw):
+                slen = int.from_bytes(raw[x + 2:x + 4], "little")
+                if raw[x:x + 2] == b"BC" and slen == 2 and x + 6 <= len(raw):
+                    bsize = int.from_bytes(raw[x + 4:x + 6], "little") + 1
+                x += 4 + slen
+            if bsize < 12 + xlen + 8 or off + bsize > len(raw):
+                raise ValueError("BGZF member without BC field or truncated at byte %d" % off)
+            isize = int.from_bytes(raw[off + bsize - 4:off + bsize], "little")
+            coff.append(off + 12 + xlen)
+            clen.append(bsize - 12 - xlen - 8)
+            uoff.append(total)
+            ulen.append(isize)
+            total += isize
+            off += bsize
+        n = len(coff)
+        comp = np.frombuffer(raw, np.uint8)
+        out = np.zeros(max(total, 1), np.uint8)
+        ok = np.zeros(max(n, 1), np.uint8)
+        a = [np.asarray(v if n else [0], t) for v, t in ((coff, np.uint64), (clen, np.uint32), (uoff, np.uint64),
+                                                         (ulen, np.uint32))]
+        got = int(self.lib.cc_bgzf_inflate(self.h, N.ptr(comp) if comp.size else None, N.ptr(a[0]), N.ptr(a[1]),
+                                           N.ptr(a[2]), N.ptr(a[3]), n, N.ptr(out), N.ptr(ok)))
+        if got < 0:
+            raise N.CCError(got, self.lib.cc_last_error(self.h).decode(errors="replace"))
+        return out[:total].tobytes(), [bool(v) for v in ok[:n]]
+
     def bgzf_deflate(self, data):
         """cc_bgzf_deflate: the framed BGZF members of data (bytes-like), one per 0xff00-byte piece,
         as a list of bytes objects."""
@@ -350,7 +423,8 @@ class Engine(object):
     def close(self):
         if self.h:
             try:
-                self.device_bgzf(False)   # the hook must not outlive the context
+                self.device_inflate(False)   # the hooks must not outlive the context
+                self.device_bgzf(False)
             finally:
                 self.lib.cc_destroy(self.h)
                 self.h = None

@@ -76,6 +76,9 @@ class cc_read_bam_params(C.Structure):
 
 # ccio_deflate_fn (include/consensuscruncher_amd.h): user, data, n, stage, slot, out_len, pieces
 DEFLATE_FN = C.CFUNCTYPE(C.c_int, P, P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint32), C.c_int64)
+# ccio_inflate_fn: user, comp, coff, clen, uoff, ulen, members, out, ok
+INFLATE_FN = C.CFUNCTYPE(C.c_int, P, P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                         C.POINTER(C.c_uint32), C.c_int64, P, C.POINTER(C.c_uint8))
 
 _io = None
 _amd = None
@@ -84,6 +87,7 @@ IO_SIGS = {
     "ccio_last_error": (C.c_char_p, []),
     "ccio_flush": (C.c_int, []),
     "ccio_set_deflate_hook": (None, [P, P]),
+    "ccio_set_inflate_hook": (None, [P, P]),
     "ccio_value_census": (C.c_int, [P, C.c_int64, C.c_int32, P, P]),
     "ccio_interner_new": (P, []),
     "ccio_interner_free": (None, [P]),
@@ -148,6 +152,8 @@ AMD_SIGS = {
     "cc_synchronize": (C.c_int, [P]),
     "cc_bgzf_deflate": (C.c_int64, [P, P, C.c_uint64, P, C.c_uint64, P, C.c_int64]),
     "cc_bgzf_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
+    "cc_bgzf_inflate": (C.c_int64, [P, P, P, P, P, P, C.c_int64, P, P]),
+    "cc_bgzf_inflate_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
     "cc_defer": (C.c_int, [P, C.c_int]),
     "cc_commit": (C.c_int, [P]),
     "cc_debug_skew_plan": (C.c_int, [P, C.c_int32, C.c_char_p, C.c_int64]),

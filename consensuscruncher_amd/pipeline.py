@@ -52,21 +52,31 @@ def cleanup(sd, identifier, scorrect):
 
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
-                       bgzf="host"):
+                       bgzf="host", inflate="host"):
     """bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
-    output files: same records, other compressed bytes and .bai offsets); see _consensus_pipeline."""
+    output files: same records, other compressed bytes and .bai offsets).  inflate: "host" (the
+    default) or "device" (the engine's BGZF inflater reads the input and stage files: same bytes read,
+    so the same outputs).  Either option is wired for this call only; see _consensus_pipeline."""
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
-    if bgzf == "host":
+    if inflate not in ("host", "device"):
+        raise ValueError('inflate must be "host" or "device"')
+    if bgzf == "host" and inflate == "host":
         return _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
                                    cleanup_files, all_unique_sscs)
     engine = engine or get_engine()
-    was = engine.device_bgzf(True)
+    was = engine.device_bgzf(True) if bgzf == "device" else None
     try:
-        return _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
-                                   cleanup_files, all_unique_sscs)
+        was_in = engine.device_inflate(True) if inflate == "device" else None
+        try:
+            return _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level,
+                                       genome, cleanup_files, all_unique_sscs)
+        finally:
+            if was_in is not None:
+                engine.device_inflate(was_in)
     finally:
-        engine.device_bgzf(was)
+        if was is not None:
+            engine.device_bgzf(was)
 
 
 def _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,

@@ -618,20 +618,29 @@ def to_owners(comm, geo, parts):
 
 def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|", scorrect="True", level=6,
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
-                     cuts=None, bgzf="host"):
+                     cuts=None, bgzf="host", inflate="host"):
     """bgzf: "host" (the default) or "device": this rank's output files deflated by the engine's BGZF
-    encoder (pipeline.consensus_pipeline's option); see _sharded_pipeline."""
+    encoder.  inflate: "host" (the default) or "device": this rank's reads inflated by the engine's
+    BGZF inflater (pipeline.consensus_pipeline's options); see _sharded_pipeline."""
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
-    if bgzf == "host":
+    if inflate not in ("host", "device"):
+        raise ValueError('inflate must be "host" or "device"')
+    if bgzf == "host" and inflate == "host":
         return _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
                                  blocks, held, refs, keep, finalize, timings, cuts)
-    was = engine.device_bgzf(True)
+    was = engine.device_bgzf(True) if bgzf == "device" else None
     try:
-        return _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
-                                 blocks, held, refs, keep, finalize, timings, cuts)
+        was_in = engine.device_inflate(True) if inflate == "device" else None
+        try:
+            return _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                     blocks, held, refs, keep, finalize, timings, cuts)
+        finally:
+            if was_in is not None:
+                engine.device_inflate(was_in)
     finally:
-        engine.device_bgzf(was)
+        if was is not None:
+            engine.device_bgzf(was)
 
 
 def _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose, blocks, held,

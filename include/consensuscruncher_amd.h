@@ -195,6 +195,22 @@ int ccio_flush(void);
 typedef int (*ccio_deflate_fn)(void *user, const uint8_t *data, uint64_t n, uint8_t *stage, uint64_t slot,
                                uint32_t *out_len, int64_t pieces);
 void ccio_set_deflate_hook(ccio_deflate_fn fn, void *user);
+/* An alternative inflater for the readers' BGZF members (the device inflater: cc_bgzf_inflate_hook
+ * below).  With a hook set, the whole-file open, the region reads and the header read hand their
+ * non-empty members to fn first:
+ *   comp, coff[j], clen[j]   member j's raw DEFLATE payload is comp[coff[j] .. coff[j] + clen[j]);
+ *   out, uoff[j], ulen[j]    its ulen[j] (ISIZE) bytes go to out[uoff[j] .. uoff[j] + ulen[j]);
+ *                            fn writes nowhere else in out;
+ *   ok[j]                    1 when fn inflated member j, 0 when it did not.
+ * fn returns 0 when ok[] is filled in.  libccio then compares the member's CRC32 field with the CRC
+ * of the bytes fn wrote (the host path checks no CRCs).  A member with ok[j] == 0 or another CRC,
+ * and every member after a nonzero return, is inflated by the host codec: a file is never misread
+ * because of the hook, and a member the host codec cannot inflate either gives the error it gives
+ * without one.  fn is called from any thread, several at once.  NULL unsets the hook; unset it
+ * before freeing what user points to. */
+typedef int (*ccio_inflate_fn)(void *user, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
+                               const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out, uint8_t *ok);
+void ccio_set_inflate_hook(ccio_inflate_fn fn, void *user);
 /* per value 0..maxv of v[0..n): count and first index (n when absent), one pass (read_families.txt) */
 int ccio_value_census(const int32_t *v, int64_t n, int32_t maxv, int64_t *first, int64_t *count);
 int ccio_write_bam_ex(const char *path, ccio_bam *tmpl, ccio_interner *it, int64_t n, const cc_out_spec *spec,
@@ -338,6 +354,21 @@ int64_t cc_bgzf_deflate(cc_ctx *ctx, const uint8_t *data, uint64_t n, uint8_t *s
                         uint32_t *out_len, int64_t cap);
 /* the pair to hand to ccio_set_deflate_hook; unset the hook before cc_destroy */
 int cc_bgzf_hook(cc_ctx *ctx, ccio_deflate_fn *fn, void **user);
+/* Raw DEFLATE members inflated on the device (k_bgzf_inflate: one wave per member, many members in
+ * flight; the decode tables, a ring of the compressed bytes and the last 32 KiB of output live in
+ * LDS).  Member j is comp[coff[j] .. coff[j] + clen[j]) and must inflate to exactly ulen[j] bytes,
+ * which go to out[uoff[j] .. uoff[j] + ulen[j]); nothing else in out is written.  ok[j] = 1 for a
+ * good member, 0 for one the device refused: corrupt (a distance before the first byte, an
+ * over-subscribed or incomplete code, symbols 286 / 287 / 30 / 31, LEN != ~NLEN, no final block, more
+ * or fewer bytes than ulen[j]) or larger than a BGZF member (clen or ulen over 65536).  What a
+ * refused member's range of out holds is unspecified.  Returns the number of members with
+ * ok == 0, or a negative CC_E_*.  Rounds of at most 1024 members alternate between the encoder's
+ * two streams; concurrent callers are serialised.  With profiling on, cc_kernel_times reports the
+ * kernel as "bgzf_inflate" and its copies as "bgzf_in_upload" and "bgzf_in_download". */
+int64_t cc_bgzf_inflate(cc_ctx *ctx, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
+                        const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out, uint8_t *ok);
+/* the pair to hand to ccio_set_inflate_hook; unset the hook before cc_destroy */
+int cc_bgzf_inflate_hook(cc_ctx *ctx, ccio_inflate_fn *fn, void **user);
 /* Deferred end-of-pass checks (no reference counterpart: the reference has no device).  With
  * deferral on, a stage call that re-runs a planned pass (cc_read_bam_rerun, cc_consensus_maker,
  * cc_duplex_consensus, cc_singleton_correction on a group that ran before) enqueues its check and
