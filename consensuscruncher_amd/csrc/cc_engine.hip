@@ -5518,9 +5518,13 @@ void flush_prof(cc_ctx* ctx) {
 template <bool MAX, class Emit, class TIn>
 int scan_launch(cc_ctx* ctx, const TIn* in, int64_t n, uint32_t* d_tot, const char* name, Emit em);
 
-// Stable sort of n (key, value) pairs by key bits [begin_bit, end_bit) (k_rs_hist / scan /
-// k_rs_scatter per 8-bit digit): kout / vout receive the result, kin / vin are not written.  Its
-// ping-pong pairs and digit counts live in the context's sort buffer (not the scans' temporary).
+// Stable sort of n (key, value) pairs by whole 8-bit digits of the key (k_rs_hist / scan / k_rs_scatter
+// per digit): the bits that take part are [begin_bit, begin_bit + 8 * ceil((end_bit - begin_bit) / 8)),
+// clipped at 64, which reaches past end_bit when end_bit - begin_bit is no multiple of 8 (the last
+// digit is not masked).  Callers pass keys that are zero between end_bit and that bound, or do not
+// care (cc_group's keys are zero above its bits; every other caller passes 48 or 64 bits from 0).
+// end_bit == begin_bit copies the pairs.  kout / vout receive the result, kin / vin are not written.
+// Its ping-pong pairs and digit counts live in the context's sort buffer (not the scans' temporary).
 int sort_pairs(cc_ctx* ctx, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, int64_t n,
                const char* name, unsigned begin_bit = 0, unsigned end_bit = 64) {
     if (n <= 0) return 0;
@@ -5710,6 +5714,7 @@ int planned_total(cc_ctx* ctx, Group& g, const char* name, uint32_t* d_tot, int6
 }
 
 // exclusive scan of u32 or byte flags with a planned total
+// (byte inputs are flags, 0 or 1: k_scan_reduce sums a word's four bytes with byte_sum, exact only below 256)
 template <class TIn>
 int scan_total(cc_ctx* ctx, Group& g, const TIn* in, uint32_t* out, int64_t n, int64_t* total,
                const char* name) {
@@ -5722,6 +5727,7 @@ int scan_total(cc_ctx* ctx, Group& g, const TIn* in, uint32_t* out, int64_t n, i
 }
 
 // exclusive scan of u32 or byte flags consumed by an emitter (compaction in the scan's store phase)
+// (byte inputs are flags, 0 or 1, as for scan_total)
 template <class Emit, class TIn>
 int scan_emit(cc_ctx* ctx, Group& g, const TIn* in, int64_t n, int64_t* total, const char* name, Emit em) {
     if (n <= 0) { *total = 0; return 0; }
@@ -6169,6 +6175,125 @@ int cc_debug_skew_plan(cc_ctx* ctx, int32_t group_id, const char* name, int64_t 
     if (!g.plan.count(name)) { ctx->err = std::string("no planned total named ") + name; return CC_E_INVALID; }
     g.plan[name] += delta;
     return 0;
+}
+
+}  // extern "C"
+namespace {
+// Test hooks on the engine's own scan and sort (cc_debug_scan, cc_debug_sort_pairs): device buffers of
+// one call, freed when it returns, and the context's switches put back as the call found them.
+constexpr int64_t DBG_TAIL = 64;               // canary elements behind every output array
+constexpr uint32_t DBG_CANARY = 0xA5A5A5A5u;
+struct DbgBufs {
+    std::vector<void*> p;
+    ~DbgBufs() {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+struct DbgSwitches {
+    cc_ctx* ctx;
+    EngineSwitches saved;
+    ~DbgSwitches() { ctx->sw = saved; }
+};
+// `words` 32-bit words, each set to `fill`
+template <typename T>
+int dbg_words(cc_ctx* ctx, DbgBufs& b, T** p, int64_t words, uint32_t fill) {
+    HIPCHK(hipMalloc((void**)p, sizeof(uint32_t) * (size_t)words));
+    b.p.push_back(*p);
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)*p, (int)fill, (size_t)words, ctx->stream));
+    return 0;
+}
+// the caller's `bytes` bytes in a buffer rounded up to 16 bytes (as the engine's flag buffers are), the
+// bytes behind them 0xff: a scan that read past n would count them
+template <typename T>
+int dbg_input(cc_ctx* ctx, DbgBufs& b, T** p, const void* src, int64_t bytes) {
+    const size_t padded = (size_t)std::max<int64_t>((bytes + 15) & ~15LL, 16);
+    HIPCHK(hipMalloc((void**)p, padded));
+    b.p.push_back(*p);
+    HIPCHK(hipMemsetAsync(*p, 0xff, padded, ctx->stream));
+    if (bytes > 0) HIPCHK(hipMemcpyAsync(*p, src, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+// the error word after a hook's launches (waits for the stream); a look-back that waited past its bound is
+// an error here, not a re-run: the hook ran the engine it was asked for
+int dbg_finish(cc_ctx* ctx) {
+    HIPCHK(hipGetLastError());
+    uint32_t bits = 0;
+    RC(read_err(ctx, &bits));
+    const int rc = err_code(ctx, bits);
+    return rc == CC_E_SCANWAIT ? CC_E_INVALID : rc;
+}
+}  // namespace
+extern "C" {
+
+// test hook: scan_launch itself on the caller's input, with the engine's own consumers (the header has
+// the kinds).  It reaches k_scan_reduce, k_scan_down and k_scan_one for u32 input with ScanStore and for
+// byte flags with ScanStore, an unstaged emitter (EmitList) and a staged one (EmitVotePairs).  It does
+// NOT reach scan_launch<true> (the running max) nor the u32-input emitter branch of the store phase:
+// the engine instantiates neither (every emitter call site passes byte flags), so no test covers them.
+int cc_debug_scan(cc_ctx* ctx, int32_t kind, int32_t engine, const void* in, int64_t n, const int32_t* aux,
+                  void* out_a, void* out_b, int64_t* total) {
+    if (!ctx) return CC_E_INVALID;
+    if (kind < 0 || kind > 3 || engine < -1 || engine > 1 || n < 0 || n >= INT32_MAX - DBG_TAIL || !total || !out_a ||
+        (n > 0 && !in) || (kind >= 2 && !out_b) || (kind == 3 && n > 0 && !aux)) {
+        ctx->err = "cc_debug_scan: kind 0..3, engine -1..1, 0 <= n < 2^31 - 65, and the arrays of the kind";
+        return CC_E_INVALID;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    DbgSwitches sw{ctx, ctx->sw};
+    ctx->sw.scan1 = engine;
+    DbgBufs bufs;
+    uint8_t* d_in = nullptr;
+    int32_t* d_aux = nullptr;
+    uint32_t *d_a = nullptr, *d_b = nullptr, *d_tot = nullptr;
+    const int64_t b_words = kind == 2 ? n + DBG_TAIL : kind == 3 ? 4 * (n + DBG_TAIL) : 0;
+    RC(dbg_input(ctx, bufs, &d_in, in, n * (kind == 0 ? 4 : 1)));
+    if (kind == 3) RC(dbg_input(ctx, bufs, &d_aux, aux, 12 * n));
+    RC(dbg_words(ctx, bufs, &d_a, n + DBG_TAIL, DBG_CANARY));
+    if (b_words) RC(dbg_words(ctx, bufs, &d_b, b_words, DBG_CANARY));
+    RC(dbg_words(ctx, bufs, &d_tot, 4, 0u));
+    HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
+    if (n > 0) {   // (n == 0: no launch, as scan_total / scan_emit)
+        if (kind == 0) RC(scan_launch<false>(ctx, (const uint32_t*)d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
+        if (kind == 1) RC(scan_launch<false>(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
+        if (kind == 2)
+            RC(scan_launch<false>(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan", EmitList{(int32_t*)d_a, (int32_t*)d_b}));
+        if (kind == 3)
+            RC(scan_launch<false>(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan",
+                                  EmitVotePairs{d_aux, d_aux + n, d_aux + 2 * n, (int32_t*)d_a, (int4*)d_b}));
+    }
+    uint32_t* h_tot = (uint32_t*)ctx->h_pinned;
+    HIPCHK(hipMemcpyAsync(out_a, d_a, sizeof(uint32_t) * (size_t)(n + DBG_TAIL), hipMemcpyDeviceToHost, ctx->stream));
+    if (b_words) HIPCHK(hipMemcpyAsync(out_b, d_b, sizeof(uint32_t) * (size_t)b_words, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_tot, d_tot, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RC(dbg_finish(ctx));
+    *total = (int64_t)h_tot[0];
+    return 0;
+}
+
+// test hook: sort_pairs itself on the caller's pairs, its digit scans by the chosen scan engine
+int cc_debug_sort_pairs(cc_ctx* ctx, int32_t engine, const uint64_t* keys, const uint32_t* vals, int64_t n,
+                        uint32_t begin_bit, uint32_t end_bit, uint64_t* out_keys, uint32_t* out_vals) {
+    if (!ctx) return CC_E_INVALID;
+    if (engine < -1 || engine > 1 || n < 0 || n >= INT32_MAX - DBG_TAIL || begin_bit > end_bit || end_bit > 64 ||
+        !out_keys || !out_vals || (n > 0 && (!keys || !vals))) {
+        ctx->err = "cc_debug_sort_pairs: engine -1..1, 0 <= n < 2^31 - 65, begin_bit <= end_bit <= 64, and the arrays";
+        return CC_E_INVALID;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    DbgSwitches sw{ctx, ctx->sw};
+    ctx->sw.scan1 = engine;
+    DbgBufs bufs;
+    uint64_t *d_k = nullptr, *d_ko = nullptr;
+    uint32_t *d_v = nullptr, *d_vo = nullptr;
+    RC(dbg_input(ctx, bufs, &d_k, keys, 8 * n));
+    RC(dbg_input(ctx, bufs, &d_v, vals, 4 * n));
+    RC(dbg_words(ctx, bufs, &d_ko, 2 * (n + DBG_TAIL), DBG_CANARY));
+    RC(dbg_words(ctx, bufs, &d_vo, n + DBG_TAIL, DBG_CANARY));
+    HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
+    RC(sort_pairs(ctx, d_k, d_ko, d_v, d_vo, n, "debug_sort", begin_bit, end_bit));
+    HIPCHK(hipMemcpyAsync(out_keys, d_ko, sizeof(uint64_t) * (size_t)(n + DBG_TAIL), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out_vals, d_vo, sizeof(uint32_t) * (size_t)(n + DBG_TAIL), hipMemcpyDeviceToHost, ctx->stream));
+    return dbg_finish(ctx);
 }
 
 int cc_synchronize(cc_ctx* ctx) {

@@ -450,6 +450,37 @@ class Engine(object):
             raise N.CCError(nb, self.lib.cc_last_error(self.h).decode(errors="replace"))
         return out[:nb].view(dtype)
 
+    def debug_scan(self, kind, engine, values, aux=None):
+        """The engine's scan on `values` (cc_debug_scan; kind 0: uint32 values, kinds 1-3: uint8 0/1 flags;
+        engine 0 reduce-then-scan, 1 look-back, -1 the default; aux: kind 3's t_rec, p_rec, dec as 3 * n
+        int32).  Returns (out_a, out_b, total) WITH the 64 canary elements behind each array: out_a is
+        uint32 prefix[n + 64] (kinds 0, 1) or int32 vslot[n + 64]; out_b is None, int32 list[n + 64]
+        (kind 2) or int32 vpair[n + 64, 4] (kind 3), written up to `total`."""
+        values = np.ascontiguousarray(values, np.uint32 if kind == 0 else np.uint8)
+        n = len(values)
+        out_a = np.zeros(n + 64, np.uint32 if kind < 2 else np.int32)
+        out_b = None if kind < 2 else np.zeros(n + 64 if kind == 2 else (n + 64, 4), np.int32)
+        if aux is not None:
+            aux = np.ascontiguousarray(aux, np.int32)
+            assert aux.size == 3 * n
+        total = C.c_int64(-1)
+        self._check(self.lib.cc_debug_scan(self.h, int(kind), int(engine), N.ptr(values), n, N.ptr(aux), N.ptr(out_a),
+                                           N.ptr(out_b), C.byref(total)))
+        return out_a, out_b, total.value
+
+    def debug_sort_pairs(self, engine, keys, vals, begin_bit=0, end_bit=64):
+        """The engine's radix sort on (uint64 key, uint32 value) pairs (cc_debug_sort_pairs; engine: the
+        digit scans' engine, as for debug_scan).  Returns (keys, vals) WITH 64 canary elements behind."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        vals = np.ascontiguousarray(vals, np.uint32)
+        n = len(keys)
+        assert len(vals) == n
+        out_k = np.zeros(n + 64, np.uint64)
+        out_v = np.zeros(n + 64, np.uint32)
+        self._check(self.lib.cc_debug_sort_pairs(self.h, int(engine), N.ptr(keys), N.ptr(vals), n, int(begin_bit),
+                                                 int(end_bit), N.ptr(out_k), N.ptr(out_v)))
+        return out_k, out_v
+
     def upload(self, records):
         tid = C.c_int32()
         self._check(self.lib.cc_table_upload(self.h, C.byref(records.struct), records.max_len, C.byref(tid)))

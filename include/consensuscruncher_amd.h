@@ -394,6 +394,40 @@ int64_t cc_launch_count(void);
 int64_t cc_guard_reruns(cc_ctx *ctx);
 /* test hook: group buffer `name` grown to at least `bytes` and every byte set to `value` */
 int cc_debug_poison(cc_ctx *ctx, int32_t group_id, const char *name, int64_t bytes, int32_t value);
+/* test hook: the engine's prefix scan (scan_launch: k_scan_reduce + k_scan_down, or the single-launch
+ * look-back k_scan_one; tiles of 4096 elements) on the caller's input, on the context's stream, with
+ * the engine's own consumers.  kind selects the instantiation class:
+ *   0  in = n uint32 values   ScanStore       out_a = exclusive prefix[n]
+ *   1  in = n uint8 flags     ScanStore       out_a = exclusive prefix[n]
+ *   2  in = n uint8 flags     EmitList        out_a = vslot[n] (the flagged element's rank, else -1),
+ *                                             out_b = list[total] (the flagged indices, int32)
+ *   3  in = n uint8 flags     EmitVotePairs   out_a = vslot[n], out_b = vpair[total] as 4 x int32
+ *                                             {t_rec[i], p_rec[i], dec[i], i}; aux = t_rec[n], p_rec[n],
+ *                                             dec[n] (3 * n int32)
+ * Byte flags must be 0 or 1 (the reduce kernel sums four of them in one multiply), and the sums must
+ * stay below 2^32.  engine: 0 reduce-then-scan, 1 look-back, -1 the engine's own choice (look-back up
+ * to 64 tiles); the hook sets the context's switch for the call and restores it, CC_SCAN1 is not read.
+ * The device input is padded to a multiple of 16 bytes with 0xff bytes, so a scan that read past n
+ * would count them.  Every output array has 64 more elements than named above, in the caller's
+ * arrays too: out_a holds n + 64 words, out_b n + 64 elements (kind 2: int32, kind 3: 4 x int32; unused
+ * and may be NULL for kinds 0 and 1).  The device arrays are pre-filled with 0xA5A5A5A5 words and copied
+ * back whole, so every element behind the last one written (out_a from n, out_b from total) must
+ * still hold that word.  n == 0 launches nothing and returns total 0.  *total receives the scan's
+ * total.  A look-back that waited past its bound is reported as CC_E_INVALID (no re-run).
+ * Not reached by this hook, because the engine never instantiates them: scan_launch<true> (the
+ * inclusive running max) and the store phase's branch for emitters fed uint32 input (every emitter
+ * call site passes byte flags; uint32 input only meets ScanStore).  EmitList has no call site but
+ * this one: the engine's other unstaged emitters (EmitGather, EmitFamStarts, ...) share its branch. */
+int cc_debug_scan(cc_ctx *ctx, int32_t kind, int32_t engine, const void *in, int64_t n, const int32_t *aux,
+                  void *out_a, void *out_b, int64_t *total);
+/* test hook: the engine's stable LSD radix sort (sort_pairs: k_rs_hist, the scan, k_rs_scatter per 8-bit
+ * digit) on the caller's n (key, value) pairs; engine chooses the digit scans' engine as above.  The
+ * sort works in whole digits: it orders by key bits
+ * [begin_bit, min(64, begin_bit + 8 * ceil((end_bit - begin_bit) / 8))), stably, and moves whole keys;
+ * begin_bit == end_bit copies the pairs.  begin_bit <= end_bit <= 64.  out_keys and out_vals hold
+ * n + 64 elements: the 64 behind the result keep the pre-filled 0xA5 bytes. */
+int cc_debug_sort_pairs(cc_ctx *ctx, int32_t engine, const uint64_t *keys, const uint32_t *vals, int64_t n,
+                        uint32_t begin_bit, uint32_t end_bit, uint64_t *out_keys, uint32_t *out_vals);
 
 /* copy a record SoA into HBM; returns a table id.  With the decoder's layout (rec->meta non-NULL,
  * rec->n_deep >= 0) its columns are uploaded as they are; otherwise k_derive builds them on the device */
