@@ -40,6 +40,7 @@
 #include <mutex>
 #include <type_traits>
 #include <string>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -5261,6 +5262,93 @@ struct DevBuf {
     size_t used = 0;
 };
 
+// Every buffer of a group (the scratch group of the function-level calls included): its name, as
+// cc_fetch and cc_debug_poison take it, and its element type, stated here once.  GB / gbuf allocate
+// by id and Group::ptr reads by id, both with the type of this list.
+#define CC_GROUP_BUFFERS(X)                                                                                          \
+    X(plan_totals, uint32_t) X(plan_stripes, uint32_t)                                                               \
+    X(stream_rec, int32_t) X(stream_region, int32_t) X(region_run, int32_t)                                          \
+    X(pc_ltab, unsigned long long) X(pc_pkeys, uint64_t) X(fam_drop, int32_t) X(cflag, uint8_t)                      \
+    X(csn_ht_key, unsigned long long) X(pc_rq, uint64_t) X(pc_spos, int32_t) X(rec_e, int32_t) X(skey, uint64_t)     \
+    X(sval, uint32_t) X(skey2, uint64_t) X(sval2, uint32_t) X(badflag, uint8_t) X(mate_of, int32_t)                  \
+    X(pflag, uint8_t) X(pc_partner, int32_t) X(pc_claims, int32_t) X(pc_resid, uint8_t) X(deep_gq, uint64_t)         \
+    X(deep_gend, int32_t) X(deep_boff, uint32_t) X(deep_gid, uint32_t) X(deep_dgk, unsigned long long)               \
+    X(pc_rk_app, uint64_t) X(pc_rv_app, uint32_t) X(lp_hist, uint32_t) X(lp_off, uint32_t) X(lp_bkeys, uint64_t)     \
+    X(pc_rht, unsigned long long) X(pc_bloom, unsigned long long) X(pc_hcnt, uint32_t) X(pc_hmin, uint32_t)          \
+    X(pc_hmax, uint32_t) X(pc_rk, uint64_t) X(pc_rv, uint32_t) X(pr_rec1, int32_t) X(pr_rec2, int32_t)               \
+    X(pr_region, int32_t) X(pr_tag, int4) X(chash, uint64_t) X(rec_thash, uint64_t) X(rec_tag, int4)                 \
+    X(thash, uint64_t) X(tval, uint32_t) X(rs_key, uint64_t) X(rs_val, uint32_t) X(grp_bigE, uint32_t)               \
+    X(mem_rec, int32_t) X(segf, uint8_t) X(mem_valid, uint32_t) X(mem_meta, uint4) X(grp_tile_small, uint32_t)       \
+    X(grp_tile_pre, uint32_t) X(grp_bx, uint32_t) X(grp_bkey, uint64_t) X(grp_bval, uint32_t)                        \
+    X(deep_gcnt, uint32_t) X(deep_goff, uint32_t) X(deep_se, uint32_t) X(deep_items, int4) X(deep_big, int4)         \
+    X(fam_beg, int32_t) X(fam_end, int32_t) X(fam_n, int32_t) X(fam_first, int32_t) X(fam_region, int32_t)           \
+    X(fam_hash, uint64_t) X(cfam, int32_t) X(fam_o, int32_t) X(fam_tag, TagKey) X(fam_rec, int32_t)                  \
+    X(fam_by_k, int32_t) X(fam_k, int32_t) X(pair_by_k, int32_t) X(fam_sizes_by_creation, int32_t)                   \
+    X(csegf, uint32_t) X(emark, uint8_t) X(e1k, int32_t) X(ekey, uint64_t) X(eval, uint32_t) X(es_key, uint64_t)     \
+    X(es_val, uint32_t) X(ent_f, int32_t) X(ent_pair, int32_t) X(has2, uint8_t)                                      \
+    /* the stages: SSCS and its vote, DCS, singleton correction */                                                   \
+    X(hx, uint32_t) X(emit_ekey, uint64_t) X(emit_skey, uint64_t) X(emit_eval, uint32_t) X(emit_sval, uint32_t)      \
+    X(emit_fam, int32_t) X(emit_n, int32_t) X(emit_rec, int32_t) X(emit_ckey, int32_t) X(needv, uint8_t)             \
+    X(emit_span, int2) X(vxs, uint32_t) X(bad_rec, int32_t) X(vote_fam, int32_t) X(vote_order, int4)                 \
+    X(emit_vslot, int32_t) X(cons_seq, uint8_t) X(cons_qual, uint8_t) X(vote_meta, int32_t)                          \
+    X(vote_slow_list, int32_t) X(cutoff_thr, int32_t) X(vote_big_item, int32_t) X(vote_items, int4)                  \
+    X(vote_partial, uint8_t) X(vote_item_fl, uint32_t) X(bc_swap, int32_t) X(dec, int32_t) X(t_rec, int32_t)         \
+    X(p_rec, int32_t) X(fl_dcs, uint8_t) X(fl_corr, uint8_t) X(ht_key, unsigned long long) X(ht_val, int32_t)        \
+    X(fam_bkt, int32_t) X(fam_del, int32_t) X(vslot, int32_t) X(vpair, int4) X(q_pair, int32_t) X(q_ckey, int32_t)   \
+    /* the scratch group: cc_group, cc_duplex_join, cc_extract_barcodes, the reductions */                           \
+    X(grp_keys, uint32_t) X(grp_tab, int32_t) X(grp_slot_of, int32_t) X(grp_slot_first, int32_t)                     \
+    X(grp_slot_cnt, int32_t) X(grp_start, uint32_t) X(grp_fx, uint32_t) X(grp_fsize, uint32_t)                       \
+    X(grp_foff, uint32_t) X(grp_fkey, uint64_t) X(grp_fval, uint32_t) X(grp_skey, uint64_t) X(grp_sval, uint32_t)    \
+    X(join_keys, uint32_t) X(join_pkeys, uint32_t) X(join_xkeys, uint32_t) X(join_tab, int32_t)                      \
+    X(join_xtab, int32_t) X(join_p, int32_t) X(join_xs, int32_t) X(join_xfirst, int32_t) X(join_indeg, int32_t)      \
+    X(join_dec, int32_t) X(join_part, int32_t) X(join_flags, uint32_t) X(join_used, uint8_t) X(join_gone, uint8_t)   \
+    X(join_xgone, uint8_t) X(eb_h1, uint8_t) X(eb_h2, uint8_t) X(eb_l1, int32_t) X(eb_l2, int32_t)                   \
+    X(eb_status, uint8_t) X(eb_bc, char) X(eb_cut1, int32_t) X(eb_cut2, int32_t) X(eb_bad1, uint32_t)                \
+    X(eb_bad2, uint32_t) X(eb_counts, unsigned long long) X(eb_hist, unsigned long long)                             \
+    X(eb_tkey, unsigned long long) X(eb_tval, int32_t) X(reduce_buf, int64_t) X(reduce_max, int64_t)
+
+enum class B : int {
+#define X(name, T) name,
+    CC_GROUP_BUFFERS(X)
+#undef X
+    COUNT
+};
+constexpr const char* BUF_NAME[] = {
+#define X(name, T) #name,
+    CC_GROUP_BUFFERS(X)
+#undef X
+};
+template <B id> struct BufType;
+#define X(name, T) template <> struct BufType<B::name> { using type = T; };
+CC_GROUP_BUFFERS(X)
+#undef X
+template <B id> using BufT = typename BufType<id>::type;
+
+// Every planned total (see Group::plan): a scan's total under the scan's profile scope name, or a
+// count a kernel leaves.  A total's slot of plan_totals is its value here.
+#define CC_PLAN_TOTALS(X)                                                                                            \
+    X(n_resid) X(n_big) X(n_drop) X(n_long) X(lp_found) X(n_multi) X(resid_app) X(lp_total) X(resid_multi)           \
+    X(deep_ovf) X(deep_items) X(deep_big) X(csn_shared) X(scan_resid) X(scan_pairs) X(scan_small) X(scan_bigE)       \
+    X(scan_deep) X(scan_fam) X(scan_creation) X(scan_entries) X(scan_emit) X(scan_vote) X(vote_items) X(vote_slow)   \
+    X(scan_bad) X(scan_dcs) X(scan_sc) X(grp_scan_fam) X(grp_scan_off)
+
+enum class PT : int {
+#define X(name) name,
+    CC_PLAN_TOTALS(X)
+#undef X
+    COUNT
+};
+constexpr const char* PLAN_NAME[] = {
+#define X(name) #name,
+    CC_PLAN_TOTALS(X)
+#undef X
+};
+constexpr int PLAN_SLOTS = 64;
+static_assert((int)PT::COUNT <= PLAN_SLOTS, "a planned total's slot is its id");
+
+enum Stage { ST_READ_BAM, ST_SSCS, ST_DCS, ST_SC, ST_COUNT };   // the stages run_planned runs
+constexpr const char* STAGE_NAME[ST_COUNT] = {"read_bam", "sscs", "dcs", "sc"};
+
 struct Group {
     int32_t table = -1;
     int64_t S = 0, P = 0, R = 0, F = 0, E = 0, Q = 0, NV = 0;
@@ -5275,21 +5363,24 @@ struct Group {
     int ident = 0;               // stream_rec[s] == s for every s (the whole table in file order)
     bool local_groups = false;   // families of each position group contiguous (coordinate grouping, no deep group)
     int64_t counters[CC_NUM_COUNTERS] = {0};
-    std::map<std::string, DevBuf> buf;
+    DevBuf buf[(int)B::COUNT];
+    // a buffer's typed pointer (null while the group has never allocated it)
+    template <B id> BufT<id>* ptr() const { return (BufT<id>*)buf[(int)id].p; }
     // Launch plan: every device-side total (scan totals, the csn sharing flag) of the last exact
-    // pass of each stage on this group, keyed by name.  A re-run on the same resident stream takes
-    // its sizes and grids from the plan instead of waiting for each total, and checks all of them
-    // against the device in the one readback at the end; a mismatch re-runs the stage exactly.
-    std::map<std::string, int64_t> plan;
-    std::map<std::string, int> slot;
-    std::map<std::string, bool> planned;   // stage -> has a complete plan
+    // pass of each stage on this group, by id; plan_set marks the totals that exist.  A re-run on the
+    // same resident stream takes its sizes and grids from the plan instead of waiting for each total,
+    // and checks all of them against the device in the one readback at the end; a mismatch re-runs
+    // the stage exactly.
+    int64_t plan[(int)PT::COUNT] = {0};
+    bool plan_set[(int)PT::COUNT] = {false};
+    bool planned[ST_COUNT] = {false};   // stage -> has a complete plan
     bool fast = false;
     bool members_built = false;  // mem_meta holds the last pass's member records
     int64_t n_deepg = 0;         // deep position groups of the last pass (k_build_meta's list)
     bool fam_tags_built = false; // fam_tag holds the last pass's family tags
     bool overlap = false;        // the stream holds a record twice (overlapping bed regions)
     int32_t n_regions = 1;       // bed regions of the stream (cc_read_bam)
-    std::vector<std::string> verify;
+    std::vector<PT> verify;
     std::vector<int32_t> swap_host;   // the barcode swap table last uploaded (bc_swap)
     double thr_cutoff = -1.0;         // the cutoff cutoff_thr holds (k_cutoff_table, once per cutoff)
 };
@@ -5311,7 +5402,21 @@ constexpr int CC_E_PLAN = -100;   // internal: a planned total did not hold (re-
 constexpr int CC_E_NEEDSORT = -101;   // internal: coordinate pairing met a qname seen 3+ times
 constexpr int CC_E_DEEPSORT = -102;   // internal: a deep family needs the sorted deep-group path
 constexpr int CC_E_SCANWAIT = -103;   // internal: a look-back scan waited past its bound (re-run with two-launch scans)
-constexpr int PLAN_SLOTS = 64;
+
+// The name-taking entry points (cc_fetch, the test hooks) resolve a name through its table's index,
+// built once: the id, or -1 for a name the table does not hold.
+using NameIndex = std::unordered_map<std::string, int>;
+NameIndex name_index(const char* const* names, int n) {
+    NameIndex ix;
+    for (int i = 0; i < n; ++i) ix[names[i]] = i;
+    return ix;
+}
+const NameIndex BUF_IDS = name_index(BUF_NAME, (int)B::COUNT);
+const NameIndex PLAN_IDS = name_index(PLAN_NAME, (int)PT::COUNT);
+inline int name_id(const NameIndex& ix, const char* name) {
+    const auto it = ix.find(name);
+    return it != ix.end() ? it->second : -1;
+}
 
 // The engine's environment switches ("Engine switches"): every one there is, read by
 // read_switches() at the top of each entry point that uses one (per call: a test changes them between
@@ -5434,24 +5539,30 @@ struct Fills {
     int launch();
 };
 
-template <typename T>
-T* gbuf(cc_ctx* ctx, Group& g, const char* name, int64_t count, int* rc) {
-    DevBuf& b = g.buf[name];
-    size_t need = (size_t)std::max<int64_t>(count, 1) * sizeof(T);
+// a group's buffer grown to at least `need` bytes (null, *rc set: the allocation failed)
+void* gbuf_bytes(cc_ctx* ctx, Group& g, B id, size_t need, int* rc) {
+    DevBuf& b = g.buf[(int)id];
     if (b.bytes < need) {
         if (b.p) (void)hipFree(b.p);
         b.p = nullptr;
         hipError_t e = hipMalloc(&b.p, need);
         if (e != hipSuccess) {
-            ctx->err = std::string("hipMalloc failed for ") + name + ": " + hipGetErrorString(e);
+            ctx->err = std::string("hipMalloc failed for ") + BUF_NAME[(int)id] + ": " + hipGetErrorString(e);
             *rc = CC_E_HIP;
             b.bytes = 0;
             return nullptr;
         }
         b.bytes = need;
     }
-    b.used = (size_t)std::max<int64_t>(count, 0) * sizeof(T);
-    return (T*)b.p;
+    return b.p;
+}
+
+template <B id>
+BufT<id>* gbuf(cc_ctx* ctx, Group& g, int64_t count, int* rc) {
+    using T = BufT<id>;
+    void* p = gbuf_bytes(ctx, g, id, (size_t)std::max<int64_t>(count, 1) * sizeof(T), rc);
+    if (p) g.buf[(int)id].used = (size_t)std::max<int64_t>(count, 0) * sizeof(T);
+    return (T*)p;
 }
 
 void* tmp_storage(cc_ctx* ctx, size_t bytes, int* rc) {
@@ -5666,76 +5777,68 @@ int Fills::launch() {
     return hipGetLastError() == hipSuccess ? 0 : CC_E_HIP;
 }
 
-uint32_t* plan_slot(cc_ctx* ctx, Group& g, const char* name, int* rc) {
-    uint32_t* dtot = gbuf<uint32_t>(ctx, g, "plan_totals", PLAN_SLOTS, rc);
+uint32_t* plan_slot(cc_ctx* ctx, Group& g, PT id, int* rc) {
+    uint32_t* dtot = gbuf<B::plan_totals>(ctx, g, PLAN_SLOTS, rc);
     if (*rc) return nullptr;
-    auto it = g.slot.find(name);
-    const int s = it != g.slot.end() ? it->second : (int)g.slot.size();
-    if (s >= PLAN_SLOTS) { ctx->err = "too many planned totals"; *rc = CC_E_INVALID; return nullptr; }
-    g.slot[name] = s;
-    return dtot + s;
+    return dtot + (int)id;
 }
 
 // the stripes of a plan slot's count (stripe_add / k_stripe_total), zeroed once when created
 uint32_t* plan_stripes(cc_ctx* ctx, Group& g, uint32_t* slot, int* rc) {
-    const bool fresh = !g.buf.count("plan_stripes") || !g.buf["plan_stripes"].p;
-    uint32_t* st = gbuf<uint32_t>(ctx, g, "plan_stripes", (int64_t)PLAN_SLOTS * PSTRIPES * PSTRIDE, rc);
+    const bool fresh = !g.ptr<B::plan_stripes>();
+    uint32_t* st = gbuf<B::plan_stripes>(ctx, g, (int64_t)PLAN_SLOTS * PSTRIPES * PSTRIDE, rc);
     if (*rc) return nullptr;
     if (fresh && hipMemsetAsync(st, 0, sizeof(uint32_t) * PLAN_SLOTS * PSTRIPES * PSTRIDE, ctx->stream) != hipSuccess) {
         *rc = CC_E_HIP;
         return nullptr;
     }
-    return st + (slot - (uint32_t*)g.buf["plan_totals"].p) * (int64_t)PSTRIPES * PSTRIDE;
+    return st + (slot - g.ptr<B::plan_totals>()) * (int64_t)PSTRIPES * PSTRIDE;
 }
 
 // The plan as a planned pass sees it: whether it holds a total, and the total or a default (an exact
-// pass: never, and the default).  Neither adds a key: the plan's keys are the totals that exist.
-inline bool has_plan(const Group& g, const char* name) { return g.fast && g.plan.count(name) != 0; }
-inline int64_t plan_or(const Group& g, const char* name, int64_t dflt) {
-    if (!g.fast) return dflt;
-    const auto it = g.plan.find(name);
-    return it != g.plan.end() ? it->second : dflt;
-}
+// pass: never, and the default).
+inline bool has_plan(const Group& g, PT id) { return g.fast && g.plan_set[(int)id]; }
+inline int64_t plan_or(const Group& g, PT id, int64_t dflt) { return has_plan(g, id) ? g.plan[(int)id] : dflt; }
 
 // A device total: on a planned re-run the plan's value (checked at the end), otherwise read back
 // now (synchronises) and recorded in the plan.
-int planned_total(cc_ctx* ctx, Group& g, const char* name, uint32_t* d_tot, int64_t* total) {
-    if (has_plan(g, name)) {
-        *total = g.plan[name];
-        g.verify.push_back(name);
+int planned_total(cc_ctx* ctx, Group& g, PT id, uint32_t* d_tot, int64_t* total) {
+    if (has_plan(g, id)) {
+        *total = g.plan[(int)id];
+        g.verify.push_back(id);
         return 0;
     }
     uint32_t* h = (uint32_t*)ctx->h_pinned;
     HIPCHK(hipMemcpyAsync(h, d_tot, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(stream_wait(ctx));
     *total = (int64_t)h[0];
-    g.plan[name] = *total;
+    g.plan[(int)id] = *total;
+    g.plan_set[(int)id] = true;
     return 0;
 }
 
-// exclusive scan of u32 or byte flags with a planned total
+// exclusive scan of u32 or byte flags with a planned total (the total's name is the scan's profile scope)
 // (byte inputs are flags, 0 or 1: k_scan_reduce sums a word's four bytes with byte_sum, exact only below 256)
 template <class TIn>
-int scan_total(cc_ctx* ctx, Group& g, const TIn* in, uint32_t* out, int64_t n, int64_t* total,
-               const char* name) {
+int scan_total(cc_ctx* ctx, Group& g, const TIn* in, uint32_t* out, int64_t n, int64_t* total, PT id) {
     if (n <= 0) { *total = 0; return 0; }
     int rc = 0;
-    uint32_t* d_tot = plan_slot(ctx, g, name, &rc);
+    uint32_t* d_tot = plan_slot(ctx, g, id, &rc);
     if (rc) return rc;
-    RC(scan_launch<false>(ctx, in, n, d_tot, name, ScanStore{out}));
-    return planned_total(ctx, g, name, d_tot, total);
+    RC(scan_launch<false>(ctx, in, n, d_tot, PLAN_NAME[(int)id], ScanStore{out}));
+    return planned_total(ctx, g, id, d_tot, total);
 }
 
 // exclusive scan of u32 or byte flags consumed by an emitter (compaction in the scan's store phase)
 // (byte inputs are flags, 0 or 1, as for scan_total)
 template <class Emit, class TIn>
-int scan_emit(cc_ctx* ctx, Group& g, const TIn* in, int64_t n, int64_t* total, const char* name, Emit em) {
+int scan_emit(cc_ctx* ctx, Group& g, const TIn* in, int64_t n, int64_t* total, PT id, Emit em) {
     if (n <= 0) { *total = 0; return 0; }
     int rc = 0;
-    uint32_t* d_tot = plan_slot(ctx, g, name, &rc);
+    uint32_t* d_tot = plan_slot(ctx, g, id, &rc);
     if (rc) return rc;
-    RC(scan_launch<false>(ctx, in, n, d_tot, name, em));
-    return planned_total(ctx, g, name, d_tot, total);
+    RC(scan_launch<false>(ctx, in, n, d_tot, PLAN_NAME[(int)id], em));
+    return planned_total(ctx, g, id, d_tot, total);
 }
 
 // End of a stage pass: ONE readback of the error word, the read_bam counters (optional) and the
@@ -5755,11 +5858,11 @@ int finish_pass(cc_ctx* ctx, Group& g, uint32_t* bits, bool counters, bool* plan
         const bool totals = !g.verify.empty();
         hipLaunchKernelGGL(k_defer_pack, dim3(1), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_err,
                            counters ? (const unsigned long long*)ctx->d_cnt : nullptr,
-                           totals ? (const uint32_t*)g.buf["plan_totals"].p : nullptr, PLAN_SLOTS,
-                           g.stripes_pending ? (const uint32_t*)g.buf["plan_stripes"].p : nullptr, dh);
+                           totals ? g.ptr<B::plan_totals>() : nullptr, PLAN_SLOTS,
+                           g.stripes_pending ? g.ptr<B::plan_stripes>() : nullptr, dh);
         g.stripes_pending = false;
         if (totals)
-            for (const auto& nm : g.verify) d.expect.push_back({g.slot[nm], g.plan[nm]});
+            for (const PT id : g.verify) d.expect.push_back({(int)id, g.plan[(int)id]});
         g.verify.clear();
         ctx->deferred.push_back(std::move(d));
         *bits = 0;
@@ -5774,12 +5877,12 @@ int finish_pass(cc_ctx* ctx, Group& g, uint32_t* bits, bool counters, bool* plan
                               hipMemcpyDeviceToHost,
                               ctx->stream));
     if (g.stripes_pending) {
-        hipLaunchKernelGGL(k_stripe_fold, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t*)g.buf["plan_stripes"].p,
-                           (uint32_t*)g.buf["plan_totals"].p, PLAN_SLOTS);
+        hipLaunchKernelGGL(k_stripe_fold, dim3(1), dim3(64), 0, ctx->stream, g.ptr<B::plan_stripes>(),
+                           g.ptr<B::plan_totals>(), PLAN_SLOTS);
         g.stripes_pending = false;
     }
     if (!g.verify.empty())
-        HIPCHK(hipMemcpyAsync(h + 256, g.buf["plan_totals"].p, 4 * PLAN_SLOTS, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(h + 256, g.ptr<B::plan_totals>(), 4 * PLAN_SLOTS, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(stream_wait(ctx));
     RC(dbg_fault(ctx));
     *bits = *(uint32_t*)(h + 16);
@@ -5794,8 +5897,8 @@ int finish_pass(cc_ctx* ctx, Group& g, uint32_t* bits, bool counters, bool* plan
             g.counters[i] = t;
         }
     *plan_ok = !cap_over;
-    for (const auto& nm : g.verify)
-        if ((int64_t)((uint32_t*)(h + 256))[g.slot[nm]] != g.plan[nm]) *plan_ok = false;
+    for (const PT id : g.verify)
+        if ((int64_t)((uint32_t*)(h + 256))[(int)id] != g.plan[(int)id]) *plan_ok = false;
     g.verify.clear();
     return 0;
 }
@@ -5806,7 +5909,7 @@ int finish_pass(cc_ctx* ctx, Group& g, uint32_t* bits, bool counters, bool* plan
 // share a GPU) substituted 0 for a prefix it never saw: the pass runs once more, exactly, with every
 // scan as the reduce-then-scan pair, which waits on nothing.
 template <typename Pass>
-int run_planned(cc_ctx* ctx, Group& g, const char* stage, Pass pass) {
+int run_planned(cc_ctx* ctx, Group& g, Stage stage, Pass pass) {
     int rc = CC_E_PLAN;
     if (g.planned[stage]) {
         g.fast = true;
@@ -5820,7 +5923,7 @@ int run_planned(cc_ctx* ctx, Group& g, const char* stage, Pass pass) {
     }
     if (rc == CC_E_SCANWAIT && !ctx->scan_two) {
         ++ctx->scan_retries;
-        if (getenv("CC_SCAN_SPIN_MAX")) fprintf(stderr, "[cc] %s: look-back scan bound hit, pass re-run (%lld)\n", stage,
+        if (getenv("CC_SCAN_SPIN_MAX")) fprintf(stderr, "[cc] %s: look-back scan bound hit, pass re-run (%lld)\n", STAGE_NAME[stage],
                                                 (long long)ctx->scan_retries);
         ctx->scan_two = true;
         g.verify.clear();
@@ -5870,14 +5973,13 @@ int upload(cc_ctx* ctx, std::vector<void*>& allocs, T** dst, const T* src, int64
     return 0;
 }
 
-#define GB(T, name, count) gbuf<T>(ctx, g, name, count, &brc); if (brc) return brc
+#define GB(name, count) gbuf<B::name>(ctx, g, count, &brc); if (brc) return brc
 
 // k_deleted_late over group g's families (fam_del: the region each was deleted in)
 int deleted_late(cc_ctx* ctx, Group& g, const int32_t* fdel) {
     if (g.F <= 0) return 0;
-    hipLaunchKernelGGL(k_deleted_late, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F, fdel,
-                       (const int32_t*)g.buf["fam_beg"].p, (const int32_t*)g.buf["fam_end"].p,
-                       (const uint32_t*)g.buf["rs_val"].p, (const int32_t*)g.buf["pr_region"].p, ctx->d_err);
+    hipLaunchKernelGGL(k_deleted_late, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F, fdel, g.ptr<B::fam_beg>(),
+                       g.ptr<B::fam_end>(), g.ptr<B::rs_val>(), g.ptr<B::pr_region>(), ctx->d_err);
     return 0;
 }
 
@@ -5886,13 +5988,13 @@ int build_ht(cc_ctx* ctx, Group& g) {
     uint64_t size = 1024;
     while (size < (uint64_t)(2 * g.F)) size <<= 1;
     g.ht_mask = size - 1;
-    unsigned long long* key = GB(unsigned long long, "ht_key", (int64_t)size);
-    int32_t* val = GB(int32_t, "ht_val", (int64_t)size);
+    unsigned long long* key = GB(ht_key, (int64_t)size);
+    int32_t* val = GB(ht_val, (int64_t)size);
     HIPCHK(hipMemsetAsync(key, 0xff, sizeof(unsigned long long) * size, ctx->stream));
     if (g.F > 0) {
         ProfScope ps(ctx, "k_ht_insert");
         hipLaunchKernelGGL(k_ht_insert, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F,
-                           (const uint64_t*)g.buf["fam_hash"].p, key, val, g.ht_mask);
+                           g.ptr<B::fam_hash>(), key, val, g.ht_mask);
     }
     return 0;
 }
@@ -5908,23 +6010,22 @@ int upload_swap(cc_ctx* ctx, Group& g, int32_t* d_swap, const int32_t* bc_swap, 
 }
 
 PairView pair_view(Group& g) {
-    return PairView{(const int32_t*)g.buf["pr_rec1"].p, (const int32_t*)g.buf["pr_rec2"].p,
-                    (const int32_t*)g.buf["pr_region"].p, (const int32_t*)g.buf["region_run"].p, g.scoped,
-                    (const int4*)g.buf["pr_tag"].p};
+    return PairView{g.ptr<B::pr_rec1>(), g.ptr<B::pr_rec2>(), g.ptr<B::pr_region>(), g.ptr<B::region_run>(), g.scoped,
+                    g.ptr<B::pr_tag>()};
 }
 
 // the per-family tags of a grouping (k_fam_tags), built by the stages that join it (DCS, SC)
 int ensure_fam_tags(cc_ctx* ctx, Group& g) {
     if (g.fam_tags_built) return 0;   // built by the pass (k_fam_build) or by an earlier join
     int brc = 0;
-    TagKey* fam_tag = GB(TagKey, "fam_tag", g.F);
-    int32_t* fam_rec = GB(int32_t, "fam_rec", g.F);
+    TagKey* fam_tag = GB(fam_tag, g.F);
+    int32_t* fam_rec = GB(fam_rec, g.F);
     g.fam_tags_built = true;
     if (g.F > 0) {
         ProfScope ps(ctx, "k_fam_tags");
         hipLaunchKernelGGL(k_fam_tags, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F,
-                           (const int32_t*)g.buf["fam_first"].p, (const int32_t*)g.buf["fam_beg"].p,
-                           (const int32_t*)g.buf["mem_rec"].p, pair_view(g), ctx->tables[g.table], fam_tag, fam_rec);
+                           g.ptr<B::fam_first>(), g.ptr<B::fam_beg>(), g.ptr<B::mem_rec>(), pair_view(g),
+                           ctx->tables[g.table], fam_tag, fam_rec);
     }
     return 0;
 }
@@ -5933,18 +6034,18 @@ GroupView view_of(Group& g) {
     GroupView v;
     v.F = g.F;
     v.seed = g.seed;
-    v.ht_key = (const unsigned long long*)g.buf["ht_key"].p;
-    v.ht_val = (const int32_t*)g.buf["ht_val"].p;
+    v.ht_key = g.ptr<B::ht_key>();
+    v.ht_val = g.ptr<B::ht_val>();
     v.ht_mask = g.ht_mask;
-    v.fam_hash = (const uint64_t*)g.buf["fam_hash"].p;
-    v.fam_first = (const int32_t*)g.buf["fam_first"].p;
-    v.fam_beg = (const int32_t*)g.buf["fam_beg"].p;
-    v.fam_region = (const int32_t*)g.buf["fam_region"].p;
-    v.fam_o = (const int32_t*)g.buf["fam_o"].p;
-    v.fam_tag = (const TagKey*)g.buf["fam_tag"].p;
-    v.fam_rec = (const int32_t*)g.buf["fam_rec"].p;
-    v.mem_rec = (const int32_t*)g.buf["mem_rec"].p;
-    v.ent_f = (const int32_t*)g.buf["ent_f"].p;
+    v.fam_hash = g.ptr<B::fam_hash>();
+    v.fam_first = g.ptr<B::fam_first>();
+    v.fam_beg = g.ptr<B::fam_beg>();
+    v.fam_region = g.ptr<B::fam_region>();
+    v.fam_o = g.ptr<B::fam_o>();
+    v.fam_tag = g.ptr<B::fam_tag>();
+    v.fam_rec = g.ptr<B::fam_rec>();
+    v.mem_rec = g.ptr<B::mem_rec>();
+    v.ent_f = g.ptr<B::ent_f>();
     v.local = g.local_groups ? 1 : 0;
     v.use_ht = 0;
     v.fbkt = nullptr;
@@ -5960,7 +6061,7 @@ int build_fam_buckets(cc_ctx* ctx, Group& g, GroupView* v, bool* ok) {
     const DevTable& T = ctx->tables[g.table];
     if (!g.local_groups || !g.coord_sorted) return 0;   // the table's buckets were built by g's pass
     int brc = 0;
-    int32_t* fbkt = GB(int32_t, "fam_bkt", T.bkt_cap);
+    int32_t* fbkt = GB(fam_bkt, T.bkt_cap);
     {
         // the table's bucket geometry from each tid's extent (k_derive)
         ProfScope ps(ctx, "k_bucket_geom");
@@ -5968,14 +6069,24 @@ int build_fam_buckets(cc_ctx* ctx, Group& g, GroupView* v, bool* ok) {
                            T.tbase, T.geom);
     }
     hipLaunchKernelGGL(k_fam_bucket, dim3(nblk(g.F + 1)), dim3(256), 0, ctx->stream, g.F,
-                       (const TagKey*)g.buf["fam_tag"].p, T.tbase, T.ntid,
-                       T.geom, fbkt);
+                       g.ptr<B::fam_tag>(), T.tbase, T.ntid, T.geom, fbkt);
     v->fbkt = fbkt;
     v->tbase = T.tbase;
     v->ntid = T.ntid;
     v->geom = T.geom;
     *ok = true;
     return 0;
+}
+
+// the duplex vote of n pairs (mode 0: DCS, 1: singleton correction; ml: the tables' longest read)
+void duplex_vote(cc_ctx* ctx, int32_t mode, int64_t n, const int4* vpair, const DevTable& TA, const DevTable& TB,
+                 int32_t ml, int32_t qstride, uint8_t* cons_seq, uint8_t* cons_qual, int32_t* vmeta) {
+    if (n <= 0) return;
+    ProfScope ps(ctx, mode ? "k_duplex_vote_sc" : "k_duplex_vote_dcs");
+    const int32_t chunks = std::min(64, std::max(1, (ml + SV_POS - 1) / SV_POS));   // lanes per output
+    const int32_t fpw = 64 / chunks;
+    hipLaunchKernelGGL(k_duplex_vote_swar, dim3(nblk((n + fpw - 1) / fpw, 4)), dim3(256), 0, ctx->stream, n, mode, fpw,
+                       chunks, vpair, TA, TB, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
 }
 
 }  // namespace
@@ -6006,13 +6117,13 @@ int cc_destroy(cc_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     bgzf_free(ctx);
     for (auto& g : ctx->groups)
-        for (auto& b : g.second->buf)
-            if (b.second.p) (void)hipFree(b.second.p);
+        for (DevBuf& b : g.second->buf)
+            if (b.p) (void)hipFree(b.p);
     for (auto& t : ctx->table_allocs)
         for (void* p : t.second) (void)hipFree(p);
     if (ctx->scratch)
-        for (auto& b : ctx->scratch->buf)
-            if (b.second.p) (void)hipFree(b.second.p);
+        for (DevBuf& b : ctx->scratch->buf)
+            if (b.p) (void)hipFree(b.p);
     if (ctx->tmp.p) (void)hipFree(ctx->tmp.p);
     if (ctx->sort_buf.p) (void)hipFree(ctx->sort_buf.p);
     if (ctx->scan_st) (void)hipFree(ctx->scan_st);
@@ -6150,30 +6261,30 @@ int cc_commit(cc_ctx* ctx) {
     return 0;
 }
 
-// test hook: shifts one planned total of a group so that its next planned pass fails its check
-// (exercises the exact re-run and the deferred replay)
 // test hook: a group's pooled buffer grown to at least `bytes` and filled with `value` (stale slots a
 // planned pass may read past what its kernels wrote: the guards' test)
 int cc_debug_poison(cc_ctx* ctx, int32_t group_id, const char* name, int64_t bytes, int32_t value) {
     if (!ctx || !name || !ctx->groups.count(group_id) || bytes < 0) return CC_E_INVALID;
     Group& g = *ctx->groups[group_id];
-    if (!g.buf.count(name)) { ctx->err = std::string("no buffer named ") + name; return CC_E_INVALID; }
-    DevBuf& b = g.buf[name];
-    const size_t used = b.used;
+    const int id = name_id(BUF_IDS, name);
+    if (id < 0 || !g.buf[id].p) { ctx->err = std::string("no buffer named ") + name; return CC_E_INVALID; }
+    DevBuf& b = g.buf[id];
     int brc = 0;
-    uint8_t* p = gbuf<uint8_t>(ctx, g, name, std::max<int64_t>(bytes, (int64_t)b.bytes), &brc);
+    void* p = gbuf_bytes(ctx, g, (B)id, std::max((size_t)bytes, b.bytes), &brc);   // (what it holds stays in use)
     if (brc) return brc;
-    b.used = used;
     HIPCHK(hipMemsetAsync(p, value & 0xff, b.bytes, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
+// test hook: shifts one planned total of a group so that its next planned pass fails its check
+// (exercises the exact re-run and the deferred replay)
 int cc_debug_skew_plan(cc_ctx* ctx, int32_t group_id, const char* name, int64_t delta) {
     if (!ctx || !name || !ctx->groups.count(group_id)) return CC_E_INVALID;
     Group& g = *ctx->groups[group_id];
-    if (!g.plan.count(name)) { ctx->err = std::string("no planned total named ") + name; return CC_E_INVALID; }
-    g.plan[name] += delta;
+    const int id = name_id(PLAN_IDS, name);
+    if (id < 0 || !g.plan_set[id]) { ctx->err = std::string("no planned total named ") + name; return CC_E_INVALID; }
+    g.plan[id] += delta;
     return 0;
 }
 
@@ -6531,26 +6642,26 @@ int vote_families(cc_ctx* ctx, Group& g, const DevTable& T, int64_t NE, uint8_t*
                   int32_t* emit_fam, int2* emit_span, double cutoff, int64_t* NV_out) {
     int brc = 0;
     int64_t NV = 0;
-    RC(scan_total(ctx, g, needv, vxs, NE, &NV, "scan_vote"));
+    RC(scan_total(ctx, g, needv, vxs, NE, &NV, PT::scan_vote));
     g.NV = NV;
     g.Q = NE;
-    int32_t* vote_fam = GB(int32_t, "vote_fam", NV);
-    int4* vote_order = GB(int4, "vote_order", NV);
-    int32_t* emit_vslot = GB(int32_t, "emit_vslot", NE);
+    int32_t* vote_fam = GB(vote_fam, NV);
+    int4* vote_order = GB(vote_order, NV);
+    int32_t* emit_vslot = GB(emit_vslot, NE);
     const int32_t qstride = (int32_t)((T.max_len + 15) & ~15);
-    uint8_t* cons_seq = GB(uint8_t, "cons_seq", NV * (qstride / 2));
-    uint8_t* cons_qual = GB(uint8_t, "cons_qual", NV * qstride);
-    int32_t* vmeta = GB(int32_t, "vote_meta", 5 * NV);
+    uint8_t* cons_seq = GB(cons_seq, NV * (qstride / 2));
+    uint8_t* cons_qual = GB(cons_qual, NV * qstride);
+    int32_t* vmeta = GB(vote_meta, 5 * NV);
     // families the SWAR vote cannot take (more than VOTE_BIGN members, or every family when reads
     // are longer than 64 SWAR chunks) land on a device-counted list for the split vote
     // (k_big_items / k_big_partial / k_big_final); their chunk count is a planned total
     const int32_t chunks = (T.max_len + SV_POS - 1) / SV_POS;
     const int all_slow = (chunks >= 1 && chunks <= 64) ? 0 : 1;
-    int32_t* slow_list = GB(int32_t, "vote_slow_list", NV);
+    int32_t* slow_list = GB(vote_slow_list, NV);
     uint32_t* d_items = (uint32_t*)(ctx->d_err) + 13;
     int brc2 = 0;
-    uint32_t* d_nitems = plan_slot(ctx, g, "vote_items", &brc2);
-    uint32_t* d_slow = plan_slot(ctx, g, "vote_slow", &brc2);   // families handed to the split vote
+    uint32_t* d_nitems = plan_slot(ctx, g, PT::vote_items, &brc2);
+    uint32_t* d_slow = plan_slot(ctx, g, PT::vote_slow, &brc2);   // families handed to the split vote
     if (brc2) return brc2;
     {
         // the error word and the hand-over counts (nothing before k_vote_plan reports errors)
@@ -6563,16 +6674,16 @@ int vote_families(cc_ctx* ctx, Group& g, const DevTable& T, int64_t NE, uint8_t*
     if (NE > 0) {
         ProfScope ps(ctx, "k_vote_plan");
         hipLaunchKernelGGL(k_vote_plan, dim3(nblk(NE)), dim3(256), 0, ctx->stream, NE, g.R, NV, needv, vxs, emit_fam,
-                           (const int2*)emit_span, (const uint4*)g.buf["mem_meta"].p, (const int32_t*)g.buf["mem_rec"].p, T, vote_fam,
+                           (const int2*)emit_span, g.ptr<B::mem_meta>(), g.ptr<B::mem_rec>(), T, vote_fam,
                            vote_order, emit_vslot, vmeta, d_slow, slow_list, d_nitems, all_slow, ctx->d_err);
     }
     if (NV > 0) {
         int64_t NI = 0, NSL = 0;
-        RC(planned_total(ctx, g, "vote_items", d_nitems, &NI));
-        RC(planned_total(ctx, g, "vote_slow", d_slow, &NSL));
+        RC(planned_total(ctx, g, PT::vote_items, d_nitems, &NI));
+        RC(planned_total(ctx, g, PT::vote_slow, d_slow, &NSL));
         if (!all_slow) {
-            const bool fresh = !g.buf.count("cutoff_thr") || !g.buf["cutoff_thr"].p;
-            int32_t* thr = GB(int32_t, "cutoff_thr", VOTE_BIGN + 1);
+            const bool fresh = !g.ptr<B::cutoff_thr>();
+            int32_t* thr = GB(cutoff_thr, VOTE_BIGN + 1);
             if (fresh || g.thr_cutoff != cutoff) {   // the table depends on the cutoff alone
                 hipLaunchKernelGGL(k_cutoff_table, dim3(1), dim3(128), 0, ctx->stream, cutoff, thr);
                 g.thr_cutoff = cutoff;
@@ -6582,18 +6693,18 @@ int vote_families(cc_ctx* ctx, Group& g, const DevTable& T, int64_t NE, uint8_t*
             const int32_t uni_ok = (1.0 >= cutoff) ? 1 : 0;   // count == pass: 1.0 >= cutoff in double
             ProfScope ps(ctx, "k_sscs_vote_swar");
             hipLaunchKernelGGL(k_sscs_vote_swar, dim3(nblk(waves, 4)), dim3(256), 0, ctx->stream, NV, fpw, chunks,
-                               vote_order, (const uint4*)g.buf["mem_meta"].p, g.R, T, thr, uni_ok, qstride, cons_seq,
+                               vote_order, g.ptr<B::mem_meta>(), g.R, T, thr, uni_ok, qstride, cons_seq,
                                cons_qual, ctx->d_err);
         }
         const int64_t icap = NI > 0 ? NI : 1;
-        int32_t* big_item = GB(int32_t, "vote_big_item", NV);
-        int4* items = GB(int4, "vote_items", icap);
-        uint8_t* partial = GB(uint8_t, "vote_partial", icap * BIG_PL * (int64_t)qstride);
-        uint32_t* item_fl = GB(uint32_t, "vote_item_fl", icap);
+        int32_t* big_item = GB(vote_big_item, NV);
+        int4* items = GB(vote_items, icap);
+        uint8_t* partial = GB(vote_partial, icap * BIG_PL * (int64_t)qstride);
+        uint32_t* item_fl = GB(vote_item_fl, icap);
         if (NSL > 0) {
             ProfScope ps(ctx, "k_big_items");
             hipLaunchKernelGGL(k_big_items, dim3(64), dim3(256), 0, ctx->stream, d_slow, slow_list, vote_fam,
-                               (const int32_t*)g.buf["fam_beg"].p, (const int32_t*)g.buf["fam_end"].p, NI, d_items,
+                               g.ptr<B::fam_beg>(), g.ptr<B::fam_end>(), NI, d_items,
                                big_item, items, ctx->d_err);
         }
         if (NI > 0) {
@@ -6601,15 +6712,14 @@ int vote_families(cc_ctx* ctx, Group& g, const DevTable& T, int64_t NE, uint8_t*
             const int32_t bfpw = 64 / bch;
             ProfScope ps(ctx, "k_big_swar");
             hipLaunchKernelGGL(k_big_swar, dim3(nblk((NI + bfpw - 1) / bfpw, 4)), dim3(256), 0, ctx->stream, d_items, NI,
-                               bfpw, bch, items, (const uint4*)g.buf["mem_meta"].p, T, qstride, partial, item_fl,
+                               bfpw, bch, items, g.ptr<B::mem_meta>(), T, qstride, partial, item_fl,
                                ctx->d_err);
         }
         ProfScope ps(ctx, "k_big_final");
         if (NSL > 0)
         hipLaunchKernelGGL(k_big_final, dim3(CC_BF_GRID), dim3(64), 0, ctx->stream, d_slow, slow_list, big_item, NI,
-                           vote_fam, (const int32_t*)g.buf["fam_beg"].p, (const int32_t*)g.buf["fam_end"].p,
-                           (const int32_t*)g.buf["fam_n"].p, (const int32_t*)g.buf["mem_rec"].p,
-                           (const uint32_t*)g.buf["mem_valid"].p, (const uint4*)g.buf["mem_meta"].p, T, cutoff,
+                           vote_fam, g.ptr<B::fam_beg>(), g.ptr<B::fam_end>(), g.ptr<B::fam_n>(), g.ptr<B::mem_rec>(),
+                           g.ptr<B::mem_valid>(), g.ptr<B::mem_meta>(), T, cutoff,
                            qstride, partial, (const uint32_t*)item_fl, qstride, cons_seq, cons_qual, vmeta,
                            ctx->d_err);
     }
@@ -6703,21 +6813,21 @@ struct ReadBamPass {
 
 // The plan's slots, the long-pair check's form and size, and the pass's first fill set.
 int ReadBamPass::setup() {
-    d_srec = (int32_t*)g.buf["stream_rec"].p;
-    d_sreg = (int32_t*)g.buf["stream_region"].p;
-    d_run = (int32_t*)g.buf["region_run"].p;
-    d_nresid = plan_slot(ctx, g, "n_resid", &brc);
-    d_nbig = plan_slot(ctx, g, "n_big", &brc);
-    d_ndrop = plan_slot(ctx, g, "n_drop", &brc);
+    d_srec = g.ptr<B::stream_rec>();
+    d_sreg = g.ptr<B::stream_region>();
+    d_run = g.ptr<B::region_run>();
+    d_nresid = plan_slot(ctx, g, PT::n_resid, &brc);
+    d_nbig = plan_slot(ctx, g, PT::n_big, &brc);
+    d_ndrop = plan_slot(ctx, g, PT::n_drop, &brc);
     if (brc) return brc;
     g.members_built = false;
     // the long pairs' keys (k_pair_coord_tile, k_pair_resid): at least twice the long pairs of the last
     // exact pass (deep groups' pairs are long), an exact pass room for every pair; more long pairs
     // than fit send the pass to the sort path
-    n_long = plan_slot(ctx, g, "n_long", &brc);
+    n_long = plan_slot(ctx, g, PT::n_long, &brc);
     if (brc) return brc;
     {
-        const uint64_t want = has_plan(g, "n_long") ? (uint64_t)(2 * plan_or(g, "n_long", 0)) + (uint64_t)S / 16
+        const uint64_t want = has_plan(g, PT::n_long) ? (uint64_t)(2 * plan_or(g, PT::n_long, 0)) + (uint64_t)S / 16
                                                     : (uint64_t)S;
         while (lsize < want) lsize <<= 1;
     }
@@ -6726,48 +6836,48 @@ int ReadBamPass::setup() {
     // the long-pair table's scattered CAS; CC_LTAB_CAS=1 keeps the table
     // (CC_LP_MIN=k: from k planned long pairs; 0: every pass, exact ones too -- the tests' switch)
     lpart = coord_pair && !sw.ltab_cas &&
-            (sw.lp_min == 0 || (has_plan(g, "n_long") && has_plan(g, "scan_pairs") && plan_or(g, "n_long", 0) >= sw.lp_min));
-    if (coord_pair && !lpart) ltab = GB(unsigned long long, "pc_ltab", (int64_t)lsize);
+            (sw.lp_min == 0 || (has_plan(g, PT::n_long) && has_plan(g, PT::scan_pairs) && plan_or(g, PT::n_long, 0) >= sw.lp_min));
+    if (coord_pair && !lpart) ltab = GB(pc_ltab, (int64_t)lsize);
     if (lpart) {
         // found pairs: at most the pass's pairs (planned), at most half the stream entries (exact)
-        pcap = (uint32_t)std::min<int64_t>(plan_or(g, "scan_pairs", S / 2) + 4096, INT32_MAX);
-        pkeys = GB(uint64_t, "pc_pkeys", pcap);
-        pcount = plan_slot(ctx, g, "lp_found", &brc);   // (a counter: zeroed with the plan totals)
+        pcap = (uint32_t)std::min<int64_t>(plan_or(g, PT::scan_pairs, S / 2) + 4096, INT32_MAX);
+        pkeys = GB(pc_pkeys, pcap);
+        pcount = plan_slot(ctx, g, PT::lp_found, &brc);   // (a counter: zeroed with the plan totals)
         if (brc) return brc;
     }
     // the pass's zeroed words, one launch with the table preparation's
     RC(fill.add(ctx->d_err, 4, 0u));
     RC(fill.add(ctx->d_cnt, sizeof(unsigned long long) * CC_NUM_COUNTERS * CNT_STRIPES, 0u));
-    RC(fill.add(g.buf["plan_totals"].p, 4 * PLAN_SLOTS, 0u));
+    RC(fill.add(g.ptr<B::plan_totals>(), 4 * PLAN_SLOTS, 0u));
     // every striped count starts the pass at zero (k_stripe_total zeroes what it folds; a planned
     // pass's unfolded stripes are summed at its end, and a pass that ended early leaves them set)
-    if (g.buf.count("plan_stripes") && g.buf["plan_stripes"].p)
-        RC(fill.add(g.buf["plan_stripes"].p, sizeof(uint32_t) * PLAN_SLOTS * PSTRIPES * PSTRIDE, 0u));
+    if (g.ptr<B::plan_stripes>())
+        RC(fill.add(g.ptr<B::plan_stripes>(), sizeof(uint32_t) * PLAN_SLOTS * PSTRIPES * PSTRIDE, 0u));
     g.stripes_pending = false;
     if (ltab) RC(fill.add(ltab, sizeof(unsigned long long) * lsize, ~0u));
     // a planned pass knows its family count: the per-family drop counts are zeroed here too
-    const int64_t Fp = plan_or(g, "scan_fam", 0);
+    const int64_t Fp = plan_or(g, PT::scan_fam, 0);
     if (Fp > 0) {
-        int32_t* fd = GB(int32_t, "fam_drop", Fp);
+        int32_t* fd = GB(fam_drop, Fp);
         RC(fill.add(fd, sizeof(int32_t) * Fp, 0u));
         drop_zeroed = true;
     }
     // a planned pass knows the sizes of the tables it zeroes later (the read ends' creation and deep
     // flags, csn_pair_dict's table): they are zeroed by the pass's first fill too (two launches fewer)
-    if (has_plan(g, "scan_pairs") && has_plan(g, "scan_fam")) {
-        const int64_t Rp = 2 * plan_or(g, "scan_pairs", 0);
-        const bool deep_planned = !g.coord_sorted || Rp == 0 || has_plan(g, "n_big");
+    if (has_plan(g, PT::scan_pairs) && has_plan(g, PT::scan_fam)) {
+        const int64_t Rp = 2 * plan_or(g, PT::scan_pairs, 0);
+        const bool deep_planned = !g.coord_sorted || Rp == 0 || has_plan(g, PT::n_big);
         if (Rp > 0 && deep_planned) {
-            uint8_t* cf = GB(uint8_t, "cflag", (Rp + 15) & ~15LL);
+            uint8_t* cf = GB(cflag, (Rp + 15) & ~15LL);
             RC(fill.add(cf, ((size_t)Rp + 15) & ~(size_t)15, 0u));
             pre_ends = true;
         }
         if (Fp > 0 && deep_planned) {
-            const int64_t nd = g.coord_sorted && Rp > 0 ? plan_or(g, "n_big", 0) : 0;
+            const int64_t nd = g.coord_sorted && Rp > 0 ? plan_or(g, PT::n_big, 0) : 0;
             const bool tiles = g.coord_sorted && g.ident && Rp > 0;
             uint64_t size = 1024;
             while (size < (uint64_t)(tiles ? 2 * std::min(nd, Fp) : 2 * Fp)) size <<= 1;   // (csn_table_size)
-            unsigned long long* ht = GB(unsigned long long, "csn_ht_key", (int64_t)size);
+            unsigned long long* ht = GB(csn_ht_key, (int64_t)size);
             RC(fill.add(ht, sizeof(unsigned long long) * size, ~0u));
             pre_csn = true;
         }
@@ -6775,28 +6885,28 @@ int ReadBamPass::setup() {
     // a bed stream's keys and slots scattered to its records (k_scatter_stream) for the mate search;
     // records outside the stream keep the all-ones fill (key ~0, slot -1)
     if (coord_pair && !g.ident) {
-        rq = GB(uint64_t, "pc_rq", N);
-        spos = GB(int32_t, "pc_spos", N);
+        rq = GB(pc_rq, N);
+        spos = GB(pc_spos, N);
         RC(fill.add(rq, sizeof(uint64_t) * N, ~0u));
         RC(fill.add(spos, sizeof(int32_t) * N, ~0u));
     }
-    if (g.coord_sorted && N > 0) rec_e = GB(int32_t, "rec_e", N);
+    if (g.coord_sorted && N > 0) rec_e = GB(rec_e, N);
     return 0;
 }
 
 // ---- 0. the table's per-record cores (and position keys when sorted), part of every pass
 // ---- 1. filters + qname keys (consensus_helper.py:389-426)
 int ReadBamPass::filters() {
-    skey = GB(uint64_t, "skey", S);
-    sval = GB(uint32_t, "sval", S);
-    skey2 = GB(uint64_t, "skey2", S);
-    sval2 = GB(uint32_t, "sval2", S);
-    uint8_t* badflag = GB(uint8_t, "badflag", (S + 15) & ~15LL);   // byte flags (16-B padded for the scan)
-    mate_of = GB(int32_t, "mate_of", S);
-    pflag = GB(uint8_t, "pflag", (S + 15) & ~15LL);
+    skey = GB(skey, S);
+    sval = GB(sval, S);
+    skey2 = GB(skey2, S);
+    sval2 = GB(sval2, S);
+    uint8_t* badflag = GB(badflag, (S + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+    mate_of = GB(mate_of, S);
+    pflag = GB(pflag, (S + 15) & ~15LL);
     if (coord_pair) {
-        partner = GB(int32_t, "pc_partner", S);
-        claims = GB(int32_t, "pc_claims", S);
+        partner = GB(pc_partner, S);
+        claims = GB(pc_claims, S);
     }
     const ClassifyOut co{skey, coord_pair ? nullptr : sval, g.badread ? badflag : nullptr, mate_of,
                          g.ident ? nullptr : partner, claims, pflag};
@@ -6845,14 +6955,14 @@ int ReadBamPass::filters() {
 
 // ---- 2. pair_dict: mates by qname
 int ReadBamPass::pairing() {
-    d_nmulti = plan_slot(ctx, g, "n_multi", &brc);   // qnames seen more than twice (k_pair_mark)
+    d_nmulti = plan_slot(ctx, g, PT::n_multi, &brc);   // qnames seen more than twice (k_pair_mark)
     if (brc) return brc;
     if (!coord_pair) {
         RC(sort_pairs(ctx, skey, skey2, sval, sval2, S, "sort_qname"));
         return S > 0 ? pair_mark(S) : 0;
     }
     const uint64_t* rkey = T.rkey;   // (the table's position keys, k_derive)
-    uint8_t* resid = GB(uint8_t, "pc_resid", (S + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+    uint8_t* resid = GB(pc_resid, (S + 15) & ~15LL);   // byte flags (16-B padded for the scan)
     uint64_t* rk_app = nullptr;   // the residual keys in append order (k_pair_resid) and their count
     uint32_t* rv_app = nullptr;
     uint32_t* n_app = nullptr;
@@ -6869,15 +6979,15 @@ int ReadBamPass::pairing() {
         uint64_t dgsize = 64;
         if (NDG > 0) {
             while (dgsize < (uint64_t)(2 * NDG)) dgsize <<= 1;
-            gq = GB(uint64_t, "deep_gq", N);
-            gend = GB(int32_t, "deep_gend", N);
-            boff = GB(uint32_t, "deep_boff", N + 1);
+            gq = GB(deep_gq, N);
+            gend = GB(deep_gend, N);
+            boff = GB(deep_boff, N + 1);
             // the records' deep group ids key the deep ends' sort, which a planned pass whose deep
             // groups all ranked in place (k_deep_fam, no overflow) does not run
-            const bool ranked_plan = plan_or(g, "deep_ovf", 1) == 0 && !g.no_deep_fam && !sw.deep_sort;
-            if (!ranked_plan) deep_gid = GB(uint32_t, "deep_gid", N);
+            const bool ranked_plan = plan_or(g, PT::deep_ovf, 1) == 0 && !g.no_deep_fam && !sw.deep_sort;
+            if (!ranked_plan) deep_gid = GB(deep_gid, N);
             deep_q = true;
-            dgk = GB(unsigned long long, "deep_dgk", 2 * (int64_t)dgsize);
+            dgk = GB(deep_dgk, 2 * (int64_t)dgsize);
             RC(fill.add(dgk, sizeof(unsigned long long) * 2 * dgsize, 0xFFFFFFFEu));
             RC(fill.launch());
             ProfScope pq(ctx, "k_deep_qsort");
@@ -6902,21 +7012,21 @@ int ReadBamPass::pairing() {
         uint32_t* st = plan_stripes(ctx, g, d_nresid, &brc);
         if (brc) return brc;
         // the residual keys appended as they are flagged (the table pairing's input without the scan)
-        rk_app = GB(uint64_t, "pc_rk_app", S);
-        rv_app = GB(uint32_t, "pc_rv_app", S);
-        n_app = plan_slot(ctx, g, "resid_app", &brc);   // (zeroed with the plan totals; not checked)
+        rk_app = GB(pc_rk_app, S);
+        rv_app = GB(pc_rv_app, S);
+        n_app = plan_slot(ctx, g, PT::resid_app, &brc);   // (zeroed with the plan totals; not checked)
         if (brc) return brc;
         hipLaunchKernelGGL(k_pair_resid, dim3((unsigned)((S + PD_TILE - 1) / PD_TILE)), dim3(256), 0, ctx->stream, S,
                            skey, partner, claims, resid, st, ltab, lsize - 1, n_long, ctx->d_err, rk_app, rv_app, n_app);
         // a planned pass leaves the count striped: the end-of-pass check folds it (k_defer_pack)
-        if (has_plan(g, "n_resid")) g.stripes_pending = true;
+        if (has_plan(g, PT::n_resid)) g.stripes_pending = true;
         else hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, st, d_nresid);
     }
     if (lpart) {   // the partitioned check for a qname in two found pairs
-        uint32_t* hist = GB(uint32_t, "lp_hist", (int64_t)LP_BUCKETS * LP_NB);
-        uint32_t* off = GB(uint32_t, "lp_off", (int64_t)LP_BUCKETS * LP_NB);
-        uint64_t* bkeys = GB(uint64_t, "lp_bkeys", pcap);
-        uint32_t* lp_tot = plan_slot(ctx, g, "lp_total", &brc);   // (the scan's total; not checked)
+        uint32_t* hist = GB(lp_hist, (int64_t)LP_BUCKETS * LP_NB);
+        uint32_t* off = GB(lp_off, (int64_t)LP_BUCKETS * LP_NB);
+        uint64_t* bkeys = GB(lp_bkeys, pcap);
+        uint32_t* lp_tot = plan_slot(ctx, g, PT::lp_total, &brc);   // (the scan's total; not checked)
         if (brc) return brc;
         {
             ProfScope pl(ctx, "k_lp_check");
@@ -6932,9 +7042,9 @@ int ReadBamPass::pairing() {
                            (const uint32_t*)off, (const uint64_t*)bkeys, ctx->d_err);
     }
     int64_t NL = 0;   // the long pairs: the next planned pass sizes its table from them
-    RC(planned_total(ctx, g, "n_long", n_long, &NL));
+    RC(planned_total(ctx, g, PT::n_long, n_long, &NL));
     int64_t NR = 0;
-    RC(planned_total(ctx, g, "n_resid", d_nresid, &NR));
+    RC(planned_total(ctx, g, PT::n_resid, d_nresid, &NR));
     return NR > 0 ? pair_residual(NR, resid, rk_app, rv_app, n_app) : 0;
 }
 
@@ -6964,14 +7074,14 @@ int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_ap
     unsigned long long* rht = nullptr;
     unsigned long long* bloom = nullptr;
     uint32_t *hcnt = nullptr, *hmin = nullptr, *hmax = nullptr;
-    uint32_t* d_rmulti = plan_slot(ctx, g, "resid_multi", &brc);
+    uint32_t* d_rmulti = plan_slot(ctx, g, PT::resid_multi, &brc);
     if (brc) return brc;
     if (!many) {
-        rht = GB(unsigned long long, "pc_rht", (int64_t)hsize);
-        bloom = GB(unsigned long long, "pc_bloom", (int64_t)bsize);
-        hcnt = GB(uint32_t, "pc_hcnt", (int64_t)hsize);
-        hmin = GB(uint32_t, "pc_hmin", (int64_t)hsize);
-        hmax = GB(uint32_t, "pc_hmax", (int64_t)hsize);
+        rht = GB(pc_rht, (int64_t)hsize);
+        bloom = GB(pc_bloom, (int64_t)bsize);
+        hcnt = GB(pc_hcnt, (int64_t)hsize);
+        hmin = GB(pc_hmin, (int64_t)hsize);
+        hmax = GB(pc_hmax, (int64_t)hsize);
         RC(fill.add(rht, sizeof(unsigned long long) * hsize, ~0u));
         RC(fill.add(bloom, sizeof(unsigned long long) * bsize, 0u));
         RC(fill.add(hcnt, sizeof(uint32_t) * hsize, 0u));
@@ -6979,8 +7089,8 @@ int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_ap
         RC(fill.add(hmax, sizeof(uint32_t) * hsize, 0u));
         RC(fill.launch());
     }
-    uint64_t* rk = GB(uint64_t, "pc_rk", NR);
-    uint32_t* rv = GB(uint32_t, "pc_rv", NR);
+    uint64_t* rk = GB(pc_rk, NR);
+    uint32_t* rv = GB(pc_rv, NR);
     int64_t NR2 = 0;
     // the table from the appended keys (no scan); the sort path (many residual reads, or a key
     // seen three times or more) takes them compacted in stream order by the scan below
@@ -6991,7 +7101,7 @@ int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_ap
                            (const uint64_t*)rk_app, (const uint32_t*)rv_app, rht, hsize - 1, bloom, bsize - 1,
                            hcnt, hmin, hmax, d_rmulti, ctx->d_err);
     } else {
-        RC(scan_emit(ctx, g, resid, S, &NR2, "scan_resid",
+        RC(scan_emit(ctx, g, resid, S, &NR2, PT::scan_resid,
                      EmitResid{skey, rk, rv, NR, rht, hsize - 1, bloom, bsize - 1, ctx->d_err, hcnt, hmin, hmax,
                                d_rmulti}));
     }
@@ -7002,7 +7112,7 @@ int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_ap
                            ctx->d_err);
     }
     int64_t nmulti_r = 1;
-    if (!many) RC(planned_total(ctx, g, "resid_multi", d_rmulti, &nmulti_r));
+    if (!many) RC(planned_total(ctx, g, PT::resid_multi, d_rmulti, &nmulti_r));
     if (!many && nmulti_r == 0 && !sw.resid_sort) {
         // every residual key seen once or twice: paired through the table, no sort
         ProfScope ps(ctx, "k_pair_mark");
@@ -7014,7 +7124,7 @@ int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_ap
         return 0;
     }
     if (appended)   // (stream order for the sort: the scan's compaction, without the table again)
-        RC(scan_emit(ctx, g, resid, S, &NR2, "scan_resid",
+        RC(scan_emit(ctx, g, resid, S, &NR2, PT::scan_resid,
                      EmitResid{skey, rk, rv, NR, nullptr, 0, nullptr, 0, ctx->d_err, nullptr, nullptr, nullptr,
                                nullptr}));
     RC(sort_pairs(ctx, rk, skey2, rv, sval2, NR, "sort_qname_resid"));
@@ -7028,38 +7138,38 @@ int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_ap
 
 // ---- 3. completed pairs (records, region, read ends) and their unique_tag / sscs_qname hashes
 int ReadBamPass::pair_keys() {
-    pr_rec1 = GB(int32_t, "pr_rec1", S);   // capacity; sized P below
-    int32_t* pr_rec2 = GB(int32_t, "pr_rec2", S);
-    pr_region = GB(int32_t, "pr_region", S);
-    RC(scan_emit(ctx, g, pflag, S, &P, "scan_pairs",
+    pr_rec1 = GB(pr_rec1, S);   // capacity; sized P below
+    int32_t* pr_rec2 = GB(pr_rec2, S);
+    pr_region = GB(pr_region, S);
+    RC(scan_emit(ctx, g, pflag, S, &P, PT::scan_pairs,
                  EmitPairs{mate_of, g.ident, d_srec, d_sreg, pr_rec1, pr_rec2, pr_region, rec_e}));
     g.P = P;
-    pr_rec1 = GB(int32_t, "pr_rec1", P);
-    pr_rec2 = GB(int32_t, "pr_rec2", P);
-    pr_region = GB(int32_t, "pr_region", P);
-    int4* pr_tag = GB(int4, "pr_tag", P);
+    pr_rec1 = GB(pr_rec1, P);
+    pr_rec2 = GB(pr_rec2, P);
+    pr_region = GB(pr_region, P);
+    int4* pr_tag = GB(pr_tag, P);
     PV = PairView{pr_rec1, pr_rec2, pr_region, d_run, g.scoped, pr_tag};
     R = 2 * P;
     g.R = R;
-    chash = GB(uint64_t, "chash", P);
+    chash = GB(chash, P);
     // rtag (sorted tables whose read ends lie mostly in small position groups) per record its tag fields
     // but the coordinates, for k_group_rank's compare in LDS.  Where most ends sit in deep groups (deep
     // panels: C4) the mates lie in other groups, the scattered copy costs more than the ranking's few
     // gathers by pair (C4 k_pair_keys +0.33 ms), and the ranking's compare takes those gathers.  The
     // deep ends' count: the plan of a repeated pass, else whether the table has deep groups at all.
     if (g.coord_sorted) {
-        rhash = GB(uint64_t, "rec_thash", N);
-        const auto nb = g.plan.find("n_big");   // (of the last pass, exact or planned)
-        const bool by_rec = nb != g.plan.end() ? nb->second * 8 <= R : NDG == 0;
-        if (by_rec && !sw.gr_by_pair) rtag = GB(int4, "rec_tag", N);
+        rhash = GB(rec_thash, N);
+        // (n_big of the last pass, exact or planned)
+        const bool by_rec = g.plan_set[(int)PT::n_big] ? g.plan[(int)PT::n_big] * 8 <= R : NDG == 0;
+        if (by_rec && !sw.gr_by_pair) rtag = GB(rec_tag, N);
     } else {
-        thash = GB(uint64_t, "thash", R);
-        tval = GB(uint32_t, "tval", R);   // the tag sort's values
+        thash = GB(thash, R);
+        tval = GB(tval, R);   // the tag sort's values
     }
-    rs_key = GB(uint64_t, "rs_key", R);
-    rs_val = GB(uint32_t, "rs_val", R);
-    cflag = GB(uint8_t, "cflag", (R + 15) & ~15LL);
-    if (g.coord_sorted && R > 0) bigE = GB(uint32_t, "grp_bigE", R);   // (every entry written by k_pair_keys)
+    rs_key = GB(rs_key, R);
+    rs_val = GB(rs_val, R);
+    cflag = GB(cflag, (R + 15) & ~15LL);
+    if (g.coord_sorted && R > 0) bigE = GB(grp_bigE, R);   // (every entry written by k_pair_keys)
     if (R > 0 && !pre_ends) RC(fill.add(cflag, ((size_t)R + 15) & ~(size_t)15, 0u));
     RC(fill.launch());
     if (P > 0) {
@@ -7073,15 +7183,15 @@ int ReadBamPass::pair_keys() {
 // ---- 4. read_dict / tag_dict: group read ends by exact tag
 int ReadBamPass::grouping() {
     g.local_groups = false;
-    mem_rec = GB(int32_t, "mem_rec", R);
-    segf = GB(uint8_t, "segf", (R + 15) & ~15LL);
-    mem_valid = GB(uint32_t, "mem_valid", R);
-    if (members) mem_meta = GB(uint4, "mem_meta", R);
+    mem_rec = GB(mem_rec, R);
+    segf = GB(segf, (R + 15) & ~15LL);
+    mem_valid = GB(mem_valid, R);
+    if (members) mem_meta = GB(mem_meta, R);
     if (!g.coord_sorted) return sort_pairs(ctx, thash, rs_key, tval, rs_val, R, "sort_tags");
     if (R <= 0) return 0;
     const uint64_t* rkey = (const uint64_t*)T.rkey;   // the table's position keys (k_derive)
     const int64_t NT = (N + GT - 1) / GT;
-    uint32_t* tsmall = GB(uint32_t, "grp_tile_small", NT);
+    uint32_t* tsmall = GB(grp_tile_small, NT);
     {
         ProfScope ps(ctx, "k_group");
         uint32_t* st = plan_stripes(ctx, g, d_nbig, &brc);
@@ -7091,12 +7201,12 @@ int ReadBamPass::grouping() {
         else
             hipLaunchKernelGGL(k_group_count, dim3(nblk(N, GT * GC_TILES)), dim3(GT), 0, ctx->stream, N, (const int32_t*)rec_e,
                                (const uint8_t*)T.rdeep, tsmall, st);
-        if (has_plan(g, "n_big")) g.stripes_pending = true;
+        if (has_plan(g, PT::n_big)) g.stripes_pending = true;
         else hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, st, d_nbig);
     }
     int64_t NS = 0, NB = 0;
-    uint32_t* tpre = GB(uint32_t, "grp_tile_pre", NT);
-    RC(scan_total(ctx, g, tsmall, tpre, NT, &NS, "scan_small"));
+    uint32_t* tpre = GB(grp_tile_pre, NT);
+    RC(scan_total(ctx, g, tsmall, tpre, NT, &NS, PT::scan_small));
     if (NS > 0) {
         ProfScope ps(ctx, "k_group_rank");
         const auto k_rank = rtag ? k_group_rank<true> : k_group_rank<false>;   // (the compare's fields by record, or by pair)
@@ -7105,7 +7215,7 @@ int ReadBamPass::grouping() {
                            (const int4*)rtag, T, segf, mem_valid, mem_meta, ctx->d_err);
     }
     n_known = NS;
-    RC(planned_total(ctx, g, "n_big", d_nbig, &NB));
+    RC(planned_total(ctx, g, PT::n_big, d_nbig, &NB));
     n_deep = NB;
     if (NS + NB != R) {
         // inconsistent coordinate pairs (a record paired twice) lose read ends here; the qname
@@ -7119,10 +7229,10 @@ int ReadBamPass::grouping() {
     g.local_groups = NB == 0;
     if (NB > 0 && deep_q && NDG > 0 && !g.no_deep_fam && !sw.deep_sort) RC(rank_deep_in_place(NS, NB));
     if (NB > 0 && !deep_ranked) {
-        uint32_t* bx = GB(uint32_t, "grp_bx", R);
-        RC(scan_total(ctx, g, bigE, bx, R, &NB, "scan_bigE"));
-        uint64_t* bkey = GB(uint64_t, "grp_bkey", NB);
-        uint32_t* bval = GB(uint32_t, "grp_bval", NB);
+        uint32_t* bx = GB(grp_bx, R);
+        RC(scan_total(ctx, g, bigE, bx, R, &NB, PT::scan_bigE));
+        uint64_t* bkey = GB(grp_bkey, NB);
+        uint32_t* bval = GB(grp_bval, NB);
         // group-major keys when this pass's coordinate search numbered the deep groups
         // (k_deep_qsort), else the full tag hash.  (The same keys with the hash bits in 16..63 and
         // a sort over bits 16..63 split c4 families on the GPU: rocPRIM's begin_bit is not used.)
@@ -7143,14 +7253,14 @@ int ReadBamPass::grouping() {
 // k_deep_emit, k_deep_sortfam): no global sort.  deep_ranked stays false when a group overflowed
 // k_deep_fam's table (the sorted path ranks them then).
 int ReadBamPass::rank_deep_in_place(int64_t NS, int64_t NB) {
-    uint32_t* gcnt = GB(uint32_t, "deep_gcnt", NDG);
-    uint32_t* goff = GB(uint32_t, "deep_goff", NDG);
-    uint32_t* se = GB(uint32_t, "deep_se", N);
-    int4* items = GB(int4, "deep_items", NB);
-    int4* bigit = GB(int4, "deep_big", NB / 65 + 1);
-    uint32_t* d_ovf = plan_slot(ctx, g, "deep_ovf", &brc);
-    uint32_t* d_items = plan_slot(ctx, g, "deep_items", &brc);
-    uint32_t* d_big = plan_slot(ctx, g, "deep_big", &brc);
+    uint32_t* gcnt = GB(deep_gcnt, NDG);
+    uint32_t* goff = GB(deep_goff, NDG);
+    uint32_t* se = GB(deep_se, N);
+    int4* items = GB(deep_items, NB);
+    int4* bigit = GB(deep_big, NB / 65 + 1);
+    uint32_t* d_ovf = plan_slot(ctx, g, PT::deep_ovf, &brc);
+    uint32_t* d_items = plan_slot(ctx, g, PT::deep_items, &brc);
+    uint32_t* d_big = plan_slot(ctx, g, PT::deep_big, &brc);
     if (brc) return brc;
     const DeepOut dout{R, rs_val, mem_rec, segf, mem_valid, mem_meta};
     {
@@ -7160,7 +7270,7 @@ int ReadBamPass::rank_deep_in_place(int64_t NS, int64_t NB) {
                            gcnt);
     }
     int64_t nd = 0;
-    RC(scan_total(ctx, g, gcnt, goff, NDG, &nd, "scan_deep"));
+    RC(scan_total(ctx, g, gcnt, goff, NDG, &nd, PT::scan_deep));
     if (nd != NB) {
         ctx->err = "deep position groups: end count differs from the group partition";
         return CC_E_INVALID;
@@ -7173,7 +7283,7 @@ int ReadBamPass::rank_deep_in_place(int64_t NS, int64_t NB) {
                            d_big, d_ovf, ctx->d_err);
     }
     int64_t novf = 0;
-    RC(planned_total(ctx, g, "deep_ovf", d_ovf, &novf));
+    RC(planned_total(ctx, g, PT::deep_ovf, d_ovf, &novf));
     if (novf != 0) return 0;
     {
         ProfScope ps(ctx, "k_deep_emit");
@@ -7182,7 +7292,7 @@ int ReadBamPass::rank_deep_in_place(int64_t NS, int64_t NB) {
                            T, dout, ctx->d_err);
     }
     int64_t nbig = 0;
-    RC(planned_total(ctx, g, "deep_big", d_big, &nbig));
+    RC(planned_total(ctx, g, PT::deep_big, d_big, &nbig));
     if (nbig > 0) {
         ProfScope ps(ctx, "k_deep_sortfam");
         hipLaunchKernelGGL(k_deep_sortfam, dim3((unsigned)std::min<int64_t>(nbig, CC_DS_GRID)), dim3(DF_ST), 0,
@@ -7210,28 +7320,28 @@ int ReadBamPass::families() {
     }
     // family starts compacted in the scan's store phase (EmitFamStarts): fam_beg and fam_drop take
     // their capacity first (F is the scan's total)
-    const int64_t Fcap = plan_or(g, "scan_fam", R);
-    fam_beg = GB(int32_t, "fam_beg", Fcap);
-    int32_t* fam_drop = GB(int32_t, "fam_drop", Fcap);
+    const int64_t Fcap = plan_or(g, PT::scan_fam, R);
+    fam_beg = GB(fam_beg, Fcap);
+    int32_t* fam_drop = GB(fam_drop, Fcap);
     if (Fcap > 0 && !drop_zeroed) HIPCHK(hipMemsetAsync(fam_drop, 0, sizeof(int32_t) * Fcap, ctx->stream));
-    RC(scan_emit(ctx, g, segf, R, &F, "scan_fam", EmitFamStarts{mem_valid, fam_beg, fam_drop, d_ndrop, Fcap, ctx->d_err}));
+    RC(scan_emit(ctx, g, segf, R, &F, PT::scan_fam, EmitFamStarts{mem_valid, fam_beg, fam_drop, d_ndrop, Fcap, ctx->d_err}));
     g.F = F;
-    fam_beg = GB(int32_t, "fam_beg", F);
-    fam_end = GB(int32_t, "fam_end", F);
-    int32_t* fam_n = GB(int32_t, "fam_n", F);
-    fam_first = GB(int32_t, "fam_first", F);
-    fam_region = GB(int32_t, "fam_region", F);
-    uint64_t* fam_hash = GB(uint64_t, "fam_hash", F);
-    int32_t* cfam = GB(int32_t, "cfam", R);
-    fam_o = GB(int32_t, "fam_o", F);
+    fam_beg = GB(fam_beg, F);
+    fam_end = GB(fam_end, F);
+    int32_t* fam_n = GB(fam_n, F);
+    fam_first = GB(fam_first, F);
+    fam_region = GB(fam_region, F);
+    uint64_t* fam_hash = GB(fam_hash, F);
+    int32_t* cfam = GB(cfam, R);
+    fam_o = GB(fam_o, F);
     // the passes whose stage joins the grouping (DCS, SC: no bad-read list) build the family tags
     // here; the SSCS pass never joins
     g.fam_tags_built = false;
     TagKey* fam_tag = nullptr;
     int32_t* fam_rec = nullptr;
     if (!g.badread) {
-        fam_tag = GB(TagKey, "fam_tag", F);
-        fam_rec = GB(int32_t, "fam_rec", F);
+        fam_tag = GB(fam_tag, F);
+        fam_rec = GB(fam_rec, F);
     }
     if (F > 0) {
         ProfScope ps(ctx, "k_fam_build");
@@ -7242,22 +7352,22 @@ int ReadBamPass::families() {
                            cfam, fam_o, PV, T, fam_tag, fam_rec);
     }
     g.fam_tags_built = fam_tag != nullptr;
-    RC(planned_total(ctx, g, "n_drop", d_ndrop, &V));
+    RC(planned_total(ctx, g, PT::n_drop, d_ndrop, &V));
     V = R - V;   // members kept
     // ---- 5. tag_dict insertion order (family creation order)
     int64_t F2 = 0;
-    fam_by_k = GB(int32_t, "fam_by_k", F);
-    int32_t* fam_k = GB(int32_t, "fam_k", F);
-    pair_by_k = GB(int32_t, "pair_by_k", F);
-    int32_t* fsz = GB(int32_t, "fam_sizes_by_creation", F);
-    return scan_emit(ctx, g, cflag, R, &F2, "scan_creation", EmitCreation{cfam, fam_n, fam_by_k, fam_k, pair_by_k, fsz});
+    fam_by_k = GB(fam_by_k, F);
+    int32_t* fam_k = GB(fam_k, F);
+    pair_by_k = GB(pair_by_k, F);
+    int32_t* fsz = GB(fam_sizes_by_creation, F);
+    return scan_emit(ctx, g, cflag, R, &F2, PT::scan_creation, EmitCreation{cfam, fam_n, fam_by_k, fam_k, pair_by_k, fsz});
 }
 
 // ---- 6. csn_pair_dict: group creation events by consensus tag
 int ReadBamPass::csn() {
-    uint32_t* csegf = GB(uint32_t, "csegf", F);
-    uint8_t* emark = GB(uint8_t, "emark", (F + 15) & ~15LL);
-    int32_t* e1k = GB(int32_t, "e1k", F);
+    uint32_t* csegf = GB(csegf, F);
+    uint8_t* emark = GB(emark, (F + 15) & ~15LL);
+    int32_t* e1k = GB(e1k, F);
     bool fast_ok = false;
     if (F > 0) {
         // with the stream in table order (each record once) the global table takes the entries whose
@@ -7267,8 +7377,8 @@ int ReadBamPass::csn() {
         const bool tiles = g.coord_sorted && g.ident && bigE;
         uint64_t size = 1024;
         while (size < (uint64_t)(tiles ? 2 * std::min<int64_t>(n_deep, F) : 2 * F)) size <<= 1;
-        unsigned long long* cht = GB(unsigned long long, "csn_ht_key", (int64_t)size);
-        uint32_t* shared = plan_slot(ctx, g, "csn_shared", &brc);   // (zeroed with the plan totals)
+        unsigned long long* cht = GB(csn_ht_key, (int64_t)size);
+        uint32_t* shared = plan_slot(ctx, g, PT::csn_shared, &brc);   // (zeroed with the plan totals)
         if (brc) return brc;
         if (!pre_csn) RC(fill.add(cht, sizeof(unsigned long long) * size, ~0u));
         RC(fill.launch());
@@ -7279,14 +7389,14 @@ int ReadBamPass::csn() {
                                cht, size - 1, emark, e1k, shared);
         }
         int64_t sh = 0;
-        RC(planned_total(ctx, g, "csn_shared", shared, &sh));
+        RC(planned_total(ctx, g, PT::csn_shared, shared, &sh));
         fast_ok = sh == 0;
     }
     if (F > 0 && !fast_ok) {
-        uint64_t* ekey = GB(uint64_t, "ekey", F);
-        uint32_t* eval = GB(uint32_t, "eval", F);
-        uint64_t* es_key = GB(uint64_t, "es_key", F);
-        uint32_t* es_val = GB(uint32_t, "es_val", F);
+        uint64_t* ekey = GB(ekey, F);
+        uint32_t* eval = GB(eval, F);
+        uint64_t* es_key = GB(es_key, F);
+        uint32_t* es_val = GB(es_val, F);
         hipLaunchKernelGGL(k_csn_keys, dim3(nblk(F)), dim3(256), 0, ctx->stream, F, fam_by_k, fam_first, chash, ekey, eval);
         RC(sort_pairs(ctx, ekey, es_key, eval, es_val, F, "sort_csn"));
         HIPCHK(hipMemsetAsync(emark, 0, std::max<int64_t>(F, 1), ctx->stream));
@@ -7297,14 +7407,14 @@ int ReadBamPass::csn() {
                            fam_region, g.badread ? 0 : 1, emark, e1k, ctx->d_cnt);
     }
     g.csn_fast = fast_ok;
-    int32_t* ent_f = GB(int32_t, "ent_f", 2 * F);   // capacity; sized E below
-    int32_t* ent_pair = GB(int32_t, "ent_pair", F);
-    uint8_t* has2 = GB(uint8_t, "has2", (F + 15) & ~15LL);   // byte flags (16-B padded for the scan)
-    RC(scan_emit(ctx, g, emark, F, &E, "scan_entries",
+    int32_t* ent_f = GB(ent_f, 2 * F);   // capacity; sized E below
+    int32_t* ent_pair = GB(ent_pair, F);
+    uint8_t* has2 = GB(has2, (F + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+    RC(scan_emit(ctx, g, emark, F, &E, PT::scan_entries,
                  EmitEntries{e1k, fam_by_k, pair_by_k, ent_f, ent_pair, fam_o, has2}));
     g.E = E;
-    ent_f = GB(int32_t, "ent_f", 2 * E);
-    ent_pair = GB(int32_t, "ent_pair", E);
+    ent_f = GB(ent_f, 2 * E);
+    ent_pair = GB(ent_pair, E);
     // (the SSCS loop's deletions; DCS and SC delete by their decisions: k_deleted_late in their calls).
     // Any stream of several regions: a pair completed in a later region can join a family emitted
     // earlier (a record fetched by two overlapping regions, or a pair whose ends sit in two regions
@@ -7346,14 +7456,14 @@ int read_bam_pass(cc_ctx* ctx, int32_t gid) {
 int read_bam_run(cc_ctx* ctx, int32_t gid) {
     Group& g = *ctx->groups[gid];
     auto run = [&]() {
-        int rc = run_planned(ctx, g, "read_bam", [&] { return read_bam_pass(ctx, gid); });
+        int rc = run_planned(ctx, g, ST_READ_BAM, [&] { return read_bam_pass(ctx, gid); });
         for (int k = 0; k < 2 && (rc == CC_E_NEEDSORT || rc == CC_E_DEEPSORT); ++k) {
             // a qname seen more than twice: pair_dict's stream order needs the sort path; a long deep
             // family out of end order: the deep ends take the sorted path (both from now on)
             if (rc == CC_E_NEEDSORT) g.force_sort = true;
             else g.no_deep_fam = true;
-            g.planned["read_bam"] = false;
-            rc = run_planned(ctx, g, "read_bam", [&] { return read_bam_pass(ctx, gid); });
+            g.planned[ST_READ_BAM] = false;
+            rc = run_planned(ctx, g, ST_READ_BAM, [&] { return read_bam_pass(ctx, gid); });
         }
         return rc;
     };
@@ -7363,7 +7473,7 @@ int read_bam_run(cc_ctx* ctx, int32_t gid) {
         // passes hash the qname bytes from now on, and this one runs again (the caller's seed
         // retries then apply to the full hash as before)
         ctx->full_qhash.insert(g.table);
-        g.planned["read_bam"] = false;
+        g.planned[ST_READ_BAM] = false;
         rc = run();
     }
     return rc;
@@ -7404,9 +7514,9 @@ int cc_read_bam(cc_ctx* ctx, int32_t table_id, int64_t S, const int32_t* stream_
         if (g.overlap) g.coord_sorted = 0;
     }
     int brc = 0;
-    int32_t* d_srec = GB(int32_t, "stream_rec", S);
-    int32_t* d_sreg = GB(int32_t, "stream_region", S);
-    int32_t* d_run = GB(int32_t, "region_run", std::max<int32_t>(n_regions, 1));
+    int32_t* d_srec = GB(stream_rec, S);
+    int32_t* d_sreg = GB(stream_region, S);
+    int32_t* d_run = GB(region_run, std::max<int32_t>(n_regions, 1));
     if (S > 0) {
         HIPCHK(hipMemcpyAsync(d_srec, stream_rec, sizeof(int32_t) * S, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(d_sreg, stream_region, sizeof(int32_t) * S, hipMemcpyHostToDevice, ctx->stream));
@@ -7441,8 +7551,8 @@ int cc_group_free(cc_ctx* ctx, int32_t group_id) {
             if (d.g != gp) keep.push_back(d);
         ctx->deferred.swap(keep);
     }
-    for (auto& b : ctx->groups[group_id]->buf)
-        if (b.second.p) (void)hipFree(b.second.p);
+    for (DevBuf& b : ctx->groups[group_id]->buf)
+        if (b.p) (void)hipFree(b.p);
     ctx->groups.erase(group_id);
     return 0;
 }
@@ -7458,45 +7568,44 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
         RC(flush_derive(ctx, g.table));
         const DevTable& T = ctx->tables[g.table];
         int brc = 0;
-        const int64_t E = g.E, F = g.F, R = g.R;
+        const int64_t E = g.E, R = g.R;
         if (!g.members_built) {   // a pass that did not write the member records (see read_bam_pass)
-            uint4* mm = GB(uint4, "mem_meta", R);
+            uint4* mm = GB(mem_meta, R);
             if (R > 0)
                 hipLaunchKernelGGL(k_mem_meta, dim3(nblk(R)), dim3(256), 0, ctx->stream, R,
-                                   (const int32_t*)g.buf["mem_rec"].p, (const uint32_t*)g.buf["mem_valid"].p, T, mm);
+                                   g.ptr<B::mem_rec>(), g.ptr<B::mem_valid>(), T, mm);
             g.members_built = true;
         }
-        const uint8_t* has2 = (const uint8_t*)g.buf["has2"].p;   // by the pass's entry scan (EmitEntries)
-        uint32_t* hx = GB(uint32_t, "hx", (E + 3) & ~3LL);
+        const uint8_t* has2 = g.ptr<B::has2>();   // by the pass's entry scan (EmitEntries)
+        uint32_t* hx = GB(hx, (E + 3) & ~3LL);
         int64_t E2 = 0;
-        RC(scan_total(ctx, g, has2, hx, E, &E2, "scan_emit"));
+        RC(scan_total(ctx, g, has2, hx, E, &E2, PT::scan_emit));
         if (!g.csn_fast && g.n_regions > 1 && E > 0) {
             // entries may complete in a later region than they start (the exact csn path only: the
             // fast path's entries are one pair's events): emission slots by (completing region, entry)
-            uint64_t* ek = GB(uint64_t, "emit_ekey", E);
-            uint64_t* sk = GB(uint64_t, "emit_skey", E);
-            uint32_t* ev = GB(uint32_t, "emit_eval", E);
-            uint32_t* sv = GB(uint32_t, "emit_sval", E);
+            uint64_t* ek = GB(emit_ekey, E);
+            uint64_t* sk = GB(emit_skey, E);
+            uint32_t* ev = GB(emit_eval, E);
+            uint32_t* sv = GB(emit_sval, E);
             hipLaunchKernelGGL(k_emit_keys, dim3(nblk(E)), dim3(256), 0, ctx->stream, E, has2,
-                               (const int32_t*)g.buf["ent_f"].p, (const int32_t*)g.buf["fam_region"].p, ek, ev);
+                               g.ptr<B::ent_f>(), g.ptr<B::fam_region>(), ek, ev);
             RC(sort_pairs(ctx, ek, sk, ev, sv, E, "sort_emit"));
             if (E2 > 0)
                 hipLaunchKernelGGL(k_emit_rank, dim3(nblk(E2)), dim3(256), 0, ctx->stream, E2, (const uint32_t*)sv, hx);
         }
         const int64_t NE = 2 * E2;
-        int32_t* emit_fam = GB(int32_t, "emit_fam", NE);
-        int32_t* emit_n = GB(int32_t, "emit_n", NE);
-        int32_t* emit_rec = GB(int32_t, "emit_rec", NE);
-        int32_t* emit_ckey = GB(int32_t, "emit_ckey", 9 * E2);   // per emitted entry (both its records)
-        uint8_t* needv = GB(uint8_t, "needv", (NE + 15) & ~15LL);   // byte flags (16-B padded for the scan)
-        int2* emit_span = GB(int2, "emit_span", NE);
-        uint32_t* vxs = GB(uint32_t, "vxs", (NE + 3) & ~3LL);
+        int32_t* emit_fam = GB(emit_fam, NE);
+        int32_t* emit_n = GB(emit_n, NE);
+        int32_t* emit_rec = GB(emit_rec, NE);
+        int32_t* emit_ckey = GB(emit_ckey, 9 * E2);   // per emitted entry (both its records)
+        uint8_t* needv = GB(needv, (NE + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+        int2* emit_span = GB(emit_span, NE);
+        uint32_t* vxs = GB(vxs, (NE + 3) & ~3LL);
         if (E > 0) {
             ProfScope ps(ctx, "k_sscs_emit");
-            hipLaunchKernelGGL(k_sscs_emit, dim3(nblk(E)), dim3(256), 0, ctx->stream, E, (const int32_t*)g.buf["ent_f"].p,
-                               (const int32_t*)g.buf["ent_pair"].p, has2, hx, (const int32_t*)g.buf["fam_n"].p,
-                               (const int32_t*)g.buf["fam_beg"].p, (const int32_t*)g.buf["fam_end"].p,
-                               (const int32_t*)g.buf["mem_rec"].p, emit_fam, emit_n, emit_rec, needv, emit_span,
+            hipLaunchKernelGGL(k_sscs_emit, dim3(nblk(E)), dim3(256), 0, ctx->stream, E, g.ptr<B::ent_f>(),
+                               g.ptr<B::ent_pair>(), has2, hx, g.ptr<B::fam_n>(), g.ptr<B::fam_beg>(),
+                               g.ptr<B::fam_end>(), g.ptr<B::mem_rec>(), emit_fam, emit_n, emit_rec, needv, emit_span,
                                pair_view(g), T, emit_ckey);
         }
         int64_t NV = 0;
@@ -7504,15 +7613,13 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
         // badReads list + read_families sizes (host formats the text)
         const int64_t S = g.S;
         int64_t NB = 0;
-        int32_t* bad_rec = GB(int32_t, "bad_rec", S);   // capacity; sized NB below
+        int32_t* bad_rec = GB(bad_rec, S);   // capacity; sized NB below
         // the flagged entries are counted by read_bam (its counters are on the host): none, no scan
         if (g.counters[CC_CNT_BAD_LISTED] > 0)
-            RC(scan_emit(ctx, g, (const uint8_t*)g.buf["badflag"].p, S, &NB, "scan_bad",
-                         EmitGather{(const int32_t*)g.buf["stream_rec"].p, bad_rec}));
-        bad_rec = GB(int32_t, "bad_rec", NB);
+            RC(scan_emit(ctx, g, g.ptr<B::badflag>(), S, &NB, PT::scan_bad,
+                         EmitGather{g.ptr<B::stream_rec>(), bad_rec}));
+        bad_rec = GB(bad_rec, NB);
         // (fam_sizes_by_creation: written by the pass's creation scan, EmitCreation)
-        (void)F;
-        (void)R;
         uint32_t bits = 0;
         bool plan_ok = true;
         RC(finish_pass(ctx, g, &bits, false, &plan_ok));
@@ -7520,7 +7627,7 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
         if (n_out) *n_out = NE;
         return err_code(ctx, bits);
     };
-    return run_planned(ctx, g, "sscs", pass);
+    return run_planned(ctx, g, ST_SSCS, pass);
 }
 
 int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, int32_t n_bc, int64_t* n_out) {
@@ -7535,12 +7642,12 @@ int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, i
         const int64_t Q = 2 * g.E;
         g.Q = Q;
         HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
-        int32_t* d_swap = GB(int32_t, "bc_swap", std::max(n_bc, 1));
+        int32_t* d_swap = GB(bc_swap, std::max(n_bc, 1));
         RC(upload_swap(ctx, g, d_swap, bc_swap, n_bc));
-        int32_t* dec = GB(int32_t, "dec", Q);
-        int32_t* t_rec = GB(int32_t, "t_rec", Q);
-        int32_t* p_rec = GB(int32_t, "p_rec", Q);
-        uint8_t* fl_dcs = GB(uint8_t, "fl_dcs", (Q + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+        int32_t* dec = GB(dec, Q);
+        int32_t* t_rec = GB(t_rec, Q);
+        int32_t* p_rec = GB(p_rec, Q);
+        uint8_t* fl_dcs = GB(fl_dcs, (Q + 15) & ~15LL);   // byte flags (16-B padded for the scan)
         if (!g.local_groups) RC(build_ht(ctx, g));   // duplex partners are found among position-group neighbours
         RC(ensure_fam_tags(ctx, g));
         GroupView G = view_of(g);
@@ -7555,28 +7662,22 @@ int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, i
                                    p_rec, fl_dcs, ctx->d_err);
         }
         if (g.n_regions > 1 && g.F > 0) {   // tags deleted at a region's end, then completed again later
-            int32_t* fdel = GB(int32_t, "fam_del", g.F);
+            int32_t* fdel = GB(fam_del, g.F);
             hipLaunchKernelGGL(k_dcs_deleted, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F,
-                               (const int32_t*)g.buf["fam_o"].p, (const int32_t*)g.buf["fam_region"].p, Q,
+                               g.ptr<B::fam_o>(), g.ptr<B::fam_region>(), Q,
                                (const int32_t*)dec, fdel);
             RC(deleted_late(ctx, g, fdel));
         }
         int64_t NV = 0;
-        int32_t* vslot = GB(int32_t, "vslot", Q);
-        int4* vpair = GB(int4, "vpair", Q);   // capacity; sized NV below
-        RC(scan_emit(ctx, g, (const uint8_t*)fl_dcs, Q, &NV, "scan_dcs", EmitVotePairs{t_rec, p_rec, dec, vslot, vpair}));
+        int32_t* vslot = GB(vslot, Q);
+        int4* vpair = GB(vpair, Q);   // capacity; sized NV below
+        RC(scan_emit(ctx, g, (const uint8_t*)fl_dcs, Q, &NV, PT::scan_dcs, EmitVotePairs{t_rec, p_rec, dec, vslot, vpair}));
         g.NV = NV;
         const int32_t qstride = (int32_t)((T.max_len + 15) & ~15);
-        uint8_t* cons_seq = GB(uint8_t, "cons_seq", NV * (qstride / 2));
-        uint8_t* cons_qual = GB(uint8_t, "cons_qual", NV * qstride);
-        int32_t* vmeta = GB(int32_t, "vote_meta", 5 * NV);
-        if (NV > 0) {
-            ProfScope ps(ctx, "k_duplex_vote_dcs");
-            const int32_t chunks = std::min(64, std::max(1, (T.max_len + SV_POS - 1) / SV_POS));   // lanes per output
-            const int32_t fpw = 64 / chunks;
-            hipLaunchKernelGGL(k_duplex_vote_swar, dim3(nblk((NV + fpw - 1) / fpw, 4)), dim3(256), 0, ctx->stream, NV, 0,
-                               fpw, chunks, (const int4*)vpair, T, T, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
-        }
+        uint8_t* cons_seq = GB(cons_seq, NV * (qstride / 2));
+        uint8_t* cons_qual = GB(cons_qual, NV * qstride);
+        int32_t* vmeta = GB(vote_meta, 5 * NV);
+        duplex_vote(ctx, 0, NV, vpair, T, T, T.max_len, qstride, cons_seq, cons_qual, vmeta);
         uint32_t bits = 0;
         bool plan_ok = true;
         RC(finish_pass(ctx, g, &bits, false, &plan_ok));
@@ -7584,7 +7685,7 @@ int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, i
         if (n_out) *n_out = Q;
         return err_code(ctx, bits);
     };
-    return run_planned(ctx, g, "dcs", pass);
+    return run_planned(ctx, g, ST_DCS, pass);
 }
 
 int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const int32_t* bc_swap, int32_t n_bc,
@@ -7604,12 +7705,12 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
         const int64_t Q = 2 * g.E;
         g.Q = Q;
         HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
-        int32_t* d_swap = GB(int32_t, "bc_swap", std::max(n_bc, 1));
+        int32_t* d_swap = GB(bc_swap, std::max(n_bc, 1));
         RC(upload_swap(ctx, g, d_swap, bc_swap, n_bc));
-        int32_t* dec = GB(int32_t, "dec", Q);
-        int32_t* t_rec = GB(int32_t, "t_rec", Q);
-        int32_t* p_rec = GB(int32_t, "p_rec", Q);
-        uint8_t* fl = GB(uint8_t, "fl_corr", (Q + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+        int32_t* dec = GB(dec, Q);
+        int32_t* t_rec = GB(t_rec, Q);
+        int32_t* p_rec = GB(p_rec, Q);
+        uint8_t* fl = GB(fl_corr, (Q + 15) & ~15LL);   // byte flags (16-B padded for the scan)
         // tables with deep position groups (targeted panels, C4: hundreds of families at a position)
         // look families up by hash instead of walking a position group's neighbours / bucket
         const bool deep_g = TA.n_deep > 0, deep_s = TB.n_deep > 0;
@@ -7631,16 +7732,16 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
         int32_t* gdel = nullptr;
         int32_t* sdel = nullptr;
         if (ov) {   // (0x7f7f7f7f: never deleted)
-            gdel = GB(int32_t, "fam_del", g.F);
+            gdel = GB(fam_del, g.F);
             HIPCHK(hipMemsetAsync(gdel, 0x7f, sizeof(int32_t) * g.F, ctx->stream));
-            sdel = gbuf<int32_t>(ctx, s, "fam_del", std::max<int64_t>(s.F, 1), &brc);   // the SSCS side's own
+            sdel = gbuf<B::fam_del>(ctx, s, std::max<int64_t>(s.F, 1), &brc);   // the SSCS side's own
             if (brc) return brc;
             HIPCHK(hipMemsetAsync(sdel, 0x7f, sizeof(int32_t) * std::max<int64_t>(s.F, 1), ctx->stream));
         }
         if (Q > 0) {
             ProfScope ps(ctx, "k_sc_decide");
             hipLaunchKernelGGL(k_sc_decide, dim3(nblk(Q)), dim3(256), 0, ctx->stream, Q, G, SV,
-                               (const int32_t*)g.buf["region_run"].p, d_swap, n_bc, dec, t_rec, p_rec, fl, gdel, sdel,
+                               g.ptr<B::region_run>(), d_swap, n_bc, dec, t_rec, p_rec, fl, gdel, sdel,
                                ctx->d_err);
         }
         if (ov) {
@@ -7648,27 +7749,21 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
             if (s.F > 0) RC(deleted_late(ctx, s, sdel));
         }
         int64_t NV = 0;
-        int32_t* vslot = GB(int32_t, "vslot", Q);
-        int4* vpair = GB(int4, "vpair", Q);   // capacity; sized NV below
-        RC(scan_emit(ctx, g, (const uint8_t*)fl, Q, &NV, "scan_sc", EmitVotePairs{t_rec, p_rec, dec, vslot, vpair}));
+        int32_t* vslot = GB(vslot, Q);
+        int4* vpair = GB(vpair, Q);   // capacity; sized NV below
+        RC(scan_emit(ctx, g, (const uint8_t*)fl, Q, &NV, PT::scan_sc, EmitVotePairs{t_rec, p_rec, dec, vslot, vpair}));
         g.NV = NV;
         const int32_t ml = std::max(TA.max_len, TB.max_len);
         const int32_t qstride = (int32_t)((ml + 15) & ~15);
-        uint8_t* cons_seq = GB(uint8_t, "cons_seq", NV * (qstride / 2));
-        uint8_t* cons_qual = GB(uint8_t, "cons_qual", NV * qstride);
-        int32_t* vmeta = GB(int32_t, "vote_meta", 5 * NV);
-        if (NV > 0) {
-            ProfScope ps(ctx, "k_duplex_vote_sc");
-            const int32_t chunks = std::min(64, std::max(1, (ml + SV_POS - 1) / SV_POS));   // lanes per output
-            const int32_t fpw = 64 / chunks;
-            hipLaunchKernelGGL(k_duplex_vote_swar, dim3(nblk((NV + fpw - 1) / fpw, 4)), dim3(256), 0, ctx->stream, NV, 1,
-                               fpw, chunks, (const int4*)vpair, TA, TB, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
-        }
+        uint8_t* cons_seq = GB(cons_seq, NV * (qstride / 2));
+        uint8_t* cons_qual = GB(cons_qual, NV * qstride);
+        int32_t* vmeta = GB(vote_meta, 5 * NV);
+        duplex_vote(ctx, 1, NV, vpair, TA, TB, ml, qstride, cons_seq, cons_qual, vmeta);
         // names: consensus tag of the singleton entry + ':1' (singleton_correction.py:286)
-        int32_t* q_pair = GB(int32_t, "q_pair", Q);
-        int32_t* q_ckey = GB(int32_t, "q_ckey", 9 * Q);
+        int32_t* q_pair = GB(q_pair, Q);
+        int32_t* q_ckey = GB(q_ckey, 9 * Q);
         if (Q > 0) {
-            hipLaunchKernelGGL(k_q_pairs, dim3(nblk(Q)), dim3(256), 0, ctx->stream, Q, (const int32_t*)g.buf["ent_pair"].p,
+            hipLaunchKernelGGL(k_q_pairs, dim3(nblk(Q)), dim3(256), 0, ctx->stream, Q, g.ptr<B::ent_pair>(),
                                q_pair);
             hipLaunchKernelGGL(k_ckey_out, dim3(nblk(Q)), dim3(256), 0, ctx->stream, Q, q_pair, pair_view(g),
                                ctx->tables[g.table], q_ckey);
@@ -7680,22 +7775,23 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
         if (n_out) *n_out = Q;
         return err_code(ctx, bits);
     };
-    return run_planned(ctx, g, "sc", pass);
+    return run_planned(ctx, g, ST_SC, pass);
 }
 
 int64_t cc_fetch(cc_ctx* ctx, int32_t group_id, const char* name, void* dst, int64_t cap) {
     if (!ctx || !ctx->groups.count(group_id) || !name) return CC_E_INVALID;
     Group& g = *ctx->groups[group_id];
-    auto it = g.buf.find(name);
-    if (it == g.buf.end()) {
+    const int id = name_id(BUF_IDS, name);
+    if (id < 0 || !g.buf[id].p) {   // (a buffer this group has never allocated: no such array)
         ctx->err = std::string("no result array named ") + name;
         return CC_E_INVALID;
     }
-    int64_t bytes = (int64_t)it->second.used;
+    const DevBuf& b = g.buf[id];
+    int64_t bytes = (int64_t)b.used;
     if (!dst) return bytes;
     int64_t nb = std::min(bytes, cap);
     if (nb > 0) {
-        HIPCHK(hipMemcpyAsync(dst, it->second.p, (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(dst, b.p, (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     return nb;
@@ -7774,16 +7870,16 @@ int cc_sscs_vote(cc_ctx* ctx, int32_t table_id, const int32_t* member_index, con
         if (member_index[j] < 0 || member_index[j] >= T.n) { ctx->err = "member index outside the table"; return CC_E_INVALID; }
     Group& g = scratch_group(ctx, table_id);
     int brc = 0;
-    int32_t* mem_rec = GB(int32_t, "mem_rec", R);
-    uint32_t* mem_valid = GB(uint32_t, "mem_valid", R);
-    uint4* mem_meta = GB(uint4, "mem_meta", R);
-    int32_t* d_beg = GB(int32_t, "fam_beg", nfam);
-    int32_t* d_end = GB(int32_t, "fam_end", nfam);
-    int32_t* d_n = GB(int32_t, "fam_n", nfam);
-    int32_t* d_fam = GB(int32_t, "emit_fam", nfam);
-    int2* d_span = GB(int2, "emit_span", nfam);
-    uint8_t* needv = GB(uint8_t, "needv", (nfam + 15) & ~15LL);
-    uint32_t* vxs = GB(uint32_t, "vxs", nfam);
+    int32_t* mem_rec = GB(mem_rec, R);
+    uint32_t* mem_valid = GB(mem_valid, R);
+    uint4* mem_meta = GB(mem_meta, R);
+    int32_t* d_beg = GB(fam_beg, nfam);
+    int32_t* d_end = GB(fam_end, nfam);
+    int32_t* d_n = GB(fam_n, nfam);
+    int32_t* d_fam = GB(emit_fam, nfam);
+    int2* d_span = GB(emit_span, nfam);
+    uint8_t* needv = GB(needv, (nfam + 15) & ~15LL);
+    uint32_t* vxs = GB(vxs, nfam);
     if (R > 0) HIPCHK(hipMemcpyAsync(mem_rec, member_index, sizeof(int32_t) * R, hipMemcpyHostToDevice, ctx->stream));
     if (nfam > 0) {
         HIPCHK(hipMemcpyAsync(d_beg, beg.data(), sizeof(int32_t) * nfam, hipMemcpyHostToDevice, ctx->stream));
@@ -7811,10 +7907,10 @@ int cc_sscs_vote(cc_ctx* ctx, int32_t table_id, const int32_t* member_index, con
     if (bits) return err_code(ctx, bits);
     // every family voted and the vote slots are 0..nfam-1 in family order (needv all set)
     const int64_t qstride = (T.max_len + 15) & ~15;
-    RC(copy_rows(ctx, out_qual, out_stride, g.buf["cons_qual"].p, qstride, T.max_len, NV));
-    RC(copy_rows(ctx, out_seq, out_stride / 2, g.buf["cons_seq"].p, qstride / 2, (T.max_len + 1) / 2, NV));
+    RC(copy_rows(ctx, out_qual, out_stride, g.ptr<B::cons_qual>(), qstride, T.max_len, NV));
+    RC(copy_rows(ctx, out_seq, out_stride / 2, g.ptr<B::cons_seq>(), qstride / 2, (T.max_len + 1) / 2, NV));
     if (NV > 0)
-        HIPCHK(hipMemcpyAsync(out_meta, g.buf["vote_meta"].p, sizeof(int32_t) * 5 * NV, hipMemcpyDeviceToHost,
+        HIPCHK(hipMemcpyAsync(out_meta, g.ptr<B::vote_meta>(), sizeof(int32_t) * 5 * NV, hipMemcpyDeviceToHost,
                               ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -7842,11 +7938,11 @@ int cc_pair_vote(cc_ctx* ctx, int32_t mode, int32_t table_a, int32_t table_b, co
         }
     Group& g = scratch_group(ctx, table_a);
     int brc = 0;
-    int4* vpair = GB(int4, "vpair", n);
+    int4* vpair = GB(vpair, n);
     const int32_t qstride = (int32_t)((ml + 15) & ~15);
-    uint8_t* cons_seq = GB(uint8_t, "cons_seq", n * (qstride / 2));
-    uint8_t* cons_qual = GB(uint8_t, "cons_qual", n * qstride);
-    int32_t* vmeta = GB(int32_t, "vote_meta", 5 * n);
+    uint8_t* cons_seq = GB(cons_seq, n * (qstride / 2));
+    uint8_t* cons_qual = GB(cons_qual, n * qstride);
+    int32_t* vmeta = GB(vote_meta, 5 * n);
     if (n > 0) {
         // {read1, read2, decision 0 (read2 in table_b), entry}
         std::vector<int4> vp((size_t)n);
@@ -7861,13 +7957,7 @@ int cc_pair_vote(cc_ctx* ctx, int32_t mode, int32_t table_a, int32_t table_b, co
     }
     RC(function_prep(ctx, TA));
     if (table_b != table_a) RC(function_prep(ctx, TB));
-    if (n > 0) {
-        ProfScope ps(ctx, mode ? "k_duplex_vote_sc" : "k_duplex_vote_dcs");
-        const int32_t chunks = std::min(64, std::max(1, (ml + SV_POS - 1) / SV_POS));
-        const int32_t fpw = 64 / chunks;
-        hipLaunchKernelGGL(k_duplex_vote_swar, dim3(nblk((n + fpw - 1) / fpw, 4)), dim3(256), 0, ctx->stream, n, mode,
-                           fpw, chunks, (const int4*)vpair, TA, TB, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
-    }
+    duplex_vote(ctx, mode, n, vpair, TA, TB, ml, qstride, cons_seq, cons_qual, vmeta);
     uint32_t bits = 0;
     RC(read_err(ctx, &bits));
     if (bits) return err_code(ctx, bits);
@@ -8076,20 +8166,24 @@ __global__ __launch_bounds__(64) void k_join_serial(int64_t n, int64_t m, int mo
     }
 }
 
-int upload_keys(cc_ctx* ctx, Group& g, const char* name, const void* keys, int64_t n, int kw, uint32_t** out) {
+template <B id>
+int upload_keys(cc_ctx* ctx, Group& g, const void* keys, int64_t n, int kw, uint32_t** out) {
     int brc = 0;
-    uint32_t* d = GB(uint32_t, name, n * kw);
+    uint32_t* d = gbuf<id>(ctx, g, n * kw, &brc);
+    if (brc) return brc;
     if (n > 0) HIPCHK(hipMemcpyAsync(d, keys, sizeof(uint32_t) * kw * n, hipMemcpyHostToDevice, ctx->stream));
     *out = d;
     return 0;
 }
 
 // an empty table of at least twice n slots; returns its mask
-int key_table(cc_ctx* ctx, Group& g, const char* name, int64_t n, int32_t** out, uint64_t* mask) {
+template <B id>
+int key_table(cc_ctx* ctx, Group& g, int64_t n, int32_t** out, uint64_t* mask) {
     int brc = 0;
     uint64_t size = 1024;
     while (size < (uint64_t)(2 * n)) size <<= 1;
-    int32_t* t = GB(int32_t, name, (int64_t)size);
+    int32_t* t = gbuf<id>(ctx, g, (int64_t)size, &brc);
+    if (brc) return brc;
     HIPCHK(hipMemsetAsync(t, 0xff, sizeof(int32_t) * size, ctx->stream));
     *out = t;
     *mask = size - 1;
@@ -8126,21 +8220,21 @@ int cc_group(cc_ctx* ctx, int64_t n, const void* keys, int32_t key_bytes, int32_
     Group& g = scratch_group(ctx, -1);
     int brc = 0;
     uint32_t* dk = nullptr;
-    RC(upload_keys(ctx, g, "grp_keys", keys, n, kw, &dk));
+    RC(upload_keys<B::grp_keys>(ctx, g, keys, n, kw, &dk));
     int32_t* tab = nullptr;
     uint64_t mask = 0;
-    RC(key_table(ctx, g, "grp_tab", n, &tab, &mask));
-    int32_t* slot_of = GB(int32_t, "grp_slot_of", n);
-    int32_t* slot_first = GB(int32_t, "grp_slot_first", (int64_t)mask + 1);
-    int32_t* slot_cnt = GB(int32_t, "grp_slot_cnt", (int64_t)mask + 1);
-    uint32_t* start = GB(uint32_t, "grp_start", (n + 3) & ~3LL);
-    uint32_t* fx = GB(uint32_t, "grp_fx", (n + 3) & ~3LL);
-    uint32_t* fam_size = GB(uint32_t, "grp_fsize", (n + 3) & ~3LL);
-    uint32_t* fam_off = GB(uint32_t, "grp_foff", (n + 3) & ~3LL);
-    uint64_t* fkey = GB(uint64_t, "grp_fkey", n);
-    uint32_t* fval = GB(uint32_t, "grp_fval", n);
-    uint64_t* skey = GB(uint64_t, "grp_skey", n);
-    uint32_t* sval = GB(uint32_t, "grp_sval", n);
+    RC(key_table<B::grp_tab>(ctx, g, n, &tab, &mask));
+    int32_t* slot_of = GB(grp_slot_of, n);
+    int32_t* slot_first = GB(grp_slot_first, (int64_t)mask + 1);
+    int32_t* slot_cnt = GB(grp_slot_cnt, (int64_t)mask + 1);
+    uint32_t* start = GB(grp_start, (n + 3) & ~3LL);
+    uint32_t* fx = GB(grp_fx, (n + 3) & ~3LL);
+    uint32_t* fam_size = GB(grp_fsize, (n + 3) & ~3LL);
+    uint32_t* fam_off = GB(grp_foff, (n + 3) & ~3LL);
+    uint64_t* fkey = GB(grp_fkey, n);
+    uint32_t* fval = GB(grp_fval, n);
+    uint64_t* skey = GB(grp_skey, n);
+    uint32_t* sval = GB(grp_sval, n);
     {
         Fills fill(ctx);
         RC(fill.add(slot_first, sizeof(int32_t) * (mask + 1), 0x7fffffffu));
@@ -8154,11 +8248,11 @@ int cc_group(cc_ctx* ctx, int64_t n, const void* keys, int32_t key_bytes, int32_
     hipLaunchKernelGGL(k_group_starts, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const int32_t*)slot_of,
                        (const int32_t*)slot_first, start);
     int64_t F = 0;
-    RC(scan_total(ctx, g, start, fx, n, &F, "grp_scan_fam"));
+    RC(scan_total(ctx, g, start, fx, n, &F, PT::grp_scan_fam));
     hipLaunchKernelGGL(k_group_fams, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const int32_t*)slot_of,
                        (const int32_t*)slot_first, (const int32_t*)slot_cnt, (const uint32_t*)fx, fam_size, fkey, fval);
     int64_t tot = 0;
-    RC(scan_total(ctx, g, fam_size, fam_off, F, &tot, "grp_scan_off"));
+    RC(scan_total(ctx, g, fam_size, fam_off, F, &tot, PT::grp_scan_off));
     // members in input order inside their family: a stable sort by family number (radix sorts are
     // stable; the values enter in input order)
     unsigned bits = 1;
@@ -8209,23 +8303,23 @@ int cc_duplex_join(cc_ctx* ctx, int32_t mode, int64_t n, const void* keys, const
     Group& g = scratch_group(ctx, table_a);
     int brc = 0;
     uint32_t *dk = nullptr, *dp = nullptr, *dx = nullptr;
-    RC(upload_keys(ctx, g, "join_keys", keys, n, kw, &dk));
-    RC(upload_keys(ctx, g, "join_pkeys", partner_keys, n, kw, &dp));
-    if (mx > 0) RC(upload_keys(ctx, g, "join_xkeys", x_keys, mx, kw, &dx));
+    RC(upload_keys<B::join_keys>(ctx, g, keys, n, kw, &dk));
+    RC(upload_keys<B::join_pkeys>(ctx, g, partner_keys, n, kw, &dp));
+    if (mx > 0) RC(upload_keys<B::join_xkeys>(ctx, g, x_keys, mx, kw, &dx));
     int32_t *tab = nullptr, *xtab = nullptr;
     uint64_t mask = 0, xmask = 0;
-    RC(key_table(ctx, g, "join_tab", n, &tab, &mask));
-    if (mx > 0) RC(key_table(ctx, g, "join_xtab", mx, &xtab, &xmask));
-    int32_t* p = GB(int32_t, "join_p", n);
-    int32_t* xs = GB(int32_t, "join_xs", n);
-    int32_t* xfirst = GB(int32_t, "join_xfirst", std::max<int64_t>(mx, 1));
-    int32_t* indeg = GB(int32_t, "join_indeg", n);
-    int32_t* dec = GB(int32_t, "join_dec", n);
-    int32_t* part = GB(int32_t, "join_part", n);
-    uint32_t* flags = GB(uint32_t, "join_flags", 4);   // [0] duplicate key, [1] serial needed
-    uint8_t* used = GB(uint8_t, "join_used", n);
-    uint8_t* gone = GB(uint8_t, "join_gone", n);
-    uint8_t* xgone = GB(uint8_t, "join_xgone", std::max<int64_t>(mx, 1));
+    RC(key_table<B::join_tab>(ctx, g, n, &tab, &mask));
+    if (mx > 0) RC(key_table<B::join_xtab>(ctx, g, mx, &xtab, &xmask));
+    int32_t* p = GB(join_p, n);
+    int32_t* xs = GB(join_xs, n);
+    int32_t* xfirst = GB(join_xfirst, std::max<int64_t>(mx, 1));
+    int32_t* indeg = GB(join_indeg, n);
+    int32_t* dec = GB(join_dec, n);
+    int32_t* part = GB(join_part, n);
+    uint32_t* flags = GB(join_flags, 4);   // [0] duplicate key, [1] serial needed
+    uint8_t* used = GB(join_used, n);
+    uint8_t* gone = GB(join_gone, n);
+    uint8_t* xgone = GB(join_xgone, std::max<int64_t>(mx, 1));
     {
         Fills fill(ctx);
         RC(fill.add(xs, sizeof(int32_t) * n, ~0u));
@@ -8287,10 +8381,10 @@ int cc_duplex_join(cc_ctx* ctx, int32_t mode, int64_t n, const void* keys, const
     const DevTable TX = (mode == 1 && m > 0) ? ctx->tables[table_x] : TA;
     const int32_t ml = std::max(TA.max_len, TX.max_len);
     const int32_t qstride = (int32_t)((ml + 15) & ~15);
-    int4* vpair = GB(int4, "vpair", nv);
-    uint8_t* cons_seq = GB(uint8_t, "cons_seq", nv * (qstride / 2));
-    uint8_t* cons_qual = GB(uint8_t, "cons_qual", nv * qstride);
-    int32_t* vmeta = GB(int32_t, "vote_meta", 5 * nv);
+    int4* vpair = GB(vpair, nv);
+    uint8_t* cons_seq = GB(cons_seq, nv * (qstride / 2));
+    uint8_t* cons_qual = GB(cons_qual, nv * qstride);
+    int32_t* vmeta = GB(vote_meta, 5 * nv);
     std::vector<int4> vp((size_t)nv);
     for (int64_t k = 0; k < nv; ++k) vp[k] = make_int4(ta[k], pb[k], dv[k], (int32_t)k);
     HIPCHK(hipMemcpyAsync(vpair, vp.data(), sizeof(int4) * nv, hipMemcpyHostToDevice, ctx->stream));
@@ -8527,20 +8621,20 @@ int cc_extract_barcodes(cc_ctx* ctx, int64_t n, const uint8_t* h1, const uint8_t
     const int nh = P.list ? P.nlist : 5 * P.plen;
     Group& g = scratch_group(ctx, -1);
     int brc = 0;
-    uint8_t* d1 = GB(uint8_t, "eb_h1", n * EB_W);
-    uint8_t* d2 = GB(uint8_t, "eb_h2", n * EB_W);
-    int32_t* dl1 = GB(int32_t, "eb_l1", n);
-    int32_t* dl2 = GB(int32_t, "eb_l2", n);
-    uint8_t* dst = GB(uint8_t, "eb_status", n);
-    char* dbc = GB(char, "eb_bc", n * EB_BC);
-    int32_t* dc1 = GB(int32_t, "eb_cut1", n);
-    int32_t* dc2 = GB(int32_t, "eb_cut2", n);
-    uint32_t* db1 = GB(uint32_t, "eb_bad1", n);
-    uint32_t* db2 = GB(uint32_t, "eb_bad2", n);
-    unsigned long long* dcnt = GB(unsigned long long, "eb_counts", 4);
-    unsigned long long* dh = GB(unsigned long long, "eb_hist", 2 * std::max(nh, 1));
-    unsigned long long* tkey = GB(unsigned long long, "eb_tkey", EB_SLOTS);
-    int32_t* tval = GB(int32_t, "eb_tval", EB_SLOTS);
+    uint8_t* d1 = GB(eb_h1, n * EB_W);
+    uint8_t* d2 = GB(eb_h2, n * EB_W);
+    int32_t* dl1 = GB(eb_l1, n);
+    int32_t* dl2 = GB(eb_l2, n);
+    uint8_t* dst = GB(eb_status, n);
+    char* dbc = GB(eb_bc, n * EB_BC);
+    int32_t* dc1 = GB(eb_cut1, n);
+    int32_t* dc2 = GB(eb_cut2, n);
+    uint32_t* db1 = GB(eb_bad1, n);
+    uint32_t* db2 = GB(eb_bad2, n);
+    unsigned long long* dcnt = GB(eb_counts, 4);
+    unsigned long long* dh = GB(eb_hist, 2 * std::max(nh, 1));
+    unsigned long long* tkey = GB(eb_tkey, EB_SLOTS);
+    int32_t* tval = GB(eb_tval, EB_SLOTS);
     if (n > 0) {
         HIPCHK(hipMemcpyAsync(d1, h1, (size_t)n * EB_W, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(d2, h2, (size_t)n * EB_W, hipMemcpyHostToDevice, ctx->stream));
@@ -8711,7 +8805,7 @@ int cc_reduce_stats(cc_ctx* ctx, cc_comm* comm, int64_t* counters, int32_t n_cou
     int brc = 0;
     if (!ctx->scratch) ctx->scratch.reset(new Group());
     Group& g = *ctx->scratch;
-    int64_t* d = GB(int64_t, "reduce_buf", ntot);
+    int64_t* d = GB(reduce_buf, ntot);
     std::vector<int64_t> h((size_t)ntot);
     std::copy(counters, counters + n_counters, h.begin());
     if (fam_len) {
@@ -8748,7 +8842,7 @@ int cc_allreduce_max(cc_ctx* ctx, cc_comm* comm, int64_t* v, int32_t n) {
     int brc = 0;
     if (!ctx->scratch) ctx->scratch.reset(new Group());
     Group& g = *ctx->scratch;
-    int64_t* d = GB(int64_t, "reduce_max", n);
+    int64_t* d = GB(reduce_max, n);
     HIPCHK(hipMemcpyAsync(d, v, sizeof(int64_t) * n, hipMemcpyHostToDevice, ctx->stream));
     const int rc = r->allreduce(d, d, (size_t)n, NCCL_INT64, NCCL_MAX, comm->comm, ctx->stream);
     if (rc) {
