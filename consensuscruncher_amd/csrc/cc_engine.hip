@@ -6577,6 +6577,8 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
 
 }  // extern "C"
 
+#include "table_unpack.hip.inc"
+
 namespace {
 // Per-pass table preparation (timed with the pass): the member records; on a coordinate-sorted table
 // also the position keys, the read-end map and the bucket geometry.  No host synchronisation.
@@ -6621,6 +6623,25 @@ int64_t cc_table_fetch(cc_ctx* ctx, int32_t id, const char* name, void* dst, int
     else if (nm == "rdeep") { src = T.rdeep; bytes = T.n; }
     else if (nm == "dlist") { src = T.dlist; bytes = 4 * T.n_deep; }
     else if (nm == "ext") { src = T.ext; bytes = 4 * (int64_t)T.ntid; }
+    else if (nm == "tid") { src = T.tid; bytes = 4 * T.n; }
+    else if (nm == "pos") { src = T.pos; bytes = 4 * T.n; }
+    else if (nm == "mtid") { src = T.mtid; bytes = 4 * T.n; }
+    else if (nm == "mpos") { src = T.mpos; bytes = 4 * T.n; }
+    else if (nm == "tlen") { src = T.tlen; bytes = 4 * T.n; }
+    else if (nm == "flag") { src = T.flag; bytes = 2 * T.n; }
+    else if (nm == "mapq") { src = T.mapq; bytes = T.n; }
+    else if (nm == "cigar_id") { src = T.cig; bytes = 4 * T.n; }
+    else if (nm == "qlen") { src = T.qlen; bytes = 4 * T.n; }
+    else if (nm == "lseq") { src = T.lseq; bytes = 4 * T.n; }
+    else if (nm == "bc_id") { src = T.bc; bytes = 4 * T.n; }
+    else if (nm == "rg_id") { src = T.rg; bytes = 4 * T.n; }
+    else if (nm == "rflags") { src = T.rflags; bytes = T.n; }
+    else if (nm == "qn_off") { src = T.qn_off; bytes = 8 * T.n; }
+    else if (nm == "qn_len") { src = T.qn_len; bytes = 2 * T.n; }
+    else if (nm == "pay_off") { src = T.pay_off; bytes = 8 * T.n; }
+    else if (nm == "rdig") { src = T.rdig; bytes = 8 * T.n; }
+    else if (nm == "qn_blob") { src = T.qn_blob; bytes = (int64_t)T.qn_bytes + 16; }   // (the blobs with their tails)
+    else if (nm == "payload") { src = T.payload; bytes = (int64_t)T.pay_bytes + 64; }
     else { ctx->err = "no table column " + nm; return CC_E_INVALID; }
     if (!dst) return bytes;
     if (cap < bytes) { ctx->err = "cc_table_fetch: destination too small"; return CC_E_INVALID; }

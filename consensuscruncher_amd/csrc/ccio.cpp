@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../include/consensuscruncher_amd.h"
+#include "unpack_core.h"
 
 namespace {
 
@@ -502,6 +503,7 @@ struct ccio_bam {
     std::vector<std::shared_ptr<const Bytes>> held;
     std::vector<const uint8_t*> rec;  // every record's block_size, in record order
     std::vector<int64_t> origin;      // ccio_bam_combine: each record's index in the combined inputs
+    std::shared_ptr<Bytes> packed;    // ccio_bam_decode_ids: a view's records packed into one stream
     std::shared_future<int> pending;  // CCIO_W_ASYNC: the write of the file this handle's stream is
                                       // being compressed into (it reads `data`: waited for first)
     ~ccio_bam() {
@@ -674,7 +676,8 @@ void derive_runs(cc_records* o, int T) {
 }
 // payload slot of one record: [qual | pad16][seq nibbles | pad16], the whole slot padded to
 // 128 B (one HBM/L2 line) so a read of L = 150 touches two lines, not three or four
-inline size_t pay_slot(int32_t lseq) { return (align16(lseq) + align16((lseq + 1) / 2) + 127) & ~(size_t)127; }
+// (unpack_core.h holds the one text of it: the device unpacker sizes its slots by the same function)
+inline size_t pay_slot(int32_t lseq) { return (size_t)upk::pay_slot(lseq); }
 
 }  // namespace
 
@@ -768,6 +771,102 @@ int64_t ccio_interner_swap_table(ccio_interner* it, int32_t* out, int64_t cap) {
 }  // extern "C"
 
 namespace {
+
+// The string work of one decode thread over its chunk of records (ccio_bam_decode and
+// ccio_bam_decode_ids share it): cigar, barcode and RG interned into thread-local tables, merged
+// into the shared interner afterwards (exact ids, deterministic order), and the two string-derived
+// record flags.
+struct StringPass {
+    Table t[3];                    // 0 barcode, 1 cigar, 2 RG
+    std::vector<int32_t> ids[3];   // per record of the chunk, its local id (-1: none)
+    std::string bc, rg, rawcig;
+    // cigar ids by the raw cigar bytes (formatting the string only for a new one)
+    std::unordered_map<std::string, int32_t> cig_by_raw;
+
+    void start(int64_t count) {
+        for (int k = 0; k < 3; ++k) ids[k].resize(count);
+    }
+    // Record k of the chunk (r = its core, after block_size).  mode 0: SSCS (barcode =
+    // qname.split(delim)[1], bad spacer when delim absent; consensus_helper.py:408,438-444); mode 1:
+    // duplex (barcode = qname.split('_')[0]; consensus_helper.py:447).  Returns CC_RF_BAD_SPACER |
+    // CC_RF_RG_UNSUPPORTED as they apply.
+    uint8_t one(int64_t k, const uint8_t* r, int32_t bs, uint32_t lqn, size_t qlen_name, uint32_t ncig, int32_t lseq,
+                int mode, const std::string& dl) {
+        const char* qn = (const char*)r + 32;
+        const uint8_t* cg = r + 32 + lqn;
+        rawcig.assign((const char*)cg, 4 * (size_t)ncig);
+        {
+            auto ci = cig_by_raw.find(rawcig);
+            if (ci == cig_by_raw.end()) ci = cig_by_raw.emplace(rawcig, t[1].get(cigar_string(r))).first;
+            ids[1][k] = ci->second;
+        }
+        uint8_t rf = 0;
+        // barcode, on the raw bytes
+        auto find_from = [&](size_t from, const std::string& pat) -> size_t {
+            if (pat.empty() || from > qlen_name) return std::string::npos;
+            for (size_t x = from; x + pat.size() <= qlen_name; ++x) {
+                const void* hit = memchr(qn + x, pat[0], qlen_name - x - pat.size() + 1);
+                if (!hit) return std::string::npos;
+                x = (size_t)((const char*)hit - qn);
+                if (!memcmp(qn + x, pat.data(), pat.size())) return x;
+            }
+            return std::string::npos;
+        };
+        if (mode == 0) {
+            const size_t d0 = find_from(0, dl);
+            if (dl.empty() || d0 == std::string::npos) {
+                rf |= CC_RF_BAD_SPACER;
+                ids[0][k] = -1;
+            } else {
+                const size_t st = d0 + dl.size();
+                const size_t d1 = find_from(st, dl);
+                bc.assign(qn + st, (d1 == std::string::npos ? qlen_name : d1) - st);
+                ids[0][k] = t[0].get(bc);
+            }
+        } else {
+            const void* u = memchr(qn, '_', qlen_name);
+            bc.assign(qn, u ? (size_t)((const char*)u - qn) : qlen_name);
+            ids[0][k] = t[0].get(bc);
+        }
+        // RG
+        bool bad = false;
+        rg.clear();
+        const uint8_t* aux = cg + 4 * (size_t)ncig + (lseq + 1) / 2 + lseq;
+        if (find_rg(aux, r + bs, rg, bad)) {
+            if (bad) { rf |= CC_RF_RG_UNSUPPORTED; ids[2][k] = -1; }
+            else ids[2][k] = t[2].get(rg);
+        } else {
+            ids[2][k] = -1;
+            if (bad) rf |= CC_RF_RG_UNSUPPORTED;
+        }
+        return rf;
+    }
+};
+
+// the threads' local tables merged into the shared interner: remap[k][t][local id] = shared id
+struct StringMerge {
+    std::vector<std::vector<int32_t>> remap[3];
+    StringMerge(ccio_interner* it, std::vector<StringPass>& loc) {
+        std::lock_guard<std::mutex> g(it->mu);
+        const size_t T = loc.size();
+        for (int k = 0; k < 3; ++k) {
+            remap[k].resize(T);
+            for (size_t t = 0; t < T; ++t) {
+                auto& strs = loc[t].t[k].strs;
+                remap[k][t].resize(strs.size());
+                for (size_t j = 0; j < strs.size(); ++j) remap[k][t][j] = it->t[k].get(strs[j]);
+            }
+        }
+    }
+    // record k of thread t's chunk: its shared ids into the three columns at i
+    void ids(const StringPass& L, int t, int64_t k, int32_t* bc_id, int32_t* cigar_id, int32_t* rg_id, int64_t i) const {
+        const int32_t v0 = L.ids[0][k];
+        bc_id[i] = v0 < 0 ? -1 : remap[0][t][v0];
+        cigar_id[i] = remap[1][t][L.ids[1][k]];
+        const int32_t v2 = L.ids[2][k];
+        rg_id[i] = v2 < 0 ? -1 : remap[2][t][v2];
+    }
+};
 
 // a plausible record at o: block_size, read name, cigar and sequence lengths consistent
 inline bool record_at(const uint8_t* d, size_t n, size_t o) {
@@ -950,24 +1049,16 @@ int ccio_bam_layout(ccio_bam* b, uint64_t* qn_bytes, uint64_t* pay_bytes, int32_
 
 // 64-bit digest of a record's bytes (block_size excluded, bin zeroed): record equality for the
 // "line read twice" rule (pysam compares every field of two AlignedSegments).
-static uint64_t rec_digest(const uint8_t* r, int32_t bs) {
-    uint64_t h = 0x9E3779B97F4A7C15ULL ^ (uint64_t)(uint32_t)bs;
-    auto mix = [](uint64_t x) {
-        x ^= x >> 31; x *= 0x7fb5d329728ea185ULL; x ^= x >> 27; x *= 0x81dadef4bc2dd44dULL; x ^= x >> 33;
-        return x;
-    };
-    int32_t i = 0;
-    for (; i + 8 <= bs; i += 8) {
-        uint64_t w;
-        memcpy(&w, r + i, 8);
-        if (i == 8) w &= ~(0xffffULL << 16);   // bin
-        h = mix(h ^ w) + 0x632BE59BD9B4E019ULL;
+// (upk::rec_digest, unpack_core.h: the device unpacker computes the same digest)
+struct MemSrc {
+    const uint8_t* r;   // record core (after block_size)
+    uint64_t word(uint32_t i, uint32_t valid) const {
+        uint64_t w = 0;
+        memcpy(&w, r + i, valid);
+        return w;
     }
-    uint64_t w = 0;
-    memcpy(&w, r + i, bs - i);
-    if (i == 8) w &= ~(0xffffULL << 16);
-    return mix(h ^ w ^ ((uint64_t)(bs - i) << 56));
-}
+};
+static uint64_t rec_digest(const uint8_t* r, int32_t bs) { return upk::rec_digest(MemSrc{r}, bs); }
 
 // Decode every record into SoA.  mode 0: SSCS (barcode = qname.split(delim)[1],
 // bad spacer when delim absent; consensus_helper.py:408,438-444); mode 1: duplex
@@ -992,21 +1083,15 @@ int ccio_bam_decode(ccio_bam* b, ccio_interner* it, int mode, const char* delim,
     });
     (void)chunk;
     for (int t = 0; t < T; ++t) { qbase[t + 1] += qbase[t]; pbase[t + 1] += pbase[t]; }
-    // thread-local string tables, merged afterwards (exact ids, deterministic order)
-    struct Local { Table t[3]; std::vector<int32_t> ids[3]; std::string err; };
     std::atomic<bool> too_long{false};
-    std::vector<Local> loc(T);
+    std::vector<StringPass> loc(T);
     parallel_for(n, T, [&](int64_t s, int64_t e, int t) {
-        Local& L = loc[t];
-        for (int k = 0; k < 3; ++k) L.ids[k].resize(e - s);
+        StringPass& L = loc[t];
+        L.start(e - s);
         uint64_t q = qbase[t], p = pbase[t];
-        std::string bc, rg, rawcig;
-        // cigar ids by the raw cigar bytes (formatting the string only for a new one)
-        std::unordered_map<std::string, int32_t> cig_by_raw;
         for (int64_t i = s; i < e; ++i) {
             const uint8_t* r = b->rec[i] + 4;
             int32_t bs = rd32(r - 4);
-            const uint8_t* end = r + bs;
             o->tid[i] = rd32(r + 0);
             o->pos[i] = rd32(r + 4);
             uint8_t lqn = r[8];
@@ -1023,7 +1108,7 @@ int ccio_bam_decode(ccio_bam* b, ccio_interner* it, int mode, const char* delim,
             // qname slot
             o->qn_off[i] = q;
             o->qn_len[i] = (uint16_t)qlen_name;
-            size_t slot = (lqn + 7) & ~7;
+            size_t slot = upk::qn_slot(lqn);
             memset(o->qn_blob + q, 0, slot);
             memcpy(o->qn_blob + q, qn, qlen_name);
             q += slot;
@@ -1039,12 +1124,6 @@ int ccio_bam_decode(ccio_bam* b, ccio_interner* it, int mode, const char* delim,
                 }
             }
             o->qlen[i] = ql;
-            rawcig.assign((const char*)cg, 4 * (size_t)ncig);
-            {
-                auto ci = cig_by_raw.find(rawcig);
-                if (ci == cig_by_raw.end()) ci = cig_by_raw.emplace(rawcig, L.t[1].get(cigar_string(r))).first;
-                L.ids[1][i - s] = ci->second;
-            }
             // payload: [qual | pad16][seq nibbles | pad16]
             const uint8_t* sq = cg + 4 * ncig;
             const uint8_t* qu = sq + (lseq + 1) / 2;
@@ -1058,69 +1137,17 @@ int ccio_bam_decode(ccio_bam* b, ccio_interner* it, int mode, const char* delim,
             p += pay_slot(lseq);
             uint8_t rf = 0;
             if (lseq == 0 || qu[0] == 0xff) rf |= CC_RF_QUAL_MISSING;
-            // barcode: qname.split(delim)[1] (SSCS) or qname.split('_')[0] (duplex), on the raw bytes
-            auto find_from = [&](size_t from, const std::string& pat) -> size_t {
-                if (pat.empty() || from > qlen_name) return std::string::npos;
-                for (size_t x = from; x + pat.size() <= qlen_name; ++x) {
-                    const void* hit = memchr(qn + x, pat[0], qlen_name - x - pat.size() + 1);
-                    if (!hit) return std::string::npos;
-                    x = (size_t)((const char*)hit - qn);
-                    if (!memcmp(qn + x, pat.data(), pat.size())) return x;
-                }
-                return std::string::npos;
-            };
-            if (mode == 0) {
-                const size_t d0 = find_from(0, dl);
-                if (dl.empty() || d0 == std::string::npos) {
-                    rf |= CC_RF_BAD_SPACER;
-                    L.ids[0][i - s] = -1;
-                } else {
-                    const size_t st = d0 + dl.size();
-                    const size_t d1 = find_from(st, dl);
-                    bc.assign(qn + st, (d1 == std::string::npos ? qlen_name : d1) - st);
-                    L.ids[0][i - s] = L.t[0].get(bc);
-                }
-            } else {
-                const void* u = memchr(qn, '_', qlen_name);
-                bc.assign(qn, u ? (size_t)((const char*)u - qn) : qlen_name);
-                L.ids[0][i - s] = L.t[0].get(bc);
-            }
-            // RG
-            bool bad = false;
-            rg.clear();
-            const uint8_t* aux = qu + lseq;
-            if (find_rg(aux, end, rg, bad)) {
-                if (bad) { rf |= CC_RF_RG_UNSUPPORTED; L.ids[2][i - s] = -1; }
-                else L.ids[2][i - s] = L.t[2].get(rg);
-            } else {
-                L.ids[2][i - s] = -1;
-                if (bad) rf |= CC_RF_RG_UNSUPPORTED;
-            }
+            // the strings: cigar, barcode, RG
+            rf |= L.one(i - s, r, bs, lqn, qlen_name, ncig, lseq, mode, dl);
             o->rflags[i] = rf;
             if (o->rdig) o->rdig[i] = rec_digest(r, bs);
             if (o->meta && !derive_record(o, i)) too_long = true;
         }
     });
-    // merge local tables into the shared interner
-    std::vector<std::vector<int32_t>> remap[3];
-    {
-        std::lock_guard<std::mutex> g(it->mu);
-        for (int k = 0; k < 3; ++k) {
-            remap[k].resize(T);
-            for (int t = 0; t < T; ++t) {
-                auto& strs = loc[t].t[k].strs;
-                remap[k][t].resize(strs.size());
-                for (size_t j = 0; j < strs.size(); ++j) remap[k][t][j] = it->t[k].get(strs[j]);
-            }
-        }
-    }
+    const StringMerge merged(it, loc);
     parallel_for(n, T, [&](int64_t s, int64_t e, int t) {
         for (int64_t i = s; i < e; ++i) {
-            int32_t v0 = loc[t].ids[0][i - s];
-            o->bc_id[i] = v0 < 0 ? -1 : remap[0][t][v0];
-            o->cigar_id[i] = remap[1][t][loc[t].ids[1][i - s]];
-            int32_t v2 = loc[t].ids[2][i - s];
-            o->rg_id[i] = v2 < 0 ? -1 : remap[2][t][v2];
+            merged.ids(loc[t], t, i - s, o->bc_id, o->cigar_id, o->rg_id, i);
             if (o->meta) derive_ids(o, i);
         }
     });
@@ -1131,6 +1158,95 @@ int ccio_bam_decode(ccio_bam* b, ccio_interner* it, int mode, const char* delim,
         if (too_long) o->n_deep = -1;
         else derive_runs(o, T);
     }
+    return 0;
+}
+
+// The slim decode behind the device unpacker (cc_table_unpack): per record the fixed-width columns
+// (tid, pos, mtid, mpos, tlen, flag, mapq, lseq, qlen, qn_len), the interned cigar / barcode / RG ids
+// (StringPass: ccio_bam_decode's interner, modes and delimiter rules) and rflags (all three bits).
+// payload, qn_blob, qn_off, pay_off, rdig and the derived columns of o are not touched (they may be
+// NULL).  *stream / *stream_bytes: the handle's records as one contiguous stream, block_size first
+// (the handle's own memory when its records already lie one after the other, else a packed copy the
+// handle keeps until it is closed or decoded again); rec_off[i]: record i's offset in it; *max_len:
+// the largest l_seq.  -1 for a record the shared parser (upk::parse) refuses.
+int ccio_bam_decode_ids(ccio_bam* b, ccio_interner* it, int mode, const char* delim, cc_records* o, int nthreads,
+                        const uint8_t** stream, uint64_t* stream_bytes, uint64_t* rec_off, int32_t* max_len) {
+    const int64_t n = (int64_t)b->rec.size();
+    const int T = hw_threads(nthreads);
+    const std::string dl = delim ? delim : "|";
+    std::vector<StringPass> loc(T);
+    std::vector<uint64_t> base(T + 1, 0);
+    std::vector<int32_t> ml(T, 0);
+    std::vector<const uint8_t*> first(T, nullptr), last_end(T, nullptr);
+    std::vector<char> contig(T, 1);
+    std::atomic<int64_t> bad{-1};
+    parallel_for(n, T, [&](int64_t s, int64_t e, int t) {
+        StringPass& L = loc[t];
+        L.start(e - s);
+        uint64_t sum = 0;
+        int32_t m = 0;
+        bool cg = true;
+        for (int64_t i = s; i < e; ++i) {
+            const uint8_t* rec = b->rec[i];
+            upk::Rec f;
+            if (!upk::parse(rec, 4 + (uint64_t)(uint32_t)rd32(rec), f)) {
+                int64_t was = -1;
+                bad.compare_exchange_strong(was, i);
+                return;
+            }
+            if (i > s && rec != b->rec[i - 1] + 4 + rd32(b->rec[i - 1])) cg = false;
+            rec_off[i] = sum;   // (within the chunk: its base is added below)
+            sum += 4 + (uint64_t)f.bs;
+            m = std::max(m, f.lseq);
+            o->tid[i] = f.tid;
+            o->pos[i] = f.pos;
+            o->mtid[i] = f.mtid;
+            o->mpos[i] = f.mpos;
+            o->tlen[i] = f.tlen;
+            o->flag[i] = (uint16_t)f.flag;
+            o->mapq[i] = (uint8_t)f.mapq;
+            o->lseq[i] = f.lseq;
+            o->qlen[i] = f.qlen;
+            o->qn_len[i] = (uint16_t)f.qn_len;
+            o->rflags[i] = f.rflags | L.one(i - s, rec + 4, f.bs, (uint32_t)f.l_read_name, (size_t)f.qn_len,
+                                            (uint32_t)f.n_cigar, f.lseq, mode, dl);
+        }
+        base[t + 1] = sum;
+        ml[t] = m;
+        contig[t] = cg;
+        if (e > s) {
+            first[t] = b->rec[s];
+            last_end[t] = b->rec[e - 1] + 4 + rd32(b->rec[e - 1]);
+        }
+    });
+    if (bad >= 0) { set_err("decode_ids: record " + std::to_string((long long)bad.load()) + " is malformed"); return -1; }
+    for (int t = 0; t < T; ++t) base[t + 1] += base[t];
+    bool one = true;
+    const uint8_t* prev_end = nullptr;
+    for (int t = 0; t < T; ++t) {
+        if (!first[t]) continue;
+        if (!contig[t] || (prev_end && first[t] != prev_end)) one = false;
+        prev_end = last_end[t];
+    }
+    const StringMerge merged(it, loc);
+    b->packed.reset();
+    if (!one) {
+        b->packed = std::make_shared<Bytes>();
+        b->packed->resize((size_t)base[T]);
+    }
+    uint8_t* pk = one ? nullptr : b->packed->data();
+    parallel_for(n, T, [&](int64_t s, int64_t e, int t) {
+        for (int64_t i = s; i < e; ++i) {
+            merged.ids(loc[t], t, i - s, o->bc_id, o->cigar_id, o->rg_id, i);
+            rec_off[i] += base[t];
+            if (pk) memcpy(pk + rec_off[i], b->rec[i], 4 + (size_t)rd32(b->rec[i]));
+        }
+    });
+    o->n = n;
+    *stream = n == 0 ? nullptr : (one ? b->rec[0] : pk);
+    *stream_bytes = base[T];
+    *max_len = 0;
+    for (int t = 0; t < T; ++t) *max_len = std::max(*max_len, ml[t]);
     return 0;
 }
 

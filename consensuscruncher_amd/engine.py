@@ -221,6 +221,26 @@ class Bam(object):
             raise IOError(N.io_error())
         return rec
 
+    def decode_ids(self, interner, mode, delim="|", nthreads=0):
+        """The slim decode in front of the device unpacker (ccio_bam_decode_ids): (records, stream,
+        rec_off).  records is a Records with its host integer columns, ids and rflags filled and no
+        blobs (qn_off, pay_off, rdig and the derived columns stay unset); stream is a uint8 view of
+        the handle's records as one contiguous stream (valid while this handle is open and not
+        decoded again), rec_off each record's offset in it."""
+        rec = Records(self.n, 0, 0, 0, nref=len(self.refs), derived=False)
+        off = np.zeros(max(self.n, 1), np.uint64)
+        sp, sb, ml = N.P(), C.c_uint64(), C.c_int32()
+        rc = N.io().ccio_bam_decode_ids(self.h, interner.h, mode, (delim or "|").encode(), C.byref(rec.struct), nthreads,
+                                        C.byref(sp), C.byref(sb), N.ptr(off), C.byref(ml))
+        if rc != 0:
+            raise IOError(N.io_error())
+        rec.max_len = int(ml.value)
+        if sb.value:
+            stream = np.ctypeslib.as_array(C.cast(sp, C.POINTER(C.c_uint8)), shape=(int(sb.value),))
+        else:
+            stream = np.zeros(0, np.uint8)
+        return rec, stream, off[:self.n]
+
 
 class Stream(object):
     """The order in which read_bam sees records: whole file (until_eof) or the bed
@@ -296,10 +316,22 @@ class Engine(object):
         self.tables = {}
         self.bgzf_device = False
         self.inflate_device = False
+        self.decode_device = False
         if os.environ.get("CC_BGZF_DEVICE") == "1":   # opt-in, in the style of CC_EXTRACT_GPU
             self.device_bgzf(True)
         if os.environ.get("CC_INFLATE_DEVICE") == "1":
             self.device_inflate(True)
+        if os.environ.get("CC_DECODE_DEVICE") == "1":
+            self.device_decode(True)
+
+    def device_decode(self, on):
+        """Switches table() between the host decoder (Bam.decode + upload, the default) and the device
+        record unpacker (unpack: Bam.decode_ids + cc_table_unpack).  The tables, and every file
+        written from them, are the same either way.  A per-engine switch (no process-wide hook).
+        Returns the previous state."""
+        was = self.decode_device
+        self.decode_device = bool(on)
+        return was
 
     def device_bgzf(self, on):
         """Wires (or unwires) this context's device BGZF encoder into libccio's writers
@@ -486,6 +518,43 @@ class Engine(object):
         self._check(self.lib.cc_table_upload(self.h, C.byref(records.struct), records.max_len, C.byref(tid)))
         self.tables[tid.value] = records
         return tid.value
+
+    def unpack_raw(self, stream, rec_off, cigar_id, bc_id, rg_id, rflags):
+        """cc_table_unpack on caller-given arrays: (table id, max_len).  The table is not registered
+        with a Records (free it with free_table)."""
+        stream = np.ascontiguousarray(stream, np.uint8)
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        n = len(off)
+        cols = [np.ascontiguousarray(a, t) for a, t in ((cigar_id, np.int32), (bc_id, np.int32), (rg_id, np.int32),
+                                                        (rflags, np.uint8))]
+        assert all(len(c) >= n for c in cols)
+        ml, tid = C.c_int32(), C.c_int32()
+        self._check(self.lib.cc_table_unpack(self.h, N.ptr(stream) if stream.size else None, stream.size,
+                                             N.ptr(off) if n else None, n, N.ptr(cols[0]), N.ptr(cols[1]), N.ptr(cols[2]),
+                                             N.ptr(cols[3]), C.byref(ml), C.byref(tid)))
+        return tid.value, ml.value
+
+    def unpack(self, bam, interner, mode, delim="|"):
+        """The device decode of bam: (records, table).  libccio's slim pass (Bam.decode_ids) keeps the
+        string work (interned cigar, barcode and RG ids, the string-derived record flags); the raw
+        records go to the device, where cc_table_unpack builds every other column and both blobs of
+        the table that bam.decode + upload would have given.  records holds the host integer columns
+        only."""
+        rec, stream, off = bam.decode_ids(interner, mode, delim)
+        table, ml = self.unpack_raw(stream, off, rec.cigar_id, rec.bc_id, rec.rg_id, rec.rflags)
+        if rec.n and ml != rec.max_len:
+            self.lib.cc_table_free(self.h, table)
+            raise N.CCError(-1, "device and host disagree on the longest read")
+        self.tables[table] = rec
+        rec.table = table   # (stages._upload takes it instead of uploading)
+        return rec, table
+
+    def table(self, bam, interner, mode, delim="|"):
+        """(records, table) of bam by the decoder this engine is switched to (device_decode)."""
+        if self.decode_device:
+            return self.unpack(bam, interner, mode, delim)
+        rec = bam.decode(interner, mode, delim)
+        return rec, self.upload(rec)
 
     def derive(self, t):
         """The table's derived columns built again (cc_table_derive; asynchronous)."""

@@ -103,6 +103,8 @@ IO_SIGS = {
     "ccio_bam_qname": (C.c_int, [P, C.c_int64, C.c_char_p, C.c_int]),
     "ccio_bam_layout": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), i32p, C.c_int]),
     "ccio_bam_decode": (C.c_int, [P, P, C.c_int, C.c_char_p, C.POINTER(cc_records), C.c_int]),
+    "ccio_bam_decode_ids": (C.c_int, [P, P, C.c_int, C.c_char_p, C.POINTER(cc_records), C.c_int, C.POINTER(P),
+                                      C.POINTER(C.c_uint64), P, i32p]),
     "ccio_format_csn_names": (C.c_int64, [P, C.c_int64, P, P, P, C.c_int64, P]),
     "ccio_dcs_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
     "ccio_duplex_tag": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
@@ -160,6 +162,7 @@ AMD_SIGS = {
     "cc_debug_build": (C.c_int, []),
     "cc_launch_count": (C.c_int64, []),
     "cc_table_upload": (C.c_int, [P, C.POINTER(cc_records), C.c_int32, i32p]),
+    "cc_table_unpack": (C.c_int, [P, P, C.c_uint64, P, C.c_int64, P, P, P, P, i32p, i32p]),
     "cc_table_free": (C.c_int, [P, C.c_int32]),
     "cc_table_derive": (C.c_int, [P, C.c_int32]),
     "cc_table_fetch": (C.c_int64, [P, C.c_int32, C.c_char_p, P, C.c_int64]),

@@ -52,15 +52,27 @@ def cleanup(sd, identifier, scorrect):
 
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
-                       bgzf="host", inflate="host"):
+                       bgzf="host", inflate="host", decode="host"):
     """bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
     output files: same records, other compressed bytes and .bai offsets).  inflate: "host" (the
     default) or "device" (the engine's BGZF inflater reads the input and stage files: same bytes read,
-    so the same outputs).  Either option is wired for this call only; see _consensus_pipeline."""
+    so the same outputs).  decode: "host" (the default) or "device" (the stage tables are built by
+    the engine's record unpacker from the raw records, Engine.unpack: the same tables, so the same
+    outputs).  Each option is wired for this call only; see _consensus_pipeline."""
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
     if inflate not in ("host", "device"):
         raise ValueError('inflate must be "host" or "device"')
+    if decode not in ("host", "device"):
+        raise ValueError('decode must be "host" or "device"')
+    if decode == "device":
+        engine = engine or get_engine()
+        was_dec = engine.device_decode(True)
+        try:
+            return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                      cleanup_files, all_unique_sscs, bgzf, inflate)
+        finally:
+            engine.device_decode(was_dec)
     if bgzf == "host" and inflate == "host":
         return _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
                                    cleanup_files, all_unique_sscs)

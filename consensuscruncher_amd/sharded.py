@@ -419,7 +419,7 @@ class Geometry(object):
             out.append((bam.pack(rec[m]) if m.any() else np.zeros(0, np.uint8), reg[m].astype(np.int32)))
         return out
 
-    def stage_input(self, bam, own, received, mode, delim, it, moved=None):
+    def stage_input(self, bam, own, received, mode, delim, it, moved=None, engine=None):
         """The rank's table (its records and the foreign ends, sorted by position) decoded, and its
         stream: the foreign entries in global stream order (sender rank, then the sender's stream
         order), then its own entries (those moved to another rank marked CC_REGION_MOVED)."""
@@ -443,7 +443,10 @@ class Geometry(object):
         sreg[nf:] = reg
         if moved is not None:
             sreg[nf:][np.asarray(moved, bool)] |= N.REGION_MOVED
-        records = table.decode(it, mode, delim)
+        if engine is not None and engine.decode_device:   # (its table is built with it: stages._upload)
+            records = engine.unpack(table, it, mode, delim)[0]
+        else:
+            records = table.decode(it, mode, delim)
         return table, records, Stream(srec, sreg, self.run, self.keys)
 
     def owners(self, b):
@@ -618,14 +621,24 @@ def to_owners(comm, geo, parts):
 
 def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|", scorrect="True", level=6,
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
-                     cuts=None, bgzf="host", inflate="host"):
+                     cuts=None, bgzf="host", inflate="host", decode="host"):
     """bgzf: "host" (the default) or "device": this rank's output files deflated by the engine's BGZF
     encoder.  inflate: "host" (the default) or "device": this rank's reads inflated by the engine's
-    BGZF inflater (pipeline.consensus_pipeline's options); see _sharded_pipeline."""
+    BGZF inflater.  decode: "host" (the default) or "device": this rank's stage tables built by the
+    engine's record unpacker (pipeline.consensus_pipeline's options); see _sharded_pipeline."""
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
     if inflate not in ("host", "device"):
         raise ValueError('inflate must be "host" or "device"')
+    if decode not in ("host", "device"):
+        raise ValueError('decode must be "host" or "device"')
+    if decode == "device":
+        was_dec = engine.device_decode(True)
+        try:
+            return sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                    blocks, held, refs, keep, finalize, timings, cuts, bgzf, inflate)
+        finally:
+            engine.device_decode(was_dec)
     if bgzf == "host" and inflate == "host":
         return _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
                                  blocks, held, refs, keep, finalize, timings, cuts)
@@ -712,7 +725,7 @@ def _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scor
             sent = comm.each(lambda r: geo.sent(cores[r][k], own[r][k], r))
             recv = comm.exchange(comm.each(lambda r: geo.routes(h[r], cores[r][k], own[r][k], r, sent[r])))
             out.append(comm.each(lambda r: geo.stage_input(h[r], own[r][k], recv[r], mode, delim, it_of[r],
-                                                           sent[r][0])))
+                                                           sent[r][0], engine=engine)))
         return out
 
     def on_root(fn):

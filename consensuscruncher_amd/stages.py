@@ -31,6 +31,20 @@ def get_engine():
     return _ENGINE
 
 
+def _decode(eng, bam, it, mode, delim="|"):
+    """bam's records by the decoder eng is switched to (Engine.device_decode): the host decoder, or the
+    device unpacker, whose records come with their table already built (_upload)."""
+    if eng.decode_device:
+        return eng.unpack(bam, it, mode, delim)[0]
+    return bam.decode(it, mode, delim)
+
+
+def _upload(eng, rec):
+    """rec's table: uploaded now, or the one the device unpacker built with it (Engine.unpack)."""
+    t = getattr(rec, "table", None)
+    return eng.upload(rec) if t is None else t
+
+
 def _stream(bam, rec, bedfile):
     return whole_file_stream(rec) if bedfile is None else bed_stream(rec, bam.refs, bedfile)
 
@@ -53,11 +67,11 @@ class SSCSRun(object):
             self.it = Interner()
             self.bam = bam if bam is not None else Bam(infile)
             self.times["open"] = time.time() - t
-            self.rec = self.bam.decode(self.it, MODE_SSCS, bdelim)
+            self.rec = _decode(eng, self.bam, self.it, MODE_SSCS, bdelim)
             self.stream = _stream(self.bam, self.rec, bedfile) if shard is None else shard(self.bam, self.rec)
         self.times["decode"] = time.time() - t - self.times.get("open", 0.0)
         t = time.time()
-        self.table = eng.upload(self.rec)
+        self.table = _upload(eng, self.rec)
         self.times["upload"] = time.time() - t
         t = time.time()
         self.g = eng.read_bam(self.table, self.stream, delim_filter=1, badread_file=1, scope_by_run=0)
@@ -275,12 +289,12 @@ class DCSRun(object):
         else:
             self.it = Interner()
             self.bam = bam if bam is not None else Bam(infile)
-            self.rec = self.bam.decode(self.it, MODE_DUPLEX)
+            self.rec = _decode(eng, self.bam, self.it, MODE_DUPLEX)
             self.stream = _stream(self.bam, self.rec, bedfile) if shard is None else shard(self.bam, self.rec)
         self.swap = self.it.swap_table()
         self.times["decode"] = time.time() - t
         t = time.time()
-        self.table = eng.upload(self.rec)
+        self.table = _upload(eng, self.rec)
         self.times["upload"] = time.time() - t
         t = time.time()
         self.g = eng.read_bam(self.table, self.stream, delim_filter=0, badread_file=0, scope_by_run=0)
@@ -396,11 +410,11 @@ class SCRun(object):
                 raise ValueError("an SSCS grouping is shared only for one chromosome scope (no bed file)")
             self.it = sscs_run.it
             self.sbam = bam if bam is not None else Bam(singleton)
-            self.srec = self.sbam.decode(self.it, MODE_DUPLEX)
+            self.srec = _decode(eng, self.sbam, self.it, MODE_DUPLEX)
             self.sstream = _stream(self.sbam, self.srec, None)
             self.xbam, self.xrec, self.xstream = sscs_run.bam, sscs_run.rec, sscs_run.stream
             self.swap = self.it.swap_table()
-            self.ts = eng.upload(self.srec)
+            self.ts = _upload(eng, self.srec)
             self.tx, self.gx = sscs_run.table, sscs_run.g
             self.gs = eng.read_bam(self.ts, self.sstream, delim_filter=0, badread_file=0, scope_by_run=0)
             eng.singleton_correction(self.gs, self.gx, self.swap)
@@ -411,8 +425,8 @@ class SCRun(object):
             self.it = Interner()
             self.sbam = bam if bam is not None else Bam(singleton)
             self.xbam = xbam if xbam is not None else Bam('{}.sscs{}'.format(self.base, rest))
-            self.srec = self.sbam.decode(self.it, MODE_DUPLEX)
-            self.xrec = self.xbam.decode(self.it, MODE_DUPLEX)
+            self.srec = _decode(eng, self.sbam, self.it, MODE_DUPLEX)
+            self.xrec = _decode(eng, self.xbam, self.it, MODE_DUPLEX)
             if shard is None:
                 self.sstream = _stream(self.sbam, self.srec, bedfile)
                 self.xstream = _stream(self.xbam, self.xrec, bedfile)
@@ -420,8 +434,8 @@ class SCRun(object):
                 self.sstream = shard(self.sbam, self.srec)
                 self.xstream = shard(self.xbam, self.xrec)
         self.swap = self.it.swap_table()
-        self.ts = eng.upload(self.srec)
-        self.tx = eng.upload(self.xrec)
+        self.ts = _upload(eng, self.srec)
+        self.tx = _upload(eng, self.xrec)
         self.gs = eng.read_bam(self.ts, self.sstream, delim_filter=0, badread_file=0, scope_by_run=0)
         self.gx = eng.read_bam(self.tx, self.xstream, delim_filter=0, badread_file=0, scope_by_run=1)
         eng.singleton_correction(self.gs, self.gx, self.swap)

@@ -149,6 +149,18 @@ int ccio_bam_qname(ccio_bam *b, int64_t i, char *buf, int cap);
 int ccio_bam_layout(ccio_bam *b, uint64_t *qn_bytes, uint64_t *pay_bytes, int32_t *max_len, int nthreads);
 /* mode 0: SSCS barcode = qname.split(delim)[1]; mode 1: duplex barcode = qname.split('_')[0] */
 int ccio_bam_decode(ccio_bam *b, ccio_interner *it, int mode, const char *delim, cc_records *out, int nthreads);
+/* The slim decode in front of the device unpacker (cc_table_unpack).  Fills, per record, out's tid,
+ * pos, mtid, mpos, tlen, flag, mapq, lseq, qlen, qn_len, the interned cigar_id / bc_id / rg_id
+ * (ccio_bam_decode's interner, modes and delimiter rules) and rflags (all three bits), and nothing
+ * else: payload, qn_blob, qn_off, pay_off, rdig and the derived columns are not touched and may be
+ * NULL.  *stream / *stream_bytes: the handle's records as one contiguous stream, block_size first;
+ * it points into the handle (its own stream, or a packed copy for a combined view) and stays valid
+ * until the handle is closed or decoded again.  rec_off[n]: each record's offset in the stream
+ * (rec_off[i] + 4 + block_size = rec_off[i + 1]; the last one ends at stream_bytes).  *max_len: the
+ * largest l_seq.  -1 (ccio_last_error names the record) for a record whose lengths do not fit its
+ * block_size (csrc/unpack_core.h's refusals). */
+int ccio_bam_decode_ids(ccio_bam *b, ccio_interner *it, int mode, const char *delim, cc_records *out, int nthreads,
+                        const uint8_t **stream, uint64_t *stream_bytes, uint64_t *rec_off, int32_t *max_len);
 
 /* sscs_qname fields (9 int32 per name: bc, tidLo, posLo, tidHi, posHi, cigA, cigB,
  * strand(0 pos/1 neg/2 None), |tlen|) + ':' + suffix.  blob NULL = size query. */
@@ -432,6 +444,22 @@ int cc_debug_sort_pairs(cc_ctx *ctx, int32_t engine, const uint64_t *keys, const
 /* copy a record SoA into HBM; returns a table id.  With the decoder's layout (rec->meta non-NULL,
  * rec->n_deep >= 0) its columns are uploaded as they are; otherwise k_derive builds them on the device */
 int cc_table_upload(cc_ctx *ctx, const cc_records *rec, int32_t max_len, int32_t *table_id);
+/* The same table built on the device from raw BAM records (opt-in; the default path is
+ * ccio_bam_decode + cc_table_upload).  recs: `bytes` bytes of records, block_size first, rec_off[n]
+ * each record's offset (strictly increasing, inside the stream); cigar_id, bc_id, rg_id, rflags: the
+ * string-derived columns of ccio_bam_decode_ids.  The stream and the four columns are uploaded, and
+ * kernels build every other column and both blobs: byte for byte what ccio_bam_decode +
+ * cc_table_upload give for the same records (padding and blob tails included), with the derived
+ * columns built by k_derive as for any table uploaded without the decoder's layout.  *max_len: the
+ * largest l_seq.  Every record is checked on the device before anything is read through its lengths
+ * (csrc/unpack_core.h): an offset out of range or out of order, block_size < 32 or past the stream,
+ * l_seq < 0, lengths overrunning block_size, or a CC_RF_QUAL_MISSING bit in rflags that disagrees
+ * with the record is CC_E_INVALID (cc_last_error names the first such record); l_seq > 0xffff or a
+ * payload of 64 GiB or more is CC_E_UNSUPPORTED.  After any error no table exists and nothing stays
+ * allocated. */
+int cc_table_unpack(cc_ctx *ctx, const uint8_t *recs, uint64_t bytes, const uint64_t *rec_off, int64_t n,
+                    const int32_t *cigar_id, const int32_t *bc_id, const int32_t *rg_id, const uint8_t *rflags,
+                    int32_t *max_len, int32_t *table_id);
 int cc_table_free(cc_ctx *ctx, int32_t table_id);
 /* the table's derived columns (member records, position keys, qname digests, record cores and deep
  * bits, the deep-group list) built again from its record columns, on the context's stream without a
@@ -440,7 +468,10 @@ int cc_table_free(cc_ctx *ctx, int32_t table_id);
  * those columns are part of its input, as the record columns are */
 int cc_table_derive(cc_ctx *ctx, int32_t table_id);
 /* test hook: a table's derived column ("rkey", "meta", "core", "qn_ol", "qdig", "rdeep", "dlist",
- * "ext") copied to dst (cap bytes); returns its byte size, or a CC_E_* code */
+ * "ext"), base column ("tid", "pos", "mtid", "mpos", "tlen", "flag", "mapq", "cigar_id", "qlen",
+ * "lseq", "bc_id", "rg_id", "rflags", "qn_off", "qn_len", "pay_off", "rdig") or blob ("qn_blob" with
+ * its 16-byte tail, "payload" with its 64-byte tail) copied to dst (cap bytes); returns its byte
+ * size, or a CC_E_* code */
 int64_t cc_table_fetch(cc_ctx *ctx, int32_t table_id, const char *name, void *dst, int64_t cap);
 
 /* read_bam over a record stream (region-major order; stream_rec indexes the
