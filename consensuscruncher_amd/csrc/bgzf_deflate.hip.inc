@@ -18,6 +18,21 @@
 //     words the piece occupied (the piece is dead by then); the words are copied out with plain
 //     vector stores.
 // The CRC32 field is left to the host (it runs while the device encodes).
+//
+// The kernel is a template over the effort (cc_bgzf_set_effort).  Effort 1 is the encoder above.
+// Effort 2 replaces pass 1's match finder and adds a lazy step; everything from the parse on is
+// the same text:
+//   buckets: a hash slot holds the four largest positions entered so far, sorted, as 16-bit
+//     position + 1 in one 64-bit LDS word (a compare-and-swap insert: the content after any set of
+//     inserts is the set's four largest, whatever their order).
+//   same-tile visibility: the eight 64-position segments of a tile take turns; a wave reads its
+//     lanes' buckets, then enters its own positions, then the workgroup meets at a barrier.  A
+//     position therefore sees every hashed position before its own segment and none from it on:
+//     a function of the bytes alone.  Distance 1 is still tried on its own.
+//   lazy step: the finder runs one tile ahead of the parse, so position i knows len[i + 1] (also
+//     across a tile's edge) and becomes a literal when len[i + 1] > len[i]; its successor is still
+//     a function of i alone and the pointer-jumping parse is unchanged.
+// With 64 KiB of buckets beside the resident piece effort 2 runs one workgroup per CU.
 #include <mutex>
 
 #include "deflate_core.h"
@@ -31,6 +46,11 @@ constexpr int BG_SLOTS = 3072;            // hash slots: piece + table + the res
 constexpr int BG_OSLOT = 0x10000 + 64;    // a member's slot in the device output
 constexpr int BG_CHUNK = 256;             // pieces per launch
 constexpr uint32_t BG_NONE = 0xffffffffu; // a position that starts no token
+constexpr int BG2_WAYS = 4;               // effort 2: positions per bucket (16 bits each, one 64-bit word)
+constexpr int BG2_SLOTS = 8192;           // effort 2: buckets (64 KiB: with the piece under the CU's 160 KiB)
+
+template <int EFFORT> struct BgTab { typedef uint32_t T; static constexpr int N = BG_SLOTS; };
+template <> struct BgTab<2> { typedef unsigned long long T; static constexpr int N = BG2_SLOTS; };
 
 struct BgCodes {   // built after pass 1 in the hash table's LDS
     uint32_t lfreq[288], dfreq[32];
@@ -42,6 +62,7 @@ struct BgCodes {   // built after pass 1 in the hash table's LDS
     dfl::DynHeader hdr;
 };
 static_assert(sizeof(BgCodes) <= BG_SLOTS * sizeof(uint32_t), "the code tables reuse the hash table's LDS");
+static_assert(BG2_WAYS * 16 == 64 && BG_PIECE < 0xffff, "a bucket is one 64-bit word of position + 1 in 16 bits");
 
 struct BgSink {   // the header writer's bit sink: one thread, plain ORs into zeroed LDS words
     uint32_t* w;
@@ -72,11 +93,70 @@ __device__ inline int bg_extend(const uint32_t* W, int c, int i, int maxl) {
     return l < maxl ? l : maxl;
 }
 
-__global__ __launch_bounds__(BG_T) void k_bgzf_deflate(const uint8_t* __restrict__ in, uint64_t n_total,
+// bucket b (16-bit fields, the largest in the low bits, 0: empty) with p entered: the four largest
+__device__ inline unsigned long long bg_bucket_with(unsigned long long b, uint32_t p) {
+    int k = 0;   // fields above p
+#pragma unroll
+    for (int w = 0; w < BG2_WAYS; ++w) k += (uint32_t)((b >> (16 * w)) & 0xffff) > p;
+    if (k == BG2_WAYS) return b;
+    const unsigned long long lo = (1ull << (16 * k)) - 1;   // k <= 3
+    return (b & lo) | ((unsigned long long)p << (16 * k)) | ((b & ~lo) << 16);
+}
+
+// A tile's parse, tokens and histogram counts: position i = tb + tid offers (len, dist), len 0: a
+// literal.  carry: the first position no earlier token covers (the same in every thread).
+__device__ __forceinline__ void bg_parse_tile(const int tb, const int i, const int n, const int len, const int dist,
+                                          int& carry, uint16_t* s_exit, uint32_t* s_lhist, uint32_t* s_dhist,
+                                          const uint8_t* s_bytes, uint32_t* tokp) {
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nxt = i + (len ? len : 1);
+    const int wb = tb + (tid & ~63), we = wb + 64;
+    int E = nxt;   // where the chain from this position leaves the wave's segment
+    for (int it = 0; it < 6; ++it) {
+        const bool in_seg = E < we;
+        const int v = __shfl(E, in_seg ? E - wb : lane);
+        if (in_seg) E = v;
+    }
+    s_exit[tid] = (uint16_t)(E - tb);
+    __syncthreads();
+    int s = carry, mystart = 0x7fffffff;
+    for (int c = 0; c < BG_T / 64; ++c)
+        if (s < tb + 64 * c + 64) {
+            if (c == wv) mystart = s;
+            s = tb + (int)s_exit[s - tb];
+        }
+    carry = s;
+    uint64_t mask = 0;
+    int p = __builtin_amdgcn_readfirstlane(mystart);
+    while (p < we) {
+        mask |= 1ull << (p - wb);
+        p = __builtin_amdgcn_readlane(nxt, p - wb);
+    }
+    if (i < n) {
+        uint32_t t = BG_NONE;
+        if ((mask >> lane) & 1) {
+            if (len) {
+                int eb, ev;
+                t = dfl::tok_match(len, dist);
+                atomicAdd(&s_lhist[dfl::len_sym(len, &eb, &ev)], 1u);
+                atomicAdd(&s_dhist[dfl::dist_sym(dist, &eb, &ev)], 1u);
+            } else {
+                t = dfl::tok_lit(s_bytes[i]);
+                atomicAdd(&s_lhist[t], 1u);
+            }
+        }
+        tokp[i] = t;
+    }
+}
+
+// (flatten: with two instantiations deflate_core.h's builders have two callers each and would no
+// longer be inlined as they are into a single kernel)
+template <int EFFORT>
+__global__ __launch_bounds__(BG_T) __attribute__((flatten)) void k_bgzf_deflate(const uint8_t* __restrict__ in, uint64_t n_total,
                                                        uint32_t* __restrict__ tok, uint8_t* __restrict__ out,
                                                        uint32_t* __restrict__ out_len) {
     __shared__ uint32_t s_data[BG_WORDS];
-    __shared__ uint32_t s_tab[BG_SLOTS];
+    __shared__ typename BgTab<EFFORT>::T s_tab[BgTab<EFFORT>::N];
     __shared__ uint32_t s_lhist[288], s_dhist[32];
     __shared__ uint16_t s_exit[BG_T];
     __shared__ uint32_t s_wsum[BG_T / 64];
@@ -97,14 +177,15 @@ __global__ __launch_bounds__(BG_T) void k_bgzf_deflate(const uint8_t* __restrict
                 if (b + k < n) v |= (uint32_t)src[b + k] << (8 * k);
         s_data[w] = v;
     }
-    for (int k = tid; k < BG_SLOTS; k += BG_T) s_tab[k] = 0;
+    for (int k = tid; k < BgTab<EFFORT>::N; k += BG_T) s_tab[k] = 0;
     if (tid < 288) s_lhist[tid] = 0;
     if (tid < 32) s_dhist[tid] = 0;
     if (tid < 4) s_misc[tid] = 0;
     __syncthreads();
 
     // ---- pass 1: matches, parse, tokens, histograms
-    int carry = 0;   // the first position no earlier token covers (the same in every thread)
+    int carry = 0;
+    if constexpr (EFFORT == 1) {
     for (int tb = 0; tb < n; tb += BG_T) {
         const int i = tb + tid;
         int len = 0, dist = 0;
@@ -132,44 +213,79 @@ __global__ __launch_bounds__(BG_T) void k_bgzf_deflate(const uint8_t* __restrict
         }
         __syncthreads();   // every lookup of this tile precedes its inserts
         if (hashed) atomicMax(&s_tab[slot], (uint32_t)(i + 1));
-        const int nxt = i + (len ? len : 1);
-        const int wb = tb + (tid & ~63), we = wb + 64;
-        int E = nxt;   // where the chain from this position leaves the wave's segment
-        for (int it = 0; it < 6; ++it) {
-            const bool in_seg = E < we;
-            const int v = __shfl(E, in_seg ? E - wb : lane);
-            if (in_seg) E = v;
-        }
-        s_exit[tid] = (uint16_t)(E - tb);
-        __syncthreads();
-        int s = carry, mystart = 0x7fffffff;
-        for (int c = 0; c < BG_T / 64; ++c)
-            if (s < tb + 64 * c + 64) {
-                if (c == wv) mystart = s;
-                s = tb + (int)s_exit[s - tb];
+        bg_parse_tile(tb, i, n, len, dist, carry, s_exit, s_lhist, s_dhist, s_bytes, tokp);
+    }
+    } else {
+    __shared__ uint16_t s_len[BG_T + 2];   // the tile's lengths and the next tile's first
+    // the matches of tile tb; its positions enter the buckets segment by segment (uniform barriers)
+    auto find_tile = [&](const int tb, int& len, int& dist) {
+        const int i = tb + tid;
+        len = 0;
+        dist = 0;
+        const bool hashed = i + 4 <= n;
+        uint32_t slot = 0;
+        if (hashed) slot = (((bg_load32(s_data, i) * 2654435761u) >> 16) * (uint32_t)BG2_SLOTS) >> 16;   // < BG2_SLOTS
+        // a position with four later positions of its own segment in its bucket would be pushed out
+        // by them: runs skip the insert (the bucket's content is the same)
+        bool enter = hashed;
+        {
+            bool covered = true;
+#pragma unroll
+            for (int k = 1; k <= BG2_WAYS; ++k) {
+                const uint32_t sk = __shfl_down(hashed ? slot : 0xffffffffu, k);
+                covered = covered && lane + k < 64 && sk == slot;
             }
-        carry = s;
-        uint64_t mask = 0;
-        int p = __builtin_amdgcn_readfirstlane(mystart);
-        while (p < we) {
-            mask |= 1ull << (p - wb);
-            p = __builtin_amdgcn_readlane(nxt, p - wb);
+            if (covered) enter = false;
         }
-        if (i < n) {
-            uint32_t t = BG_NONE;
-            if ((mask >> lane) & 1) {
-                if (len) {
-                    int eb, ev;
-                    t = dfl::tok_match(len, dist);
-                    atomicAdd(&s_lhist[dfl::len_sym(len, &eb, &ev)], 1u);
-                    atomicAdd(&s_dhist[dfl::dist_sym(dist, &eb, &ev)], 1u);
-                } else {
-                    t = dfl::tok_lit(s_bytes[i]);
-                    atomicAdd(&s_lhist[t], 1u);
+        unsigned long long seen = 0;   // the bucket before this segment's positions
+        for (int sg = 0; sg < BG_T / 64; ++sg) {
+            if (sg == wv && hashed) {
+                seen = s_tab[slot];   // the whole wave reads before any of its lanes enters
+                if (enter) {
+                    unsigned long long old = seen;
+                    for (;;) {
+                        const unsigned long long nw = bg_bucket_with(old, (uint32_t)(i + 1));
+                        if (nw == old) break;
+                        const unsigned long long got = atomicCAS(&s_tab[slot], old, nw);
+                        if (got == old) break;
+                        old = got;
+                    }
                 }
             }
-            tokp[i] = t;
+            __syncthreads();
         }
+        if (i < n) {
+            const int maxl = n - i < dfl::MAX_MATCH ? n - i : dfl::MAX_MATCH;
+#pragma unroll
+            for (int w = 0; w < BG2_WAYS; ++w) {   // nearest first: a farther one must be longer
+                const int c = (int)((seen >> (16 * w)) & 0xffff);   // position + 1, 0: none
+                const int d = i - (c - 1);
+                if (c && d > 0 && d <= dfl::WINDOW && len < maxl && s_bytes[c - 1 + len] == s_bytes[i + len]) {
+                    const int l = bg_extend(s_data, c - 1, i, maxl);
+                    if (l >= dfl::MIN_MATCH && l > len) { len = l; dist = d; }
+                }
+            }
+            if (i >= 1 && len < maxl) {
+                const int l1 = bg_extend(s_data, i - 1, i, maxl);
+                if (l1 >= dfl::MIN_MATCH && l1 >= len) { len = l1; dist = 1; }
+            }
+            if (len == dfl::MIN_MATCH && dist > 4096) len = 0;   // three literals are cheaper
+        }
+    };
+    int len, dist;
+    find_tile(0, len, dist);
+    for (int tb = 0; tb < n; tb += BG_T) {
+        int nlen = 0, ndist = 0;
+        if (tb + BG_T < n) find_tile(tb + BG_T, nlen, ndist);
+        s_len[tid] = (uint16_t)len;
+        if (tid == 0) s_len[BG_T] = (uint16_t)nlen;   // of position tb + BG_T
+        __syncthreads();
+        if ((int)s_len[tid + 1] > len) len = 0;   // lazy: the next position's match is longer
+        // (the parse's barrier separates these reads from the next tile's writes)
+        bg_parse_tile(tb, tb + tid, n, len, dist, carry, s_exit, s_lhist, s_dhist, s_bytes, tokp);
+        len = nlen;
+        dist = ndist;
+    }
     }
     __syncthreads();
 
@@ -367,6 +483,7 @@ struct BgzfDec;   // the inflater's buffers (bgzf_inflate.hip.inc): same streams
 struct BgzfEnc {
     std::mutex mu;          // one caller at a time (the writers' and readers' threads call concurrently)
     bool ready = false, broken = false, streams = false;
+    int effort = 1;         // cc_bgzf_set_effort: read once per round, under mu
     BgzfDec* dec = nullptr;
     std::string err;
     hipStream_t st[2] = {nullptr, nullptr};
@@ -497,6 +614,7 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
     BGCHK(hipSetDevice(ctx->device));
     if (!E->ready) RC(bgzf_init(E));
     const bool prof = ctx->profiling;
+    const auto kernel = E->effort == 2 ? k_bgzf_deflate<2> : k_bgzf_deflate<1>;   // the whole round at one effort
     const int64_t nchunks = (np + BG_CHUNK - 1) / BG_CHUNK;
     std::vector<uint32_t> crcs((size_t)np);
     auto pieces_of = [&](int64_t k) { return (int)std::min<int64_t>(BG_CHUNK, np - k * BG_CHUNK); };
@@ -509,7 +627,7 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
         if (prof) BGCHK(hipEventRecord(E->ev[b][3], E->st[b]));
         E->timed[b] = prof;
         if (prof) BGCHK(hipEventRecord(E->ev[b][0], E->st[b]));
-        hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)pc), dim3(BG_T), 0, E->st[b], E->d_in[b], bytes, E->d_tok[b],
+        hipLaunchKernelGGL(kernel, dim3((unsigned)pc), dim3(BG_T), 0, E->st[b], E->d_in[b], (uint64_t)bytes, E->d_tok[b],
                            E->d_out[b], E->d_len[b]);
         if (prof) BGCHK(hipEventRecord(E->ev[b][1], E->st[b]));
         hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)pc), dim3(256), 0, E->st[b], E->d_out[b], E->d_len[b], E->d_pack[b]);
@@ -602,6 +720,18 @@ int64_t cc_bgzf_deflate(cc_ctx* ctx, const uint8_t* data, uint64_t n, uint8_t* s
     const int64_t r = bgzf_encode(ctx, E, data, n, stage, slot, out_len, cap);
     if (r < 0) ctx->err = E->err;
     return r;
+}
+
+int cc_bgzf_set_effort(cc_ctx* ctx, int effort) {
+    if (!ctx) return CC_E_INVALID;
+    if (effort != 1 && effort != 2) {
+        ctx->err = "cc_bgzf_set_effort: the effort is 1 or 2";
+        return CC_E_INVALID;
+    }
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);   // a running round holds it: it finishes at its own effort
+    E->effort = effort;
+    return 0;
 }
 
 int cc_bgzf_hook(cc_ctx* ctx, ccio_deflate_fn* fn, void** user) {

@@ -315,8 +315,11 @@ class Engine(object):
         self.h = h
         self.tables = {}
         self.bgzf_device = False
+        self._bgzf_effort = 1
         self.inflate_device = False
         self.decode_device = False
+        if os.environ.get("CC_BGZF_EFFORT"):   # the encoder's effort, for CC_BGZF_DEVICE and bgzf_deflate alike
+            self._set_bgzf_effort(os.environ["CC_BGZF_EFFORT"])
         if os.environ.get("CC_BGZF_DEVICE") == "1":   # opt-in, in the style of CC_EXTRACT_GPU
             self.device_bgzf(True)
         if os.environ.get("CC_INFLATE_DEVICE") == "1":
@@ -333,7 +336,25 @@ class Engine(object):
         self.decode_device = bool(on)
         return was
 
-    def device_bgzf(self, on):
+    @property
+    def bgzf_effort(self):
+        """The device BGZF encoder's effort (cc_bgzf_set_effort): 1 or 2."""
+        return self._bgzf_effort
+
+    def _set_bgzf_effort(self, effort):
+        """cc_bgzf_set_effort; returns the previous effort.  ValueError for anything but 1 or 2."""
+        was = self._bgzf_effort
+        try:
+            effort = int(effort)
+        except (TypeError, ValueError):
+            raise ValueError("bgzf effort must be 1 or 2")
+        if effort not in (1, 2):
+            raise ValueError("bgzf effort must be 1 or 2")
+        self._check(self.lib.cc_bgzf_set_effort(self.h, effort))
+        self._bgzf_effort = effort
+        return was
+
+    def device_bgzf(self, on, effort=None):
         """Wires (or unwires) this context's device BGZF encoder into libccio's writers
         (cc_bgzf_hook -> ccio_set_deflate_hook): every BAM written at level >= 1 from now on is
         deflated by k_bgzf_deflate instead of the host codec.  The records are the same either way;
@@ -341,10 +362,19 @@ class Engine(object):
         last engine to wire it serves the writers, and the engine it took the hook from reads
         bgzf_device False from then on (its close or unwiring leaves the new owner's hook alone).
         Wiring and unwiring wait for the background writes first, so a file is encoded by one
-        encoder throughout.  Returns the previous state."""
+        encoder throughout.  effort (1 or 2; None leaves it as it is) is the encoder's effort from
+        now on, for the writers and for bgzf_deflate; a change while the hook is wired waits for the
+        background writes first.  Returns the previous state."""
         global _BGZF_OWNER
         was = self.bgzf_device
         on = bool(on)
+        if effort is not None:
+            if int(effort) not in (1, 2):
+                raise ValueError("bgzf effort must be 1 or 2")
+            if was and int(effort) != self._bgzf_effort:
+                if N.io().ccio_flush() != 0:   # a file is encoded at one effort throughout
+                    raise IOError(N.io_error())
+            self._set_bgzf_effort(effort)
         if on == was:
             return was
         io = N.io()
@@ -438,9 +468,16 @@ class Engine(object):
             raise N.CCError(got, self.lib.cc_last_error(self.h).decode(errors="replace"))
         return out[:total].tobytes(), [bool(v) for v in ok[:n]]
 
-    def bgzf_deflate(self, data):
+    def bgzf_deflate(self, data, effort=None):
         """cc_bgzf_deflate: the framed BGZF members of data (bytes-like), one per 0xff00-byte piece,
-        as a list of bytes objects."""
+        as a list of bytes objects.  effort (1 or 2) holds for this call only; None encodes at the
+        engine's effort."""
+        if effort is not None:
+            was = self._set_bgzf_effort(effort)
+            try:
+                return self.bgzf_deflate(data)
+            finally:
+                self._set_bgzf_effort(was)
         buf = np.frombuffer(bytes(data), np.uint8)
         pieces = (buf.size + 0xff00 - 1) // 0xff00
         slot = 0x10000

@@ -154,6 +154,7 @@ AMD_SIGS = {
     "cc_synchronize": (C.c_int, [P]),
     "cc_bgzf_deflate": (C.c_int64, [P, P, C.c_uint64, P, C.c_uint64, P, C.c_int64]),
     "cc_bgzf_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
+    "cc_bgzf_set_effort": (C.c_int, [P, C.c_int]),
     "cc_bgzf_inflate": (C.c_int64, [P, P, P, P, P, P, C.c_int64, P, P]),
     "cc_bgzf_inflate_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
     "cc_defer": (C.c_int, [P, C.c_int]),

@@ -52,15 +52,21 @@ def cleanup(sd, identifier, scorrect):
 
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
-                       bgzf="host", inflate="host", decode="host"):
+                       bgzf="host", inflate="host", decode="host", bgzf_effort=1):
     """bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
-    output files: same records, other compressed bytes and .bai offsets).  inflate: "host" (the
+    output files: same records, other compressed bytes and .bai offsets).  bgzf_effort: the device
+    encoder's effort, 1 (the default) or 2 (smaller files, a slower kernel); 2 needs bgzf="device",
+    and the BGZF level does not select it.  inflate: "host" (the
     default) or "device" (the engine's BGZF inflater reads the input and stage files: same bytes read,
     so the same outputs).  decode: "host" (the default) or "device" (the stage tables are built by
     the engine's record unpacker from the raw records, Engine.unpack: the same tables, so the same
     outputs).  Each option is wired for this call only; see _consensus_pipeline."""
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
+    if bgzf_effort not in (1, 2):
+        raise ValueError("bgzf_effort must be 1 or 2")
+    if bgzf_effort != 1 and bgzf != "device":
+        raise ValueError('bgzf_effort=2 needs bgzf="device"')
     if inflate not in ("host", "device"):
         raise ValueError('inflate must be "host" or "device"')
     if decode not in ("host", "device"):
@@ -70,14 +76,15 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
         was_dec = engine.device_decode(True)
         try:
             return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
-                                      cleanup_files, all_unique_sscs, bgzf, inflate)
+                                      cleanup_files, all_unique_sscs, bgzf, inflate, bgzf_effort=bgzf_effort)
         finally:
             engine.device_decode(was_dec)
     if bgzf == "host" and inflate == "host":
         return _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
                                    cleanup_files, all_unique_sscs)
     engine = engine or get_engine()
-    was = engine.device_bgzf(True) if bgzf == "device" else None
+    was_effort = engine.bgzf_effort
+    was = engine.device_bgzf(True, effort=bgzf_effort) if bgzf == "device" else None
     try:
         was_in = engine.device_inflate(True) if inflate == "device" else None
         try:
@@ -88,7 +95,7 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
                 engine.device_inflate(was_in)
     finally:
         if was is not None:
-            engine.device_bgzf(was)
+            engine.device_bgzf(was, effort=was_effort)
 
 
 def _consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,

@@ -621,13 +621,17 @@ def to_owners(comm, geo, parts):
 
 def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|", scorrect="True", level=6,
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
-                     cuts=None, bgzf="host", inflate="host", decode="host"):
+                     cuts=None, bgzf="host", inflate="host", decode="host", bgzf_effort=1):
     """bgzf: "host" (the default) or "device": this rank's output files deflated by the engine's BGZF
-    encoder.  inflate: "host" (the default) or "device": this rank's reads inflated by the engine's
+    encoder, at bgzf_effort 1 (the default) or 2 (2 needs bgzf="device").  inflate: "host" (the default) or "device": this rank's reads inflated by the engine's
     BGZF inflater.  decode: "host" (the default) or "device": this rank's stage tables built by the
     engine's record unpacker (pipeline.consensus_pipeline's options); see _sharded_pipeline."""
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
+    if bgzf_effort not in (1, 2):
+        raise ValueError("bgzf_effort must be 1 or 2")
+    if bgzf_effort != 1 and bgzf != "device":
+        raise ValueError('bgzf_effort=2 needs bgzf="device"')
     if inflate not in ("host", "device"):
         raise ValueError('inflate must be "host" or "device"')
     if decode not in ("host", "device"):
@@ -636,13 +640,15 @@ def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|
         was_dec = engine.device_decode(True)
         try:
             return sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
-                                    blocks, held, refs, keep, finalize, timings, cuts, bgzf, inflate)
+                                    blocks, held, refs, keep, finalize, timings, cuts, bgzf, inflate,
+                                    bgzf_effort=bgzf_effort)
         finally:
             engine.device_decode(was_dec)
     if bgzf == "host" and inflate == "host":
         return _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
                                  blocks, held, refs, keep, finalize, timings, cuts)
-    was = engine.device_bgzf(True) if bgzf == "device" else None
+    was_effort = engine.bgzf_effort
+    was = engine.device_bgzf(True, effort=bgzf_effort) if bgzf == "device" else None
     try:
         was_in = engine.device_inflate(True) if inflate == "device" else None
         try:
@@ -653,7 +659,7 @@ def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|
                 engine.device_inflate(was_in)
     finally:
         if was is not None:
-            engine.device_bgzf(was)
+            engine.device_bgzf(was, effort=was_effort)
 
 
 def _sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose, blocks, held,

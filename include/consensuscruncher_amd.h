@@ -366,6 +366,14 @@ int64_t cc_bgzf_deflate(cc_ctx *ctx, const uint8_t *data, uint64_t n, uint8_t *s
                         uint32_t *out_len, int64_t cap);
 /* the pair to hand to ccio_set_deflate_hook; unset the hook before cc_destroy */
 int cc_bgzf_hook(cc_ctx *ctx, ccio_deflate_fn *fn, void **user);
+/* The encoder's effort: 1 (the default: one candidate per hash from earlier 512-position tiles, a
+ * greedy parse) or 2 (buckets of the four most recent positions per hash, entered 64 positions at a
+ * time so that a position also sees its own tile, and a one-step lazy parse: smaller members, a
+ * slower kernel, one workgroup per CU).  Anything else is CC_E_INVALID and changes nothing.  The
+ * setting holds for later cc_bgzf_deflate calls and hook rounds of this context; a round that is
+ * running finishes at the effort it started with (the call waits for it).  Either effort gives the
+ * same members for the same bytes on every call. */
+int cc_bgzf_set_effort(cc_ctx *ctx, int effort);
 /* Raw DEFLATE members inflated on the device (k_bgzf_inflate: one wave per member, many members in
  * flight; the decode tables, a ring of the compressed bytes and the last 32 KiB of output live in
  * LDS).  Member j is comp[coff[j] .. coff[j] + clen[j]) and must inflate to exactly ulen[j] bytes,
