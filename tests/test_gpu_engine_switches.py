@@ -6,8 +6,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-# CC_QDIG_BITS=10 keeps 10 bits of the tables' qname digests: the seeded keys collide everywhere, the
-# pass meets EB_COLLISION and re-runs on the full qname hash (read_bam_run)
+# CC_QDIG_BITS=10 keeps 10 bits of the tables' qname digests: the seeded keys collide everywhere.  Two
+# found pairs with one key first send the pass to the sort path (EB_NEEDSORT); k_pair_mark's qname
+# compare meets EB_COLLISION there, and the pass re-runs on the full qname hash (read_bam_run)
 SWITCHES = [("CC_PC_TILE", "1024"), ("CC_PC_TILE", "512"), ("CC_RESID_SORT", "1"), ("CC_SCAN1", "1"),
             ("CC_SCAN1", "0"), ("CC_QDIG", "0"), ("CC_QDIG_BITS", "10"), ("CC_DCS_PER_ENTRY", "1"),
             ("CC_LP_MIN", "0"), ("CC_GROUP_STAGED", "1"),
