@@ -62,7 +62,7 @@ static std::atomic<long long> g_launches{0};
 enum : uint32_t {
     EB_COLLISION = 1u << 0,
     EB_DUP_QNAME = 1u << 1,
-    EB_AMBIGUOUS = 1u << 2,
+    // (bit 2 is unused)
     EB_N_HIGHQ = 1u << 3,
     EB_BAD_BASE = 1u << 4,
     EB_SHORT = 1u << 5,
@@ -1527,7 +1527,7 @@ __device__ __forceinline__ uint64_t bloom_bits(uint64_t k) {
 __device__ __forceinline__ uint64_t bloom_word(uint64_t k, uint64_t bmask) { return (k >> 24) & bmask; }
 
 struct EmitResid {   // residual entries (byte flags): key and stream slot compacted, table and filter
-    static constexpr bool kPlain = false;
+    static constexpr bool kPlain = false, kStaged = false;
     const uint64_t* skey;
     uint64_t* rk;
     uint32_t* rv;
@@ -4616,16 +4616,14 @@ __global__ __launch_bounds__(256) void k_q_pairs(int64_t Q, const int32_t* __res
 
 
 // ------------------------------------------------------------------ scans
-// Reduce-then-scan over u32 flags (sum, exclusive) or group starts (max, inclusive):
+// Reduce-then-scan (exclusive u32 sum) over u32 counts or byte flags:
 // 4096-element tiles staged through LDS so every global access is a coalesced 16-B
 // lane load/store; 12 B of HBM traffic per element (read, read, write) plus a tiny
 // pass over the per-tile partials, which also leaves the total on the device.
 constexpr int SCAN_T = 256, SCAN_I = 16, SCAN_TILE = SCAN_T * SCAN_I;
 
-template <bool MAX>
-__device__ __forceinline__ uint32_t sop(uint32_t a, uint32_t b) { return MAX ? (a > b ? a : b) : a + b; }
-
-// tile -> s_tile (coalesced), returns this thread's 16 contiguous elements
+// The tile load: this thread's 16 contiguous elements of the tile at base.
+// u32 input goes tile -> s_tile (coalesced) and ends behind a barrier
 __device__ __forceinline__ void scan_load_tile(const uint32_t* __restrict__ in, int64_t n, int64_t base,
                                                uint32_t* s_tile, uint32_t v[SCAN_I]) {
     const int tid = threadIdx.x;
@@ -4647,34 +4645,50 @@ __device__ __forceinline__ void scan_load_tile(const uint32_t* __restrict__ in, 
         v[4 * jj + 0] = q.x; v[4 * jj + 1] = q.y; v[4 * jj + 2] = q.z; v[4 * jj + 3] = q.w;
     }
 }
+// byte flags: one 16-B load (the thread's elements are contiguous), no LDS and no barrier
+__device__ __forceinline__ void scan_load_tile(const uint8_t* __restrict__ in, int64_t n, int64_t base,
+                                               uint32_t*, uint32_t v[SCAN_I]) {
+    const int tid = threadIdx.x;
+    if (base + SCAN_TILE <= n) {
+        const uint4 q = *reinterpret_cast<const uint4*>(in + base + tid * SCAN_I);
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < SCAN_I; ++k) v[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+    } else {
+#pragma unroll
+        for (int k = 0; k < SCAN_I; ++k) {
+            const int64_t i = base + tid * SCAN_I + k;
+            v[k] = i < n ? (uint32_t)in[i] : 0u;
+        }
+    }
+}
 
-template <bool MAX>
 __device__ __forceinline__ uint32_t block_scan_excl(uint32_t x, uint32_t* s_w, uint32_t* tot) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     uint32_t inc = x;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const uint32_t y = __shfl_up(inc, o, 64);
-        if (lane >= o) inc = sop<MAX>(inc, y);
+        if (lane >= o) inc += y;
     }
     if (lane == 63) s_w[w] = inc;
     __syncthreads();
     uint32_t pre = 0, all = 0;
 #pragma unroll
     for (int j = 0; j < SCAN_T / 64; ++j) {
-        if (j < w) pre = sop<MAX>(pre, s_w[j]);
-        all = sop<MAX>(all, s_w[j]);
+        if (j < w) pre += s_w[j];
+        all += s_w[j];
     }
     *tot = all;
     uint32_t ex = __shfl_up(inc, 1, 64);
     if (lane == 0) ex = 0;
-    return sop<MAX>(pre, ex);
+    return pre + ex;
 }
 
 // the sum of the 4 byte flags (0/1) of a word
 __device__ __forceinline__ uint32_t byte_sum(uint32_t w) { return (w * 0x01010101u) >> 24; }
 
-template <bool MAX, class TIn>
+template <class TIn>
 __global__ __launch_bounds__(SCAN_T) void k_scan_reduce(const TIn* __restrict__ in, int64_t n,
                                                         uint32_t* __restrict__ part) {
     __shared__ uint32_t s_w[SCAN_T / 64];
@@ -4682,7 +4696,6 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_reduce(const TIn* __restrict__ 
     const int tid = threadIdx.x;
     uint32_t acc = 0;
     if constexpr (sizeof(TIn) == 1) {
-        static_assert(!MAX, "byte flags are summed");
         // one 16-B load per thread (SCAN_I byte flags)
         if (base + SCAN_TILE <= n) {
             const uint4 q = *reinterpret_cast<const uint4*>(in + base + tid * SCAN_I);
@@ -4695,40 +4708,35 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_reduce(const TIn* __restrict__ 
 #pragma unroll
         for (int j = 0; j < SCAN_I / 4; ++j) {
             const uint4 q = *reinterpret_cast<const uint4*>(in + base + (j * SCAN_T + tid) * 4);
-            acc = sop<MAX>(acc, sop<MAX>(sop<MAX>(q.x, q.y), sop<MAX>(q.z, q.w)));
+            acc += (q.x + q.y) + (q.z + q.w);
         }
     } else {
         for (int o = tid; o < SCAN_TILE; o += SCAN_T)
-            if (base + o < n) acc = sop<MAX>(acc, in[base + o]);
+            if (base + o < n) acc += in[base + o];
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc = sop<MAX>(acc, __shfl_xor(acc, o, 64));
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if ((tid & 63) == 0) s_w[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) {
         uint32_t t = 0;
 #pragma unroll
-        for (int j = 0; j < SCAN_T / 64; ++j) t = sop<MAX>(t, s_w[j]);
+        for (int j = 0; j < SCAN_T / 64; ++j) t += s_w[j];
         part[blockIdx.x] = t;
     }
 }
 
-// out = exclusive prefix sum (MAX = false) or inclusive running max (MAX = true)
-// Scan outputs.  ScanStore writes the prefix array; the Emit* consumers take (i, prefix, value)
-// per element in the store phase instead, so a compaction needs neither the prefix array nor a
-// pass of its own.
-template <class E, class = void>
-struct is_staged { static constexpr bool value = false; };
-template <class E>
-struct is_staged<E, std::void_t<decltype(E::kStaged)>> { static constexpr bool value = E::kStaged; };
+// Scan outputs.  ScanStore writes the exclusive prefix array; the Emit* consumers take
+// (i, prefix, flag) per element in the store phase instead, so a compaction needs neither the
+// prefix array nor a pass of its own.  Emitters are fed byte flags.
 struct ScanStore {
-    static constexpr bool kPlain = true;
+    static constexpr bool kPlain = true, kStaged = false;
     uint32_t* out;
-    __device__ void operator()(int64_t, uint32_t, uint32_t) const {}
 };
 // Staged emitters (kStaged) split an element's work into ld1 (loads indexed by the element), ld2
 // (loads indexed by what ld1 read) and st (the stores), so the scan's store phase issues the loads
-// of all of a thread's elements before waiting on any of them (k_scan_down).
+// of all of a thread's elements before waiting on any of them (the scan kernels' store phase).  The others take
+// an element whole, in operator().
 struct EmitPairs {   // completed pairs (mate_of >= 0) in stream order of their second end: the two
                      // records, the completing region, and on a sorted table each record's read end
     static constexpr bool kPlain = false, kStaged = true;
@@ -4755,14 +4763,9 @@ struct EmitPairs {   // completed pairs (mate_of >= 0) in stream order of their 
         region[x] = l.reg < 0 ? -l.reg - 1 : l.reg;
         if (rec_e) { rec_e[l.a] = (int32_t)(2 * x); rec_e[l.b] = (int32_t)(2 * x + 1); }
     }
-    __device__ void operator()(int64_t i, uint32_t x, uint32_t f) const {
-        Ld l = ld1(i, f);
-        ld2(l, f);
-        st(i, x, f, l);
-    }
 };
 struct EmitFamStarts {   // each family's first slot, and per family the members dropped ("line read twice")
-    static constexpr bool kPlain = false;
+    static constexpr bool kPlain = false, kStaged = false;
     const uint32_t* validf;
     int32_t *fam_beg, *fam_drop;
     uint32_t* n_drop;
@@ -4791,14 +4794,9 @@ struct EmitCreation {   // family creation order (tag_dict insertion order), eac
         pair_by_k[x] = (int32_t)(i >> 1);   // i is the creating read end (fam_first)
         fsz[x] = l.n;
     }
-    __device__ void operator()(int64_t i, uint32_t x, uint32_t f) const {
-        Ld l = ld1(i, f);
-        ld2(l, f);
-        st(i, x, f, l);
-    }
 };
 struct EmitGather {   // out[x] = src[i] for the flagged i
-    static constexpr bool kPlain = false;
+    static constexpr bool kPlain = false, kStaged = false;
     const int32_t* src;
     int32_t* out;
     __device__ void operator()(int64_t i, uint32_t x, uint32_t f) const {
@@ -4818,13 +4816,9 @@ struct EmitVotePairs {   // the duplex votes' pairs {read1, read2, decision, ent
         vslot[i] = f ? (int32_t)x : -1;
         if (f) vpair[x] = make_int4(l.t, l.p, l.d, (int32_t)i);
     }
-    __device__ void operator()(int64_t i, uint32_t x, uint32_t f) const {
-        Ld l = ld1(i, f);
-        st(i, x, f, l);
-    }
 };
 struct EmitList {   // vote list of the flagged pairs and each pair's vote slot (-1: none)
-    static constexpr bool kPlain = false;
+    static constexpr bool kPlain = false, kStaged = false;
     int32_t *vslot, *list;
     __device__ void operator()(int64_t i, uint32_t x, uint32_t f) const {
         vslot[i] = f ? (int32_t)x : -1;
@@ -4852,16 +4846,38 @@ struct EmitEntries {   // csn_pair_dict entries in creation order: the family pa
         fam_o[f0] = (int32_t)(2 * r);
         if (f1 >= 0) fam_o[f1] = (int32_t)(2 * r + 1);
     }
-    __device__ void operator()(int64_t k, uint32_t r, uint32_t f) const {
-        Ld l = ld1(k, f);
-        ld2(l, f);
-        st(k, r, f, l);
-    }
 };
+
+// one element through an emitter (the partial tile's tail)
+template <class Emit>
+__device__ __forceinline__ void emit_one(const Emit& em, int64_t i, uint32_t x, uint32_t f) {
+    if constexpr (Emit::kStaged) {
+        typename Emit::Ld l = em.ld1(i, f);
+        em.ld2(l, f);
+        em.st(i, x, f, l);
+    } else {
+        em(i, x, f);
+    }
+}
+
+// The thread's sum of its elements, scanned over the block: its exclusive rank within the tile
+__device__ __forceinline__ uint32_t scan_tile_rank(const uint32_t v[SCAN_I], uint32_t* s_w, uint32_t* all) {
+    uint32_t t = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_I; ++k) t += v[k];
+    return block_scan_excl(t, s_w, all);
+}
+
+// The store phase of a tile stands in both kernels' bodies, line for line the same (SCAN STORE PHASE
+// below): v becomes each element's exclusive prefix, is transposed through s_tile, and goes to the
+// output array or through the emitter in coalesced order.  It is not a helper on purpose: behind a
+// function boundary (emitter by value or by reference, tile base or tile index, LDS pointer with or
+// without its address space) the staged emitters' kernels allocate 3-6 more VGPRs, and
+// k_scan_*<EmitVotePairs> drops from 5 to 4 waves per SIMD.  A change to one copy goes into the other.
 
 // The tile's carry-in is the reduction of the partials of the tiles before it (L2-resident, a
 // few KB), so no separate pass scans the partials; the last tile writes the total.
-template <bool MAX, class Emit, class TIn>
+template <class Emit, class TIn>
 __global__ __launch_bounds__(SCAN_T) void k_scan_down(const TIn* __restrict__ in, int64_t n,
                                                       const uint32_t* __restrict__ part,
                                                       uint32_t* __restrict__ total, Emit em) {
@@ -4871,43 +4887,27 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_down(const TIn* __restrict__ in
     const int64_t base = (int64_t)blockIdx.x * SCAN_TILE;
     const int tid = threadIdx.x;
     uint32_t pre = 0;
-    for (uint32_t i = tid; i < blockIdx.x; i += SCAN_T) pre = sop<MAX>(pre, part[i]);
+    for (uint32_t i = tid; i < blockIdx.x; i += SCAN_T) pre += part[i];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) pre = sop<MAX>(pre, __shfl_xor(pre, o, 64));
+    for (int o = 32; o > 0; o >>= 1) pre += __shfl_xor(pre, o, 64);
     if ((tid & 63) == 0) s_pre[tid >> 6] = pre;
     uint32_t v[SCAN_I];
-    if constexpr (sizeof(TIn) == 1) {
-        // the thread's 16 byte flags in one 16-B load (its elements are contiguous)
-        if (base + SCAN_TILE <= n) {
-            const uint4 q = *reinterpret_cast<const uint4*>(in + base + tid * SCAN_I);
-            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int k = 0; k < SCAN_I; ++k) v[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
-        } else {
-#pragma unroll
-            for (int k = 0; k < SCAN_I; ++k) {
-                const int64_t i = base + tid * SCAN_I + k;
-                v[k] = i < n ? (uint32_t)in[i] : 0u;
-            }
-        }
-        __syncthreads();   // publishes s_pre
-    } else {
-        scan_load_tile(in, n, base, s_tile, v);   // its barrier publishes s_pre too
-    }
+    scan_load_tile(in, n, base, s_tile, v);
+    if constexpr (sizeof(TIn) == 1) __syncthreads();   // publishes s_pre (the u32 load's own barrier does)
     pre = 0;
 #pragma unroll
-    for (int j = 0; j < SCAN_T / 64; ++j) pre = sop<MAX>(pre, s_pre[j]);
-    uint32_t t = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_I; ++k) t = sop<MAX>(t, v[k]);
+    for (int j = 0; j < SCAN_T / 64; ++j) pre += s_pre[j];
     uint32_t all;
-    uint32_t run = sop<MAX>(pre, block_scan_excl<MAX>(t, s_w, &all));
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) *total = sop<MAX>(pre, all);
+    const uint32_t rank = scan_tile_rank(v, s_w, &all);
+    uint32_t run = pre + rank;
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) *total = pre + all;
+    // ---- SCAN STORE PHASE (to the kernel's end)
+    static_assert(Emit::kPlain || sizeof(TIn) == 1, "emitters are fed byte flags");
 #pragma unroll
     for (int k = 0; k < SCAN_I; ++k) {
         const uint32_t x = v[k];
-        if (MAX) { run = sop<MAX>(run, x); v[k] = run; }
-        else { v[k] = run; run += x; }
+        v[k] = run;
+        run += x;
     }
 #pragma unroll
     for (int j = 0; j < SCAN_I / 4; ++j) {
@@ -4916,29 +4916,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_down(const TIn* __restrict__ in
     }
     __syncthreads();
     if (base + SCAN_TILE <= n) {
-#pragma unroll
-        for (int j = 0; j < SCAN_I / 4; ++j) {
-            const int o = (j * SCAN_T + tid) * 4;
-            const uint4 x = reinterpret_cast<const uint4*>(s_tile)[o >> 2];
-            if constexpr (Emit::kPlain) {
-                *reinterpret_cast<uint4*>(em.out + base + o) = x;
-            } else if constexpr (sizeof(TIn) == 1 && is_staged<Emit>::value) {
-                continue;   // (below: all of the thread's elements at once)
-            } else if constexpr (sizeof(TIn) == 1) {
-                const uint32_t f = *reinterpret_cast<const uint32_t*>(in + base + o);   // L2-resident
-                em(base + o, x.x, f & 0xffu);
-                em(base + o + 1, x.y, (f >> 8) & 0xffu);
-                em(base + o + 2, x.z, (f >> 16) & 0xffu);
-                em(base + o + 3, x.w, f >> 24);
-            } else {
-                const uint4 f = *reinterpret_cast<const uint4*>(in + base + o);   // L2-resident
-                em(base + o, x.x, f.x);
-                em(base + o + 1, x.y, f.y);
-                em(base + o + 2, x.z, f.z);
-                em(base + o + 3, x.w, f.w);
-            }
-        }
-        if constexpr (!Emit::kPlain && sizeof(TIn) == 1 && is_staged<Emit>::value) {
+        if constexpr (Emit::kStaged) {
             // the thread's 16 elements: every ld1, then every ld2, then the stores
             typename Emit::Ld ld[SCAN_I];
             uint32_t fx[SCAN_I], xx[SCAN_I];
@@ -4957,12 +4935,27 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_down(const TIn* __restrict__ in
             for (int e = 0; e < SCAN_I; ++e) em.ld2(ld[e], fx[e]);
 #pragma unroll
             for (int e = 0; e < SCAN_I; ++e) em.st(base + ((e >> 2) * SCAN_T + tid) * 4 + (e & 3), xx[e], fx[e], ld[e]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < SCAN_I / 4; ++j) {
+                const int o = (j * SCAN_T + tid) * 4;
+                const uint4 x = reinterpret_cast<const uint4*>(s_tile)[o >> 2];
+                if constexpr (Emit::kPlain) {
+                    *reinterpret_cast<uint4*>(em.out + base + o) = x;
+                } else {
+                    const uint32_t f = *reinterpret_cast<const uint32_t*>(in + base + o);   // L2-resident
+                    em(base + o, x.x, f & 0xffu);
+                    em(base + o + 1, x.y, (f >> 8) & 0xffu);
+                    em(base + o + 2, x.z, (f >> 16) & 0xffu);
+                    em(base + o + 3, x.w, f >> 24);
+                }
+            }
         }
     } else {
         for (int o = tid; o < SCAN_TILE; o += SCAN_T) {
             if (base + o >= n) continue;
             if constexpr (Emit::kPlain) em.out[base + o] = s_tile[o];
-            else em(base + o, s_tile[o], (uint32_t)in[base + o]);
+            else emit_one(em, base + o, s_tile[o], (uint32_t)in[base + o]);
         }
     }
 }
@@ -4985,7 +4978,7 @@ __device__ __forceinline__ void lb_publish(const ScanLB& lb, uint32_t tile, uint
     __hip_atomic_store(lb.st + tile, ((unsigned long long)lb.epoch << 34) | ((unsigned long long)kind << 32) | v,
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool MAX, class Emit, class TIn>
+template <class Emit, class TIn>
 __global__ __launch_bounds__(SCAN_T) void k_scan_one(const TIn* __restrict__ in, int64_t n, int64_t nb,
                                                      uint32_t* __restrict__ total, Emit em, ScanLB lb) {
     __shared__ uint32_t s_tile[SCAN_TILE];
@@ -5001,27 +4994,9 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_one(const TIn* __restrict__ in,
     const uint32_t b = s_id[0];
     const int64_t base = (int64_t)b * SCAN_TILE;
     uint32_t v[SCAN_I];
-    if constexpr (sizeof(TIn) == 1) {
-        if (base + SCAN_TILE <= n) {
-            const uint4 q = *reinterpret_cast<const uint4*>(in + base + tid * SCAN_I);
-            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int k = 0; k < SCAN_I; ++k) v[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
-        } else {
-#pragma unroll
-            for (int k = 0; k < SCAN_I; ++k) {
-                const int64_t i = base + tid * SCAN_I + k;
-                v[k] = i < n ? (uint32_t)in[i] : 0u;
-            }
-        }
-    } else {
-        scan_load_tile(in, n, base, s_tile, v);
-    }
-    uint32_t t = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_I; ++k) t = sop<MAX>(t, v[k]);
+    scan_load_tile(in, n, base, s_tile, v);
     uint32_t all;
-    uint32_t run = block_scan_excl<MAX>(t, s_w, &all);
+    const uint32_t rank = scan_tile_rank(v, s_w, &all);
     if (tid < 64) {
         uint32_t excl = 0;
         if (b == 0) {
@@ -5048,8 +5023,8 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_one(const TIn* __restrict__ in,
                 const int first = im ? __ffsll((unsigned long long)im) - 1 : 64;
                 uint32_t x = tid <= first ? val : 0u;
 #pragma unroll
-                for (int o = 32; o > 0; o >>= 1) x = sop<MAX>(x, __shfl_xor(x, o, 64));
-                excl = sop<MAX>(excl, x);
+                for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+                excl += x;
                 if (im) break;
                 j -= 64;
             }
@@ -5058,14 +5033,14 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_one(const TIn* __restrict__ in,
                 // (slow, always right), so the published prefixes and the pass's outputs stay exact
                 // and every later kernel of the pass sees consistent offsets; EB_SCANWAIT reports it
                 uint32_t x = 0;
-                for (int64_t i = tid; i < base; i += 64) x = sop<MAX>(x, (uint32_t)in[i]);
+                for (int64_t i = tid; i < base; i += 64) x += (uint32_t)in[i];
 #pragma unroll
-                for (int o = 32; o > 0; o >>= 1) x = sop<MAX>(x, __shfl_xor(x, o, 64));
+                for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
                 excl = x;
                 late = true;
             }
             if (tid == 0) {
-                lb_publish(lb, b, 2u, sop<MAX>(excl, all));
+                lb_publish(lb, b, 2u, excl + all);
                 if (late) atomicOr(lb.err, EB_SCANWAIT);
             }
         }
@@ -5073,13 +5048,15 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_one(const TIn* __restrict__ in,
     }
     __syncthreads();
     const uint32_t pre = s_id[1];
-    run = sop<MAX>(pre, run);
-    if ((int64_t)b == nb - 1 && tid == 0) *total = sop<MAX>(pre, all);
+    uint32_t run = pre + rank;
+    if ((int64_t)b == nb - 1 && tid == 0) *total = pre + all;
+    // ---- SCAN STORE PHASE (to the kernel's end)
+    static_assert(Emit::kPlain || sizeof(TIn) == 1, "emitters are fed byte flags");
 #pragma unroll
     for (int k = 0; k < SCAN_I; ++k) {
         const uint32_t x = v[k];
-        if (MAX) { run = sop<MAX>(run, x); v[k] = run; }
-        else { v[k] = run; run += x; }
+        v[k] = run;
+        run += x;
     }
 #pragma unroll
     for (int j = 0; j < SCAN_I / 4; ++j) {
@@ -5088,29 +5065,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_one(const TIn* __restrict__ in,
     }
     __syncthreads();
     if (base + SCAN_TILE <= n) {
-#pragma unroll
-        for (int j = 0; j < SCAN_I / 4; ++j) {
-            const int o = (j * SCAN_T + tid) * 4;
-            const uint4 x = reinterpret_cast<const uint4*>(s_tile)[o >> 2];
-            if constexpr (Emit::kPlain) {
-                *reinterpret_cast<uint4*>(em.out + base + o) = x;
-            } else if constexpr (sizeof(TIn) == 1 && is_staged<Emit>::value) {
-                continue;   // (below: all of the thread's elements at once)
-            } else if constexpr (sizeof(TIn) == 1) {
-                const uint32_t f = *reinterpret_cast<const uint32_t*>(in + base + o);   // L2-resident
-                em(base + o, x.x, f & 0xffu);
-                em(base + o + 1, x.y, (f >> 8) & 0xffu);
-                em(base + o + 2, x.z, (f >> 16) & 0xffu);
-                em(base + o + 3, x.w, f >> 24);
-            } else {
-                const uint4 f = *reinterpret_cast<const uint4*>(in + base + o);   // L2-resident
-                em(base + o, x.x, f.x);
-                em(base + o + 1, x.y, f.y);
-                em(base + o + 2, x.z, f.z);
-                em(base + o + 3, x.w, f.w);
-            }
-        }
-        if constexpr (!Emit::kPlain && sizeof(TIn) == 1 && is_staged<Emit>::value) {
+        if constexpr (Emit::kStaged) {
             // the thread's 16 elements: every ld1, then every ld2, then the stores
             typename Emit::Ld ld[SCAN_I];
             uint32_t fx[SCAN_I], xx[SCAN_I];
@@ -5129,12 +5084,27 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_one(const TIn* __restrict__ in,
             for (int e = 0; e < SCAN_I; ++e) em.ld2(ld[e], fx[e]);
 #pragma unroll
             for (int e = 0; e < SCAN_I; ++e) em.st(base + ((e >> 2) * SCAN_T + tid) * 4 + (e & 3), xx[e], fx[e], ld[e]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < SCAN_I / 4; ++j) {
+                const int o = (j * SCAN_T + tid) * 4;
+                const uint4 x = reinterpret_cast<const uint4*>(s_tile)[o >> 2];
+                if constexpr (Emit::kPlain) {
+                    *reinterpret_cast<uint4*>(em.out + base + o) = x;
+                } else {
+                    const uint32_t f = *reinterpret_cast<const uint32_t*>(in + base + o);   // L2-resident
+                    em(base + o, x.x, f & 0xffu);
+                    em(base + o + 1, x.y, (f >> 8) & 0xffu);
+                    em(base + o + 2, x.z, (f >> 16) & 0xffu);
+                    em(base + o + 3, x.w, f >> 24);
+                }
+            }
         }
     } else {
         for (int o = tid; o < SCAN_TILE; o += SCAN_T) {
             if (base + o >= n) continue;
             if constexpr (Emit::kPlain) em.out[base + o] = s_tile[o];
-            else em(base + o, s_tile[o], (uint32_t)in[base + o]);
+            else emit_one(em, base + o, s_tile[o], (uint32_t)in[base + o]);
         }
     }
 }
@@ -5626,7 +5596,7 @@ void flush_prof(cc_ctx* ctx) {
     ctx->pending.clear();
 }
 
-template <bool MAX, class Emit, class TIn>
+template <class Emit, class TIn>
 int scan_launch(cc_ctx* ctx, const TIn* in, int64_t n, uint32_t* d_tot, const char* name, Emit em);
 
 // Stable sort of n (key, value) pairs by whole 8-bit digits of the key (k_rs_hist / scan / k_rs_scatter
@@ -5674,7 +5644,7 @@ int sort_pairs(cc_ctx* ctx, const uint64_t* kin, uint64_t* kout, const uint32_t*
         uint64_t* dk = ((passes - p) & 1) ? kout : tk;
         uint32_t* dv = ((passes - p) & 1) ? vout : tv;
         hipLaunchKernelGGL(k_rs_hist, dim3((unsigned)nt), dim3(RS_T), 0, ctx->stream, sk, n, shift, hist, nt);
-        RC(scan_launch<false>(ctx, (const uint32_t*)hist, (int64_t)RS_BINS * nt, tot, "sort_scan", ScanStore{off}));
+        RC(scan_launch(ctx, (const uint32_t*)hist, (int64_t)RS_BINS * nt, tot, "sort_scan", ScanStore{off}));
         hipLaunchKernelGGL(k_rs_scatter, dim3((unsigned)nt), dim3(RS_T), 0, ctx->stream, sk, sv, n, shift,
                            (const uint32_t*)off, nt, dk, dv);
         sk = dk;
@@ -5690,7 +5660,7 @@ int sort_pairs(cc_ctx* ctx, const uint64_t* kin, uint64_t* kout, const uint32_t*
 // of a 20 M-entry scan costs more than the second pass over L2-resident flags), C5 1.612 -> 1.596 ms
 // (profiles/r04_scan1_*).
 constexpr int64_t SCAN_ONE_MAX = 64;
-template <bool MAX, class Emit, class TIn>
+template <class Emit, class TIn>
 int scan_launch(cc_ctx* ctx, const TIn* in, int64_t n, uint32_t* d_tot, const char* name, Emit em) {
     const int64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
     uintptr_t al = (uintptr_t)in;
@@ -5718,7 +5688,7 @@ int scan_launch(cc_ctx* ctx, const TIn* in, int64_t n, uint32_t* d_tot, const ch
         }
         const ScanLB lb{ctx->scan_st, ctx->scan_ticket, ctx->scan_epoch, ctx->d_err, ctx->scan_spin_max};
         ProfScope ps(ctx, name);
-        hipLaunchKernelGGL((k_scan_one<MAX, Emit, TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, nb,
+        hipLaunchKernelGGL((k_scan_one<Emit, TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, nb,
                            d_tot, em, lb);
         return 0;
     }
@@ -5726,8 +5696,8 @@ int scan_launch(cc_ctx* ctx, const TIn* in, int64_t n, uint32_t* d_tot, const ch
     uint32_t* part = (uint32_t*)tmp_storage(ctx, (size_t)nb * 4 + 64, &rc);
     if (!part) return rc;
     ProfScope ps(ctx, name);
-    hipLaunchKernelGGL((k_scan_reduce<MAX, TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, part);
-    hipLaunchKernelGGL((k_scan_down<MAX, Emit, TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, part, d_tot, em);
+    hipLaunchKernelGGL((k_scan_reduce<TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, part);
+    hipLaunchKernelGGL((k_scan_down<Emit, TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, part, d_tot, em);
     return 0;
 }
 
@@ -5817,28 +5787,21 @@ int planned_total(cc_ctx* ctx, Group& g, PT id, uint32_t* d_tot, int64_t* total)
     return 0;
 }
 
-// exclusive scan of u32 or byte flags with a planned total (the total's name is the scan's profile scope)
+// exclusive scan with a planned total (the total's name is the scan's profile scope) of byte flags
+// consumed by an emitter (compaction in the scan's store phase), or of u32 or byte flags into ScanStore
 // (byte inputs are flags, 0 or 1: k_scan_reduce sums a word's four bytes with byte_sum, exact only below 256)
-template <class TIn>
-int scan_total(cc_ctx* ctx, Group& g, const TIn* in, uint32_t* out, int64_t n, int64_t* total, PT id) {
-    if (n <= 0) { *total = 0; return 0; }
-    int rc = 0;
-    uint32_t* d_tot = plan_slot(ctx, g, id, &rc);
-    if (rc) return rc;
-    RC(scan_launch<false>(ctx, in, n, d_tot, PLAN_NAME[(int)id], ScanStore{out}));
-    return planned_total(ctx, g, id, d_tot, total);
-}
-
-// exclusive scan of u32 or byte flags consumed by an emitter (compaction in the scan's store phase)
-// (byte inputs are flags, 0 or 1, as for scan_total)
 template <class Emit, class TIn>
 int scan_emit(cc_ctx* ctx, Group& g, const TIn* in, int64_t n, int64_t* total, PT id, Emit em) {
     if (n <= 0) { *total = 0; return 0; }
     int rc = 0;
     uint32_t* d_tot = plan_slot(ctx, g, id, &rc);
     if (rc) return rc;
-    RC(scan_launch<false>(ctx, in, n, d_tot, PLAN_NAME[(int)id], em));
+    RC(scan_launch(ctx, in, n, d_tot, PLAN_NAME[(int)id], em));
     return planned_total(ctx, g, id, d_tot, total);
+}
+template <class TIn>
+int scan_total(cc_ctx* ctx, Group& g, const TIn* in, uint32_t* out, int64_t n, int64_t* total, PT id) {
+    return scan_emit(ctx, g, in, n, total, id, ScanStore{out});
 }
 
 // End of a stage pass: ONE readback of the error word, the read_bam counters (optional) and the
@@ -5948,7 +5911,6 @@ int err_code(cc_ctx* ctx, uint32_t bits) {
     if (!bits) return 0;
     if (bits & EB_COLLISION) { ctx->err = "64-bit key hash collision (retry with another seed)"; return CC_E_COLLISION; }
     if (bits & EB_KEYERROR) { ctx->err = "KeyError: read_dict[tag] already deleted (consensus_helper.py:490 with overlapping bed regions, or DCS_maker.py:258 with duplex keys that are not mutual)"; return CC_E_KEYERROR; }
-    if (bits & EB_AMBIGUOUS) { ctx->err = "duplex keys are not mutual or span regions; reference outcome is order-dependent"; return CC_E_AMBIGUOUS; }
     if (bits & EB_N_HIGHQ) { ctx->err = "IndexError: N base with quality >= 30 in a family of size >= 2 (SSCS_maker.py:129)"; return CC_E_N_HIGHQ; }
     if (bits & EB_SHORT) { ctx->err = "IndexError: read shorter than the consensus length"; return CC_E_SHORT_READ; }
     if (bits & EB_BAD_BASE) { ctx->err = "ValueError: base outside ACGTN in a voted family (SSCS_maker.py:122)"; return CC_E_BAD_BASE; }
@@ -6087,6 +6049,45 @@ void duplex_vote(cc_ctx* ctx, int32_t mode, int64_t n, const int4* vpair, const 
     const int32_t fpw = 64 / chunks;
     hipLaunchKernelGGL(k_duplex_vote_swar, dim3(nblk((n + fpw - 1) / fpw, 4)), dim3(256), 0, ctx->stream, n, mode, fpw,
                        chunks, vpair, TA, TB, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
+}
+
+// What the two duplex stages (DCS, singleton correction) share.  Their head: the error word cleared,
+// the barcode swap table uploaded, and per entry end (Q of them) the decision, the two records and
+// the vote flag (FL: the stage's own flag buffer) that the stage's decide kernel fills.
+struct DuplexBufs {
+    int32_t *d_swap, *dec, *t_rec, *p_rec;
+    uint8_t* fl;
+};
+template <B FL>
+int duplex_head(cc_ctx* ctx, Group& g, const int32_t* bc_swap, int32_t n_bc, int64_t Q, DuplexBufs* d) {
+    int brc = 0;
+    g.Q = Q;
+    HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
+    d->d_swap = GB(bc_swap, std::max(n_bc, 1));
+    RC(upload_swap(ctx, g, d->d_swap, bc_swap, n_bc));
+    d->dec = GB(dec, Q);
+    d->t_rec = GB(t_rec, Q);
+    d->p_rec = GB(p_rec, Q);
+    d->fl = gbuf<FL>(ctx, g, (Q + 15) & ~15LL, &brc);   // byte flags (16-B padded for the scan)
+    return brc;
+}
+// Their tail: the flagged ends compacted into vote pairs (the scan `id`) and voted between the
+// tables of the two sides (mode as duplex_vote's).
+int duplex_tail(cc_ctx* ctx, Group& g, const DuplexBufs& d, int64_t Q, PT id, int32_t mode, const DevTable& TA,
+                const DevTable& TB) {
+    int brc = 0;
+    int64_t NV = 0;
+    int32_t* vslot = GB(vslot, Q);
+    int4* vpair = GB(vpair, Q);   // capacity; sized NV below
+    RC(scan_emit(ctx, g, (const uint8_t*)d.fl, Q, &NV, id, EmitVotePairs{d.t_rec, d.p_rec, d.dec, vslot, vpair}));
+    g.NV = NV;
+    const int32_t ml = std::max(TA.max_len, TB.max_len);
+    const int32_t qstride = (int32_t)((ml + 15) & ~15);
+    uint8_t* cons_seq = GB(cons_seq, NV * (qstride / 2));
+    uint8_t* cons_qual = GB(cons_qual, NV * qstride);
+    int32_t* vmeta = GB(vote_meta, 5 * NV);
+    duplex_vote(ctx, mode, NV, vpair, TA, TB, ml, qstride, cons_seq, cons_qual, vmeta);
+    return 0;
 }
 
 }  // namespace
@@ -6338,9 +6339,8 @@ extern "C" {
 
 // test hook: scan_launch itself on the caller's input, with the engine's own consumers (the header has
 // the kinds).  It reaches k_scan_reduce, k_scan_down and k_scan_one for u32 input with ScanStore and for
-// byte flags with ScanStore, an unstaged emitter (EmitList) and a staged one (EmitVotePairs).  It does
-// NOT reach scan_launch<true> (the running max) nor the u32-input emitter branch of the store phase:
-// the engine instantiates neither (every emitter call site passes byte flags), so no test covers them.
+// byte flags with ScanStore, an unstaged emitter (EmitList) and a staged one (EmitVotePairs): every
+// path of the store phase (an emitter fed u32 input does not compile).
 int cc_debug_scan(cc_ctx* ctx, int32_t kind, int32_t engine, const void* in, int64_t n, const int32_t* aux,
                   void* out_a, void* out_b, int64_t* total) {
     if (!ctx) return CC_E_INVALID;
@@ -6364,13 +6364,13 @@ int cc_debug_scan(cc_ctx* ctx, int32_t kind, int32_t engine, const void* in, int
     RC(dbg_words(ctx, bufs, &d_tot, 4, 0u));
     HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
     if (n > 0) {   // (n == 0: no launch, as scan_total / scan_emit)
-        if (kind == 0) RC(scan_launch<false>(ctx, (const uint32_t*)d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
-        if (kind == 1) RC(scan_launch<false>(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
+        if (kind == 0) RC(scan_launch(ctx, (const uint32_t*)d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
+        if (kind == 1) RC(scan_launch(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
         if (kind == 2)
-            RC(scan_launch<false>(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan", EmitList{(int32_t*)d_a, (int32_t*)d_b}));
+            RC(scan_launch(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan", EmitList{(int32_t*)d_a, (int32_t*)d_b}));
         if (kind == 3)
-            RC(scan_launch<false>(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan",
-                                  EmitVotePairs{d_aux, d_aux + n, d_aux + 2 * n, (int32_t*)d_a, (int4*)d_b}));
+            RC(scan_launch(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan",
+                           EmitVotePairs{d_aux, d_aux + n, d_aux + 2 * n, (int32_t*)d_a, (int4*)d_b}));
     }
     uint32_t* h_tot = (uint32_t*)ctx->h_pinned;
     HIPCHK(hipMemcpyAsync(out_a, d_a, sizeof(uint32_t) * (size_t)(n + DBG_TAIL), hipMemcpyDeviceToHost, ctx->stream));
@@ -7054,7 +7054,7 @@ int ReadBamPass::pairing() {
             hipLaunchKernelGGL(k_lp_hist, dim3(LP_NB), dim3(LP_T), 0, ctx->stream, (const uint64_t*)pkeys,
                                (const uint32_t*)pcount, pcap, hist);
         }
-        RC(scan_launch<false>(ctx, (const uint32_t*)hist, (int64_t)LP_BUCKETS * LP_NB, lp_tot, "k_lp_check",
+        RC(scan_launch(ctx, (const uint32_t*)hist, (int64_t)LP_BUCKETS * LP_NB, lp_tot, "k_lp_check",
                               ScanStore{off}));
         ProfScope pl(ctx, "k_lp_check");
         hipLaunchKernelGGL(k_lp_scatter, dim3(LP_NB), dim3(LP_T), 0, ctx->stream, (const uint64_t*)pkeys,
@@ -7661,14 +7661,10 @@ int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, i
         const DevTable& T = ctx->tables[g.table];
         int brc = 0;
         const int64_t Q = 2 * g.E;
-        g.Q = Q;
-        HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
-        int32_t* d_swap = GB(bc_swap, std::max(n_bc, 1));
-        RC(upload_swap(ctx, g, d_swap, bc_swap, n_bc));
-        int32_t* dec = GB(dec, Q);
-        int32_t* t_rec = GB(t_rec, Q);
-        int32_t* p_rec = GB(p_rec, Q);
-        uint8_t* fl_dcs = GB(fl_dcs, (Q + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+        DuplexBufs d;
+        RC(duplex_head<B::fl_dcs>(ctx, g, bc_swap, n_bc, Q, &d));
+        int32_t *const d_swap = d.d_swap, *const dec = d.dec, *const t_rec = d.t_rec, *const p_rec = d.p_rec;
+        uint8_t* const fl_dcs = d.fl;
         if (!g.local_groups) RC(build_ht(ctx, g));   // duplex partners are found among position-group neighbours
         RC(ensure_fam_tags(ctx, g));
         GroupView G = view_of(g);
@@ -7689,16 +7685,7 @@ int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, i
                                (const int32_t*)dec, fdel);
             RC(deleted_late(ctx, g, fdel));
         }
-        int64_t NV = 0;
-        int32_t* vslot = GB(vslot, Q);
-        int4* vpair = GB(vpair, Q);   // capacity; sized NV below
-        RC(scan_emit(ctx, g, (const uint8_t*)fl_dcs, Q, &NV, PT::scan_dcs, EmitVotePairs{t_rec, p_rec, dec, vslot, vpair}));
-        g.NV = NV;
-        const int32_t qstride = (int32_t)((T.max_len + 15) & ~15);
-        uint8_t* cons_seq = GB(cons_seq, NV * (qstride / 2));
-        uint8_t* cons_qual = GB(cons_qual, NV * qstride);
-        int32_t* vmeta = GB(vote_meta, 5 * NV);
-        duplex_vote(ctx, 0, NV, vpair, T, T, T.max_len, qstride, cons_seq, cons_qual, vmeta);
+        RC(duplex_tail(ctx, g, d, Q, PT::scan_dcs, 0, T, T));
         uint32_t bits = 0;
         bool plan_ok = true;
         RC(finish_pass(ctx, g, &bits, false, &plan_ok));
@@ -7724,14 +7711,10 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
         const DevTable& TB = ctx->tables[s.table];
         int brc = 0;
         const int64_t Q = 2 * g.E;
-        g.Q = Q;
-        HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
-        int32_t* d_swap = GB(bc_swap, std::max(n_bc, 1));
-        RC(upload_swap(ctx, g, d_swap, bc_swap, n_bc));
-        int32_t* dec = GB(dec, Q);
-        int32_t* t_rec = GB(t_rec, Q);
-        int32_t* p_rec = GB(p_rec, Q);
-        uint8_t* fl = GB(fl_corr, (Q + 15) & ~15LL);   // byte flags (16-B padded for the scan)
+        DuplexBufs d;
+        RC(duplex_head<B::fl_corr>(ctx, g, bc_swap, n_bc, Q, &d));
+        int32_t *const d_swap = d.d_swap, *const dec = d.dec, *const t_rec = d.t_rec, *const p_rec = d.p_rec;
+        uint8_t* const fl = d.fl;
         // tables with deep position groups (targeted panels, C4: hundreds of families at a position)
         // look families up by hash instead of walking a position group's neighbours / bucket
         const bool deep_g = TA.n_deep > 0, deep_s = TB.n_deep > 0;
@@ -7769,17 +7752,7 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
             RC(deleted_late(ctx, g, gdel));
             if (s.F > 0) RC(deleted_late(ctx, s, sdel));
         }
-        int64_t NV = 0;
-        int32_t* vslot = GB(vslot, Q);
-        int4* vpair = GB(vpair, Q);   // capacity; sized NV below
-        RC(scan_emit(ctx, g, (const uint8_t*)fl, Q, &NV, PT::scan_sc, EmitVotePairs{t_rec, p_rec, dec, vslot, vpair}));
-        g.NV = NV;
-        const int32_t ml = std::max(TA.max_len, TB.max_len);
-        const int32_t qstride = (int32_t)((ml + 15) & ~15);
-        uint8_t* cons_seq = GB(cons_seq, NV * (qstride / 2));
-        uint8_t* cons_qual = GB(cons_qual, NV * qstride);
-        int32_t* vmeta = GB(vote_meta, 5 * NV);
-        duplex_vote(ctx, 1, NV, vpair, TA, TB, ml, qstride, cons_seq, cons_qual, vmeta);
+        RC(duplex_tail(ctx, g, d, Q, PT::scan_sc, 1, TA, TB));
         // names: consensus tag of the singleton entry + ':1' (singleton_correction.py:286)
         int32_t* q_pair = GB(q_pair, Q);
         int32_t* q_ckey = GB(q_ckey, 9 * Q);

@@ -251,8 +251,8 @@ int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint
                                d_rf, T, sz16, sz8, d_st);
             HIPCHK(hipGetLastError());
         }
-        RC(scan_launch<false>(ctx, (const uint32_t*)sz16, n, &d_st->tot16, "unpack_scan_pay", ScanStore{off16}));
-        RC(scan_launch<false>(ctx, (const uint32_t*)sz8, n, &d_st->tot8, "unpack_scan_qn", ScanStore{off8}));
+        RC(scan_launch(ctx, (const uint32_t*)sz16, n, &d_st->tot16, "unpack_scan_pay", ScanStore{off16}));
+        RC(scan_launch(ctx, (const uint32_t*)sz8, n, &d_st->tot8, "unpack_scan_qn", ScanStore{off8}));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_st, d_st, sizeof(UnpackStatus), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -13,7 +13,8 @@ LIBDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 
 CC_E = {
     -1: "CC_E_INVALID", -2: "CC_E_HIP", -3: "CC_E_N_HIGHQ", -4: "CC_E_BAD_BASE", -5: "CC_E_SHORT_READ",
-    -6: "CC_E_NO_QUAL", -7: "CC_E_NO_CIGAR", -8: "CC_E_DUP_QNAME", -9: "CC_E_AMBIGUOUS",
+    -6: "CC_E_NO_QUAL", -7: "CC_E_NO_CIGAR", -8: "CC_E_DUP_QNAME",
+    -9: "CC_E_AMBIGUOUS",   # retired: never returned, the number stays reserved
     -10: "CC_E_COLLISION", -11: "CC_E_UNSUPPORTED", -12: "CC_E_KEYERROR",
     -13: "CC_E_REPLAY",
 }

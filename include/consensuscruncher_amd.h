@@ -49,7 +49,8 @@ extern "C" {
 #define CC_E_NO_QUAL -6        /* qualities absent ('*') in a voted read (TypeError) */
 #define CC_E_NO_CIGAR -7       /* infer_query_length() is None (TypeError) */
 #define CC_E_DUP_QNAME -8      /* (no longer returned: qnames seen more than twice pair in stream order) */
-#define CC_E_AMBIGUOUS -9      /* one consensus tag created in two regions (tags of one pair completing apart) */
+#define CC_E_AMBIGUOUS -9      /* (retired, never returned: the region loops' deletions are followed; the
+                                  number stays reserved) */
 #define CC_E_COLLISION -10     /* internal 64-bit hash collision (callers retry with another seed) */
 #define CC_E_UNSUPPORTED -11
 #define CC_E_KEYERROR -12      /* the reference raises KeyError (DCS_maker.py:258: read_dict[duplex] deleted,
@@ -434,10 +435,9 @@ int cc_debug_poison(cc_ctx *ctx, int32_t group_id, const char *name, int64_t byt
  * back whole, so every element behind the last one written (out_a from n, out_b from total) must
  * still hold that word.  n == 0 launches nothing and returns total 0.  *total receives the scan's
  * total.  A look-back that waited past its bound is reported as CC_E_INVALID (no re-run).
- * Not reached by this hook, because the engine never instantiates them: scan_launch<true> (the
- * inclusive running max) and the store phase's branch for emitters fed uint32 input (every emitter
- * call site passes byte flags; uint32 input only meets ScanStore).  EmitList has no call site but
- * this one: the engine's other unstaged emitters (EmitGather, EmitFamStarts, ...) share its branch. */
+ * These four kinds are every path of the scan: it is an exclusive sum only, and an emitter fed uint32
+ * input does not compile (uint32 input only meets ScanStore).  EmitList has no call site but this
+ * one: the engine's other unstaged emitters (EmitGather, EmitFamStarts, ...) share its path. */
 int cc_debug_scan(cc_ctx *ctx, int32_t kind, int32_t engine, const void *in, int64_t n, const int32_t *aux,
                   void *out_a, void *out_b, int64_t *total);
 /* test hook: the engine's stable LSD radix sort (sort_pairs: k_rs_hist, the scan, k_rs_scatter per 8-bit

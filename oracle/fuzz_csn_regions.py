@@ -1,6 +1,7 @@
-"""Search for the input the engine fences with CC_E_AMBIGUOUS: one consensus tag (csn_pair_dict key)
-created in two bed regions by different pairs (consensus_helper.py:455-489 with the SSCS region loop,
-SSCS_maker.py:265-339, which emits and deletes the first region's entry).
+"""Search for inputs with one consensus tag (csn_pair_dict key) created in two bed regions by
+different pairs (consensus_helper.py:455-489 with the SSCS region loop, SSCS_maker.py:265-339, which
+emits and deletes the first region's entry).  The engine once fenced these with CC_E_AMBIGUOUS; that
+code is retired, and the engine now follows the reference's region loops on them.
 
 TEST INFRASTRUCTURE ONLY (CPU, the pinned Python oracle).  Small seeded samples with overlapping random
 bed regions on one contig, qnames seen three and four times (synth dupq_frac) and shared consensus

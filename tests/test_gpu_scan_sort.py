@@ -4,8 +4,9 @@ test hooks cc_debug_scan / cc_debug_sort_pairs, at sizes chosen for the code's o
 (4096), the 64-tile look-back window, the default engine's switch at 64 tiles, a last tile of one
 element, a digit histogram of more than one scan tile.  Every comparison is exact integer equality.
 
-Not covered (the engine instantiates neither): scan_launch<true> (the running max) and the store
-phase's branch for emitters fed uint32 input."""
+The hook's four kinds reach every path of the store phase (the scan is an exclusive sum only, and an
+emitter fed uint32 input does not compile), through one unstaged and one staged emitter: not every
+instantiation the engine makes."""
 import functools
 
 import numpy as np
