@@ -611,7 +611,7 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
         return CC_E_INVALID;
     }
     if (E->broken) return CC_E_HIP;
-    BGCHK(hipSetDevice(ctx->device));
+    BGCHK(hipSetDevice(ctx->device));   // (not enter(): a writer's thread, the switches are the engine thread's)
     if (!E->ready) RC(bgzf_init(E));
     const bool prof = ctx->profiling;
     const auto kernel = E->effort == 2 ? k_bgzf_deflate<2> : k_bgzf_deflate<1>;   // the whole round at one effort
@@ -627,10 +627,10 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
         if (prof) BGCHK(hipEventRecord(E->ev[b][3], E->st[b]));
         E->timed[b] = prof;
         if (prof) BGCHK(hipEventRecord(E->ev[b][0], E->st[b]));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)pc), dim3(BG_T), 0, E->st[b], E->d_in[b], (uint64_t)bytes, E->d_tok[b],
-                           E->d_out[b], E->d_len[b]);
+        klaunch(E->st[b], kernel, (unsigned)pc, BG_T, E->d_in[b], (uint64_t)bytes, E->d_tok[b], E->d_out[b],
+                E->d_len[b]);
         if (prof) BGCHK(hipEventRecord(E->ev[b][1], E->st[b]));
-        hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)pc), dim3(256), 0, E->st[b], E->d_out[b], E->d_len[b], E->d_pack[b]);
+        klaunch(E->st[b], k_bgzf_pack, (unsigned)pc, 256, E->d_out[b], E->d_len[b], E->d_pack[b]);
         BGCHK(hipGetLastError());
         BGCHK(hipMemcpyAsync(E->h_len[b], E->d_len[b], (size_t)pc * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[b]));
         return 0;

@@ -265,7 +265,7 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
         return CC_E_INVALID;
     }
     if (E->broken) return CC_E_HIP;
-    BGCHK(hipSetDevice(ctx->device));
+    BGCHK(hipSetDevice(ctx->device));   // (not enter(): a reader's thread, the switches are the engine thread's)
     if (!E->dec) E->dec = new BgzfDec();
     BgzfDec* D = E->dec;
     if (!D->ready) RC(bgzf_dec_init(E, D));
@@ -311,8 +311,7 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
         BGCHK(hipMemcpyAsync(D->d_desc[b], D->h_desc[b], (size_t)n * sizeof(uint4), hipMemcpyHostToDevice, E->st[b]));
         if (prof) BGCHK(hipEventRecord(D->ev[b][3], E->st[b]));
         if (prof) BGCHK(hipEventRecord(D->ev[b][0], E->st[b]));
-        hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)n), dim3(BI_T), 0, E->st[b], D->d_in[b], D->d_desc[b], D->d_out[b],
-                           D->d_ok[b], n);
+        klaunch(E->st[b], k_bgzf_inflate, (unsigned)n, BI_T, D->d_in[b], D->d_desc[b], D->d_out[b], D->d_ok[b], n);
         BGCHK(hipGetLastError());
         if (prof) BGCHK(hipEventRecord(D->ev[b][1], E->st[b]));
         if (prof) BGCHK(hipEventRecord(D->ev[b][4], E->st[b]));

@@ -4,15 +4,24 @@
 // over struct-of-arrays records resident in HBM.  The reference's sequential
 // dictionary program (consensus_helper.read_bam, consensus_helper.py:308-506,
 // and the stage loops of SSCS_maker.py:272-346, DCS_maker.py:210-282,
-// singleton_correction.py:209-319) is restated as sort/scan/segment steps:
+// singleton_correction.py:209-319) is restated as search/rank/scan/segment steps.  read_bam as it runs
+// by default, on a coordinate-sorted table (its fallbacks to the right):
 //
-//   read_bam    k_classify   filters of consensus_helper.py:404-420 + counters
-//               radix sort   (qname hash, stream pos)      -> pair_dict by qname (:426-432)
-//               k_pair_mark  runs of equal qname -> pairs completed at the 2nd mate
-//               k_pair_keys  which_read/which_strand/cigar_order/sscs_qname/unique_tag (:57-305)
-//               radix sort   (tag hash, read-end index)     -> read_dict / tag_dict (:455-494)
-//               k_fam_*      families, members in completion order, "line read twice" drop
-//               radix sort   (consensus-tag hash, creation) -> csn_pair_dict (:469-489)
+//   read_bam    k_build_meta_cls4  the table's preparation fused with the filters of
+//                                  consensus_helper.py:404-420 + counters (a bed stream: k_build_meta, k_classify)
+//               k_pair_coord_tile  mates by coordinates, a tile of records per block -> pair_dict (:426-432);
+//                                  deep position groups bisected by qname (k_deep_qsort), the reads left over
+//                                  paired through a table (k_pair_resid, k_resid_*).  Fallback (unsorted table,
+//                                  a qname seen 3+ times): radix sort by (qname hash, stream pos), k_pair_mark
+//               k_pair_keys        which_read/which_strand/cigar_order/sscs_qname/unique_tag (:57-305)
+//               k_group_rank       read ends ranked by tag inside their position group -> read_dict / tag_dict
+//                                  (:455-494); deep groups in place (k_deep_count / _fam / _emit / _sortfam).
+//                                  Fallback (unsorted table, a deep group past its table): radix sort by
+//                                  (tag hash, read-end index), k_fam_mark
+//               k_fam_build        families, members in completion order, "line read twice" drop; their starts
+//                                  and creation order by scans
+//               k_csn_fast         csn_pair_dict (:469-489) through a hash table.  Fallback (two pairs share
+//                                  an entry): radix sort by (consensus-tag hash, creation), k_csn_mark
 //   SSCS        k_sscs_vote_swar consensus_maker (SSCS_maker.py:81-168) fused with read_mode /
 //                            consensus_flag (consensus_helper.py:509-565)
 //   DCS         k_dcs_decide duplex_tag hash-join + the duplex_dict rule (DCS_maker.py:245-282)
@@ -42,19 +51,14 @@
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "../../include/consensuscruncher_amd.h"
 
 // every device operation this library enqueues is counted (cc_launch_count: the bench's launches
-// per step): kernel launches, memsets, async copies, and each rocPRIM call once
+// per step): kernel launches (klaunch), memsets and async copies
 static std::atomic<long long> g_launches{0};
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kernelName, ...)                                                          \
-    do {                                                                                            \
-        g_launches.fetch_add(1, std::memory_order_relaxed);                                         \
-        hipLaunchKernelGGLInternal((kernelName), __VA_ARGS__);                                      \
-    } while (0)
 #define hipMemsetAsync(...) (g_launches.fetch_add(1, std::memory_order_relaxed), ::hipMemsetAsync(__VA_ARGS__))
 #define hipMemcpyAsync(...) (g_launches.fetch_add(1, std::memory_order_relaxed), ::hipMemcpyAsync(__VA_ARGS__))
 
@@ -5389,7 +5393,7 @@ inline int name_id(const NameIndex& ix, const char* name) {
 }
 
 // The engine's environment switches ("Engine switches"): every one there is, read by
-// read_switches() at the top of each entry point that uses one (per call: a test changes them between
+// enter() at the top of each entry point that enqueues work (per call: a test changes them between
 // runs on one live engine).  None changes an output.
 struct EngineSwitches {
     int scan1 = -1;                // CC_SCAN1=1 / 0: every scan as one look-back launch / as reduce-then-scan
@@ -5437,7 +5441,7 @@ struct cc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
-    EngineSwitches sw;              // as the entry point now running read them (read_switches), not kept across calls
+    EngineSwitches sw;              // as the entry point now running read them (enter), not kept across calls
     std::map<int32_t, DevTable> tables;
     std::map<int32_t, std::vector<void*>> table_allocs;
     std::map<int32_t, std::unique_ptr<Group>> groups;
@@ -5488,7 +5492,28 @@ namespace {
         if (rc_) return rc_;      \
     } while (0)
 
+// The prologue of every entry point that enqueues work: the context's device made current and the
+// engine switches read (per call: a test changes them between runs on one live engine).
+int enter(cc_ctx* ctx) {
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
+    return 0;
+}
+
 inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+
+// Every kernel launch of the library: counted (cc_launch_count) and enqueued on the context's stream, or
+// on the stream given (the BGZF coders launch on their own).  The arguments reach the kernel's
+// parameters by ordinary call conversion: a pointer of the wrong type does not compile.
+template <class... P, class... A>
+inline void klaunch(hipStream_t stream, void (*kernel)(P...), dim3 grid, dim3 block, A&&... args) {
+    g_launches.fetch_add(1, std::memory_order_relaxed);
+    kernel<<<grid, block, 0, stream>>>(std::forward<A>(args)...);
+}
+template <class... P, class... A>
+inline void klaunch(cc_ctx* ctx, void (*kernel)(P...), dim3 grid, dim3 block, A&&... args) {
+    klaunch(ctx->stream, kernel, grid, block, std::forward<A>(args)...);
+}
 
 // fills gathered for one k_fill launch (flushed when full or by launch())
 struct Fills {
@@ -5581,6 +5606,13 @@ struct ProfScope {
     }
 };
 
+// a launch that is a timing scope of its own (scopes do not nest: never inside an open ProfScope)
+template <class... P, class... A>
+inline void klaunch(cc_ctx* ctx, const char* scope, void (*kernel)(P...), dim3 grid, dim3 block, A&&... args) {
+    ProfScope ps(ctx, scope);
+    klaunch(ctx->stream, kernel, grid, block, std::forward<A>(args)...);
+}
+
 void flush_prof(cc_ctx* ctx) {
     if (ctx->pending.empty()) return;
     (void)hipStreamSynchronize(ctx->stream);
@@ -5643,10 +5675,9 @@ int sort_pairs(cc_ctx* ctx, const uint64_t* kin, uint64_t* kout, const uint32_t*
         // the last pass lands in kout / vout; the passes alternate between them and the ping-pong pair
         uint64_t* dk = ((passes - p) & 1) ? kout : tk;
         uint32_t* dv = ((passes - p) & 1) ? vout : tv;
-        hipLaunchKernelGGL(k_rs_hist, dim3((unsigned)nt), dim3(RS_T), 0, ctx->stream, sk, n, shift, hist, nt);
-        RC(scan_launch(ctx, (const uint32_t*)hist, (int64_t)RS_BINS * nt, tot, "sort_scan", ScanStore{off}));
-        hipLaunchKernelGGL(k_rs_scatter, dim3((unsigned)nt), dim3(RS_T), 0, ctx->stream, sk, sv, n, shift,
-                           (const uint32_t*)off, nt, dk, dv);
+        klaunch(ctx, k_rs_hist, (unsigned)nt, RS_T, sk, n, shift, hist, nt);
+        RC(scan_launch(ctx, hist, (int64_t)RS_BINS * nt, tot, "sort_scan", ScanStore{off}));
+        klaunch(ctx, k_rs_scatter, (unsigned)nt, RS_T, sk, sv, n, shift, off, nt, dk, dv);
         sk = dk;
         sv = dv;
     }
@@ -5687,17 +5718,15 @@ int scan_launch(cc_ctx* ctx, const TIn* in, int64_t n, uint32_t* d_tot, const ch
             ctx->scan_epoch = 1;
         }
         const ScanLB lb{ctx->scan_st, ctx->scan_ticket, ctx->scan_epoch, ctx->d_err, ctx->scan_spin_max};
-        ProfScope ps(ctx, name);
-        hipLaunchKernelGGL((k_scan_one<Emit, TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, nb,
-                           d_tot, em, lb);
+        klaunch(ctx, name, k_scan_one<Emit, TIn>, (unsigned)nb, SCAN_T, in, n, nb, d_tot, em, lb);
         return 0;
     }
     int rc = 0;
     uint32_t* part = (uint32_t*)tmp_storage(ctx, (size_t)nb * 4 + 64, &rc);
     if (!part) return rc;
     ProfScope ps(ctx, name);
-    hipLaunchKernelGGL((k_scan_reduce<TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, part);
-    hipLaunchKernelGGL((k_scan_down<Emit, TIn>), dim3((unsigned)nb), dim3(SCAN_T), 0, ctx->stream, in, n, part, d_tot, em);
+    klaunch(ctx, k_scan_reduce<TIn>, (unsigned)nb, SCAN_T, in, n, part);
+    klaunch(ctx, k_scan_down<Emit, TIn>, (unsigned)nb, SCAN_T, in, n, part, d_tot, em);
     return 0;
 }
 
@@ -5741,7 +5770,7 @@ int dbg_fault(cc_ctx* ctx) {
 int Fills::launch() {
     if (fs.k == 0) return 0;
     const unsigned blocks = std::min<unsigned>(nblk((maxw + 3) / 4), 2048u);
-    hipLaunchKernelGGL(k_fill, dim3(blocks), dim3(256), 0, ctx->stream, fs);
+    klaunch(ctx, k_fill, blocks, 256, fs);
     fs.k = 0;
     maxw = 0;
     return hipGetLastError() == hipSuccess ? 0 : CC_E_HIP;
@@ -5819,10 +5848,9 @@ int finish_pass(cc_ctx* ctx, Group& g, uint32_t* bits, bool counters, bool* plan
         d.bad_listed = g.counters[CC_CNT_BAD_LISTED] > 0;
         uint8_t* dh = ctx->d_defer + (size_t)d.slot * DEFER_SLOT_BYTES;
         const bool totals = !g.verify.empty();
-        hipLaunchKernelGGL(k_defer_pack, dim3(1), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_err,
-                           counters ? (const unsigned long long*)ctx->d_cnt : nullptr,
-                           totals ? g.ptr<B::plan_totals>() : nullptr, PLAN_SLOTS,
-                           g.stripes_pending ? g.ptr<B::plan_stripes>() : nullptr, dh);
+        klaunch(ctx, k_defer_pack, 1, 256, ctx->d_err, counters ? ctx->d_cnt : nullptr,
+                totals ? g.ptr<B::plan_totals>() : nullptr, PLAN_SLOTS,
+                g.stripes_pending ? g.ptr<B::plan_stripes>() : nullptr, dh);
         g.stripes_pending = false;
         if (totals)
             for (const PT id : g.verify) d.expect.push_back({(int)id, g.plan[(int)id]});
@@ -5833,15 +5861,14 @@ int finish_pass(cc_ctx* ctx, Group& g, uint32_t* bits, bool counters, bool* plan
         return 0;
     }
     uint8_t* h = (uint8_t*)ctx->h_pinned;
-    hipLaunchKernelGGL(k_guard_fold, dim3(1), dim3(64), 0, ctx->stream, ctx->d_err);
+    klaunch(ctx, k_guard_fold, 1, 64, ctx->d_err);
     HIPCHK(hipMemcpyAsync(h + 16, ctx->d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (counters)
         HIPCHK(hipMemcpyAsync(h + 1024, ctx->d_cnt, sizeof(unsigned long long) * CC_NUM_COUNTERS * CNT_STRIPES,
                               hipMemcpyDeviceToHost,
                               ctx->stream));
     if (g.stripes_pending) {
-        hipLaunchKernelGGL(k_stripe_fold, dim3(1), dim3(64), 0, ctx->stream, g.ptr<B::plan_stripes>(),
-                           g.ptr<B::plan_totals>(), PLAN_SLOTS);
+        klaunch(ctx, k_stripe_fold, 1, 64, g.ptr<B::plan_stripes>(), g.ptr<B::plan_totals>(), PLAN_SLOTS);
         g.stripes_pending = false;
     }
     if (!g.verify.empty())
@@ -5900,7 +5927,7 @@ int run_planned(cc_ctx* ctx, Group& g, Stage stage, Pass pass) {
 
 int read_err(cc_ctx* ctx, uint32_t* bits) {
     uint32_t* h = (uint32_t*)ctx->h_pinned + 4;
-    hipLaunchKernelGGL(k_guard_fold, dim3(1), dim3(64), 0, ctx->stream, ctx->d_err);
+    klaunch(ctx, k_guard_fold, 1, 64, ctx->d_err);
     HIPCHK(hipMemcpyAsync(h, ctx->d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(stream_wait(ctx));
     *bits = *h;
@@ -5926,6 +5953,17 @@ int err_code(cc_ctx* ctx, uint32_t bits) {
     return CC_E_INVALID;
 }
 
+// The end the three stage calls share: the pass's one readback, CC_E_PLAN when a planned total did not
+// hold (run_planned re-runs exactly), else the stage's output count and the error word's code.
+int finish_stage(cc_ctx* ctx, Group& g, int64_t* n_out, int64_t n) {
+    uint32_t bits = 0;
+    bool plan_ok = true;
+    RC(finish_pass(ctx, g, &bits, false, &plan_ok));
+    if (!plan_ok) return CC_E_PLAN;
+    if (n_out) *n_out = n;
+    return err_code(ctx, bits);
+}
+
 template <typename T>
 int upload(cc_ctx* ctx, std::vector<void*>& allocs, T** dst, const T* src, int64_t count) {
     size_t bytes = (size_t)std::max<int64_t>(count, 1) * sizeof(T);
@@ -5935,13 +5973,20 @@ int upload(cc_ctx* ctx, std::vector<void*>& allocs, T** dst, const T* src, int64
     return 0;
 }
 
-#define GB(name, count) gbuf<B::name>(ctx, g, count, &brc); if (brc) return brc
+// A group buffer of `count` elements as one expression: its typed pointer, or the enclosing function
+// returns the allocation's error (ctx, g and the status brc are the caller's names).
+#define GB(name, count)                                  \
+    ({                                                   \
+        auto* gb_ = gbuf<B::name>(ctx, g, count, &brc);  \
+        if (brc) return brc;                             \
+        gb_;                                             \
+    })
 
 // k_deleted_late over group g's families (fam_del: the region each was deleted in)
 int deleted_late(cc_ctx* ctx, Group& g, const int32_t* fdel) {
     if (g.F <= 0) return 0;
-    hipLaunchKernelGGL(k_deleted_late, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F, fdel, g.ptr<B::fam_beg>(),
-                       g.ptr<B::fam_end>(), g.ptr<B::rs_val>(), g.ptr<B::pr_region>(), ctx->d_err);
+    klaunch(ctx, k_deleted_late, nblk(g.F), 256, g.F, fdel, g.ptr<B::fam_beg>(), g.ptr<B::fam_end>(),
+            g.ptr<B::rs_val>(), g.ptr<B::pr_region>(), ctx->d_err);
     return 0;
 }
 
@@ -5953,11 +5998,8 @@ int build_ht(cc_ctx* ctx, Group& g) {
     unsigned long long* key = GB(ht_key, (int64_t)size);
     int32_t* val = GB(ht_val, (int64_t)size);
     HIPCHK(hipMemsetAsync(key, 0xff, sizeof(unsigned long long) * size, ctx->stream));
-    if (g.F > 0) {
-        ProfScope ps(ctx, "k_ht_insert");
-        hipLaunchKernelGGL(k_ht_insert, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F,
-                           g.ptr<B::fam_hash>(), key, val, g.ht_mask);
-    }
+    if (g.F > 0)
+        klaunch(ctx, "k_ht_insert", k_ht_insert, nblk(g.F), 256, g.F, g.ptr<B::fam_hash>(), key, val, g.ht_mask);
     return 0;
 }
 
@@ -5983,12 +6025,9 @@ int ensure_fam_tags(cc_ctx* ctx, Group& g) {
     TagKey* fam_tag = GB(fam_tag, g.F);
     int32_t* fam_rec = GB(fam_rec, g.F);
     g.fam_tags_built = true;
-    if (g.F > 0) {
-        ProfScope ps(ctx, "k_fam_tags");
-        hipLaunchKernelGGL(k_fam_tags, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F,
-                           g.ptr<B::fam_first>(), g.ptr<B::fam_beg>(), g.ptr<B::mem_rec>(), pair_view(g),
-                           ctx->tables[g.table], fam_tag, fam_rec);
-    }
+    if (g.F > 0)
+        klaunch(ctx, "k_fam_tags", k_fam_tags, nblk(g.F), 256, g.F, g.ptr<B::fam_first>(), g.ptr<B::fam_beg>(),
+                g.ptr<B::mem_rec>(), pair_view(g), ctx->tables[g.table], fam_tag, fam_rec);
     return 0;
 }
 
@@ -6024,14 +6063,9 @@ int build_fam_buckets(cc_ctx* ctx, Group& g, GroupView* v, bool* ok) {
     if (!g.local_groups || !g.coord_sorted) return 0;   // the table's buckets were built by g's pass
     int brc = 0;
     int32_t* fbkt = GB(fam_bkt, T.bkt_cap);
-    {
-        // the table's bucket geometry from each tid's extent (k_derive)
-        ProfScope ps(ctx, "k_bucket_geom");
-        hipLaunchKernelGGL(k_bucket_geom, dim3(1), dim3(BG_T), 0, ctx->stream, T.n, T.ntid, (const int32_t*)T.ext,
-                           T.tbase, T.geom);
-    }
-    hipLaunchKernelGGL(k_fam_bucket, dim3(nblk(g.F + 1)), dim3(256), 0, ctx->stream, g.F,
-                       g.ptr<B::fam_tag>(), T.tbase, T.ntid, T.geom, fbkt);
+    // the table's bucket geometry from each tid's extent (k_derive)
+    klaunch(ctx, "k_bucket_geom", k_bucket_geom, 1, BG_T, T.n, T.ntid, T.ext, T.tbase, T.geom);
+    klaunch(ctx, k_fam_bucket, nblk(g.F + 1), 256, g.F, g.ptr<B::fam_tag>(), T.tbase, T.ntid, T.geom, fbkt);
     v->fbkt = fbkt;
     v->tbase = T.tbase;
     v->ntid = T.ntid;
@@ -6044,11 +6078,10 @@ int build_fam_buckets(cc_ctx* ctx, Group& g, GroupView* v, bool* ok) {
 void duplex_vote(cc_ctx* ctx, int32_t mode, int64_t n, const int4* vpair, const DevTable& TA, const DevTable& TB,
                  int32_t ml, int32_t qstride, uint8_t* cons_seq, uint8_t* cons_qual, int32_t* vmeta) {
     if (n <= 0) return;
-    ProfScope ps(ctx, mode ? "k_duplex_vote_sc" : "k_duplex_vote_dcs");
     const int32_t chunks = std::min(64, std::max(1, (ml + SV_POS - 1) / SV_POS));   // lanes per output
     const int32_t fpw = 64 / chunks;
-    hipLaunchKernelGGL(k_duplex_vote_swar, dim3(nblk((n + fpw - 1) / fpw, 4)), dim3(256), 0, ctx->stream, n, mode, fpw,
-                       chunks, vpair, TA, TB, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
+    klaunch(ctx, mode ? "k_duplex_vote_sc" : "k_duplex_vote_dcs", k_duplex_vote_swar, nblk((n + fpw - 1) / fpw, 4), 256,
+            n, mode, fpw, chunks, vpair, TA, TB, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
 }
 
 // What the two duplex stages (DCS, singleton correction) share.  Their head: the error word cleared,
@@ -6079,7 +6112,7 @@ int duplex_tail(cc_ctx* ctx, Group& g, const DuplexBufs& d, int64_t Q, PT id, in
     int64_t NV = 0;
     int32_t* vslot = GB(vslot, Q);
     int4* vpair = GB(vpair, Q);   // capacity; sized NV below
-    RC(scan_emit(ctx, g, (const uint8_t*)d.fl, Q, &NV, id, EmitVotePairs{d.t_rec, d.p_rec, d.dec, vslot, vpair}));
+    RC(scan_emit(ctx, g, d.fl, Q, &NV, id, EmitVotePairs{d.t_rec, d.p_rec, d.dec, vslot, vpair}));
     g.NV = NV;
     const int32_t ml = std::max(TA.max_len, TB.max_len);
     const int32_t qstride = (int32_t)((ml + 15) & ~15);
@@ -6266,6 +6299,7 @@ int cc_commit(cc_ctx* ctx) {
 // planned pass may read past what its kernels wrote: the guards' test)
 int cc_debug_poison(cc_ctx* ctx, int32_t group_id, const char* name, int64_t bytes, int32_t value) {
     if (!ctx || !name || !ctx->groups.count(group_id) || bytes < 0) return CC_E_INVALID;
+    RC(enter(ctx));
     Group& g = *ctx->groups[group_id];
     const int id = name_id(BUF_IDS, name);
     if (id < 0 || !g.buf[id].p) { ctx->err = std::string("no buffer named ") + name; return CC_E_INVALID; }
@@ -6349,7 +6383,7 @@ int cc_debug_scan(cc_ctx* ctx, int32_t kind, int32_t engine, const void* in, int
         ctx->err = "cc_debug_scan: kind 0..3, engine -1..1, 0 <= n < 2^31 - 65, and the arrays of the kind";
         return CC_E_INVALID;
     }
-    HIPCHK(hipSetDevice(ctx->device));
+    RC(enter(ctx));
     DbgSwitches sw{ctx, ctx->sw};
     ctx->sw.scan1 = engine;
     DbgBufs bufs;
@@ -6364,12 +6398,12 @@ int cc_debug_scan(cc_ctx* ctx, int32_t kind, int32_t engine, const void* in, int
     RC(dbg_words(ctx, bufs, &d_tot, 4, 0u));
     HIPCHK(hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
     if (n > 0) {   // (n == 0: no launch, as scan_total / scan_emit)
-        if (kind == 0) RC(scan_launch(ctx, (const uint32_t*)d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
-        if (kind == 1) RC(scan_launch(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
+        if (kind == 0) RC(scan_launch(ctx, (const uint32_t*)d_in /* picks TIn */, n, d_tot, "debug_scan", ScanStore{d_a}));
+        if (kind == 1) RC(scan_launch(ctx, d_in, n, d_tot, "debug_scan", ScanStore{d_a}));
         if (kind == 2)
-            RC(scan_launch(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan", EmitList{(int32_t*)d_a, (int32_t*)d_b}));
+            RC(scan_launch(ctx, d_in, n, d_tot, "debug_scan", EmitList{(int32_t*)d_a, (int32_t*)d_b}));
         if (kind == 3)
-            RC(scan_launch(ctx, (const uint8_t*)d_in, n, d_tot, "debug_scan",
+            RC(scan_launch(ctx, d_in, n, d_tot, "debug_scan",
                            EmitVotePairs{d_aux, d_aux + n, d_aux + 2 * n, (int32_t*)d_a, (int4*)d_b}));
     }
     uint32_t* h_tot = (uint32_t*)ctx->h_pinned;
@@ -6390,7 +6424,7 @@ int cc_debug_sort_pairs(cc_ctx* ctx, int32_t engine, const uint64_t* keys, const
         ctx->err = "cc_debug_sort_pairs: engine -1..1, 0 <= n < 2^31 - 65, begin_bit <= end_bit <= 64, and the arrays";
         return CC_E_INVALID;
     }
-    HIPCHK(hipSetDevice(ctx->device));
+    RC(enter(ctx));
     DbgSwitches sw{ctx, ctx->sw};
     ctx->sw.scan1 = engine;
     DbgBufs bufs;
@@ -6436,9 +6470,7 @@ int derive_table(cc_ctx* ctx, DevTable& T) {
     if (T.n <= 0) return 0;
     // (the tid extents were zeroed at upload: a step rewrites the same values)
     HIPCHK(hipMemsetAsync(T.ndeep, 0, 16, ctx->stream));
-    ProfScope ps(ctx, "k_derive");
-    hipLaunchKernelGGL(k_derive<false>, dim3(nblk(T.n, GT)), dim3(GT), 0, ctx->stream, T, T.dlist, T.ndeep,
-                       T.n / DEEP_MIN + 2, DeriveCls{});
+    klaunch(ctx, "k_derive", k_derive<false>, nblk(T.n, GT), GT, T, T.dlist, T.ndeep, T.n / DEEP_MIN + 2, DeriveCls{});
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -6457,7 +6489,7 @@ extern "C" {
 int cc_table_derive(cc_ctx* ctx, int32_t table_id) {
     if (!ctx || !ctx->tables.count(table_id)) return CC_E_INVALID;
     if (ctx->tables[table_id].host_layout) return 0;   // its derived columns are part of its input
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     if (ctx->sw.derive_separate) return derive_table(ctx, ctx->tables[table_id]);
     ctx->tables[table_id].derive_pending = true;   // (built by the next read_bam pass on the table)
     return 0;
@@ -6465,8 +6497,7 @@ int cc_table_derive(cc_ctx* ctx, int32_t table_id) {
 
 int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* table_id) {
     if (!ctx || !r || !table_id) return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     int32_t id = ctx->next_id++;
     std::vector<void*>& al = ctx->table_allocs[id];
     DevTable T;
@@ -6585,12 +6616,9 @@ namespace {
 int prep_table(cc_ctx* ctx, const DevTable& T, Fills& fill, int32_t* rec_e) {
     RC(fill.launch());
     if (T.n <= 0) return 0;
-    {
-        // (no deep-group list: that is the table's, listed by k_derive)
-        ProfScope ps(ctx, "k_build_meta");
-        hipLaunchKernelGGL(k_build_meta, dim3(nblk(T.n, BC_T)), dim3(BC_T), 0, ctx->stream, T, rec_e, ctx->d_err,
-                           (int32_t*)nullptr, (uint32_t*)nullptr, (int64_t)0);
-    }
+    // (no deep-group list: that is the table's, listed by k_derive)
+    klaunch(ctx, "k_build_meta", k_build_meta, nblk(T.n, BC_T), BC_T, T, rec_e, ctx->d_err, nullptr, nullptr,
+            (int64_t)0);
     // (the bucket geometry from each tid's extent: built by the SC join that uses it, build_fam_buckets)
     return 0;
 }
@@ -6610,6 +6638,7 @@ int cc_table_free(cc_ctx* ctx, int32_t id) {
 // test hook: one derived column of a table (its decoder-built or device-built layout), synchronously
 int64_t cc_table_fetch(cc_ctx* ctx, int32_t id, const char* name, void* dst, int64_t cap) {
     if (!ctx || !name || !ctx->tables.count(id)) return CC_E_INVALID;
+    RC(enter(ctx));
     RC(flush_derive(ctx, id));
     const DevTable& T = ctx->tables[id];
     const std::string nm(name);
@@ -6692,12 +6721,10 @@ int vote_families(cc_ctx* ctx, Group& g, const DevTable& T, int64_t NE, uint8_t*
         RC(fill.add(d_slow, 4, 0u));
         RC(fill.launch());
     }
-    if (NE > 0) {
-        ProfScope ps(ctx, "k_vote_plan");
-        hipLaunchKernelGGL(k_vote_plan, dim3(nblk(NE)), dim3(256), 0, ctx->stream, NE, g.R, NV, needv, vxs, emit_fam,
-                           (const int2*)emit_span, g.ptr<B::mem_meta>(), g.ptr<B::mem_rec>(), T, vote_fam,
-                           vote_order, emit_vslot, vmeta, d_slow, slow_list, d_nitems, all_slow, ctx->d_err);
-    }
+    if (NE > 0)
+        klaunch(ctx, "k_vote_plan", k_vote_plan, nblk(NE), 256, NE, g.R, NV, needv, vxs, emit_fam, emit_span,
+                g.ptr<B::mem_meta>(), g.ptr<B::mem_rec>(), T, vote_fam, vote_order, emit_vslot, vmeta, d_slow,
+                slow_list, d_nitems, all_slow, ctx->d_err);
     if (NV > 0) {
         int64_t NI = 0, NSL = 0;
         RC(planned_total(ctx, g, PT::vote_items, d_nitems, &NI));
@@ -6706,43 +6733,35 @@ int vote_families(cc_ctx* ctx, Group& g, const DevTable& T, int64_t NE, uint8_t*
             const bool fresh = !g.ptr<B::cutoff_thr>();
             int32_t* thr = GB(cutoff_thr, VOTE_BIGN + 1);
             if (fresh || g.thr_cutoff != cutoff) {   // the table depends on the cutoff alone
-                hipLaunchKernelGGL(k_cutoff_table, dim3(1), dim3(128), 0, ctx->stream, cutoff, thr);
+                klaunch(ctx, k_cutoff_table, 1, 128, cutoff, thr);
                 g.thr_cutoff = cutoff;
             }
             const int32_t fpw = 64 / chunks;
             const int64_t waves = (NV + fpw - 1) / fpw;
             const int32_t uni_ok = (1.0 >= cutoff) ? 1 : 0;   // count == pass: 1.0 >= cutoff in double
-            ProfScope ps(ctx, "k_sscs_vote_swar");
-            hipLaunchKernelGGL(k_sscs_vote_swar, dim3(nblk(waves, 4)), dim3(256), 0, ctx->stream, NV, fpw, chunks,
-                               vote_order, g.ptr<B::mem_meta>(), g.R, T, thr, uni_ok, qstride, cons_seq,
-                               cons_qual, ctx->d_err);
+            klaunch(ctx, "k_sscs_vote_swar", k_sscs_vote_swar, nblk(waves, 4), 256, NV, fpw, chunks, vote_order,
+                    g.ptr<B::mem_meta>(), g.R, T, thr, uni_ok, qstride, cons_seq, cons_qual, ctx->d_err);
         }
         const int64_t icap = NI > 0 ? NI : 1;
         int32_t* big_item = GB(vote_big_item, NV);
         int4* items = GB(vote_items, icap);
         uint8_t* partial = GB(vote_partial, icap * BIG_PL * (int64_t)qstride);
         uint32_t* item_fl = GB(vote_item_fl, icap);
-        if (NSL > 0) {
-            ProfScope ps(ctx, "k_big_items");
-            hipLaunchKernelGGL(k_big_items, dim3(64), dim3(256), 0, ctx->stream, d_slow, slow_list, vote_fam,
-                               g.ptr<B::fam_beg>(), g.ptr<B::fam_end>(), NI, d_items,
-                               big_item, items, ctx->d_err);
-        }
+        if (NSL > 0)
+            klaunch(ctx, "k_big_items", k_big_items, 64, 256, d_slow, slow_list, vote_fam, g.ptr<B::fam_beg>(),
+                    g.ptr<B::fam_end>(), NI, d_items, big_item, items, ctx->d_err);
         if (NI > 0) {
             const int32_t bch = std::min(64, std::max(1, (T.max_len + SV_POS - 1) / SV_POS));   // lanes per item
             const int32_t bfpw = 64 / bch;
-            ProfScope ps(ctx, "k_big_swar");
-            hipLaunchKernelGGL(k_big_swar, dim3(nblk((NI + bfpw - 1) / bfpw, 4)), dim3(256), 0, ctx->stream, d_items, NI,
-                               bfpw, bch, items, g.ptr<B::mem_meta>(), T, qstride, partial, item_fl,
-                               ctx->d_err);
+            klaunch(ctx, "k_big_swar", k_big_swar, nblk((NI + bfpw - 1) / bfpw, 4), 256, d_items, NI, bfpw, bch, items,
+                    g.ptr<B::mem_meta>(), T, qstride, partial, item_fl, ctx->d_err);
         }
-        ProfScope ps(ctx, "k_big_final");
+        ProfScope ps(ctx, "k_big_final");   // (recorded with or without the launch)
         if (NSL > 0)
-        hipLaunchKernelGGL(k_big_final, dim3(CC_BF_GRID), dim3(64), 0, ctx->stream, d_slow, slow_list, big_item, NI,
-                           vote_fam, g.ptr<B::fam_beg>(), g.ptr<B::fam_end>(), g.ptr<B::fam_n>(), g.ptr<B::mem_rec>(),
-                           g.ptr<B::mem_valid>(), g.ptr<B::mem_meta>(), T, cutoff,
-                           qstride, partial, (const uint32_t*)item_fl, qstride, cons_seq, cons_qual, vmeta,
-                           ctx->d_err);
+            klaunch(ctx, k_big_final, CC_BF_GRID, 64, d_slow, slow_list, big_item, NI, vote_fam, g.ptr<B::fam_beg>(),
+                    g.ptr<B::fam_end>(), g.ptr<B::fam_n>(), g.ptr<B::mem_rec>(), g.ptr<B::mem_valid>(),
+                    g.ptr<B::mem_meta>(), T, cutoff, qstride, partial, item_fl, qstride, cons_seq, cons_qual, vmeta,
+                    ctx->d_err);
     }
     *NV_out = NV;
     return 0;
@@ -6941,31 +6960,24 @@ int ReadBamPass::filters() {
         // the table's derived columns and this pass's preparation and filters in one kernel
         RC(fill.add(Tm.ndeep, 16, 0u));
         RC(fill.launch());
-        ProfScope ps(ctx, "k_derive");
-        hipLaunchKernelGGL(k_derive<true>, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, T, Tm.dlist, Tm.ndeep,
-                           N / DEEP_MIN + 2,
-                           DeriveCls{(const int32_t*)d_sreg, (const int32_t*)d_run, g.delim_filter, g.badread, g.scoped,
-                                     use_dig, g.seed, co, ctx->d_cnt, rec_e, ctx->d_err});
+        klaunch(ctx, "k_derive", k_derive<true>, nblk(N, GT), GT, T, Tm.dlist, Tm.ndeep, N / DEEP_MIN + 2,
+                DeriveCls{d_sreg, d_run, g.delim_filter, g.badread, g.scoped, use_dig, g.seed, co, ctx->d_cnt, rec_e,
+                          ctx->d_err});
         Tm.derive_pending = false;
     } else if (fused) {
         RC(fill.launch());
         ProfScope ps(ctx, "k_build_meta_cls");
         if (!sw.meta_scalar)
-            hipLaunchKernelGGL(k_build_meta_cls4, dim3(nblk(N, BC_T * BM4)), dim3(BC_T), 0, ctx->stream, T, rec_e,
-                               ctx->d_err, (const int32_t*)d_sreg, (const int32_t*)d_run, g.delim_filter, g.badread,
-                               g.scoped, g.seed, use_dig, co, ctx->d_cnt);
+            klaunch(ctx, k_build_meta_cls4, nblk(N, BC_T * BM4), BC_T, T, rec_e, ctx->d_err, d_sreg, d_run,
+                    g.delim_filter, g.badread, g.scoped, g.seed, use_dig, co, ctx->d_cnt);
         else
-            hipLaunchKernelGGL(k_build_meta_cls, dim3(nblk(N, BC_T)), dim3(BC_T), 0, ctx->stream, T, rec_e,
-                               ctx->d_err, (int32_t*)nullptr, (uint32_t*)nullptr, (int64_t)0, (const int32_t*)d_sreg,
-                               (const int32_t*)d_run, g.delim_filter, g.badread, g.scoped, g.seed, use_dig, co,
-                               ctx->d_cnt);
+            klaunch(ctx, k_build_meta_cls, nblk(N, BC_T), BC_T, T, rec_e, ctx->d_err, nullptr, nullptr, (int64_t)0,
+                    d_sreg, d_run, g.delim_filter, g.badread, g.scoped, g.seed, use_dig, co, ctx->d_cnt);
     } else {
         RC(prep_table(ctx, T, fill, rec_e));
-        if (S > 0) {
-            ProfScope ps(ctx, "k_classify");
-            hipLaunchKernelGGL(k_classify, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, g.ident, d_srec, d_sreg, d_run, T,
-                               g.delim_filter, g.badread, g.scoped, g.seed, use_dig, co, ctx->d_cnt);
-        }
+        if (S > 0)
+            klaunch(ctx, "k_classify", k_classify, nblk(S), 256, S, g.ident, d_srec, d_sreg, d_run, T, g.delim_filter,
+                    g.badread, g.scoped, g.seed, use_dig, co, ctx->d_cnt);
     }
     // the deep position groups' first records (T.dlist, T.ndeep): a property of the table's positions,
     // listed once at upload and every step (k_derive), for the per-group sorts
@@ -6988,10 +7000,8 @@ int ReadBamPass::pairing() {
     uint32_t* rv_app = nullptr;
     uint32_t* n_app = nullptr;
     {   // the coordinate search (one k_pair_coord scope from the tile search on)
-        if (!g.ident) {
-            ProfScope ps(ctx, "k_pair_coord");
-            hipLaunchKernelGGL(k_scatter_stream, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, g.ident, d_srec, skey, spos, rq);
-        }
+        if (!g.ident)
+            klaunch(ctx, "k_pair_coord", k_scatter_stream, nblk(S), 256, S, g.ident, d_srec, skey, spos, rq);
         const uint64_t* qk = g.ident ? (const uint64_t*)skey : (const uint64_t*)rq;
         // deep position groups: each group's records sorted by qname key (the search bisects there)
         uint64_t* gq = nullptr;
@@ -7011,10 +7021,8 @@ int ReadBamPass::pairing() {
             dgk = GB(deep_dgk, 2 * (int64_t)dgsize);
             RC(fill.add(dgk, sizeof(unsigned long long) * 2 * dgsize, 0xFFFFFFFEu));
             RC(fill.launch());
-            ProfScope pq(ctx, "k_deep_qsort");
-            hipLaunchKernelGGL(k_deep_qsort, dim3((unsigned)std::min<int64_t>(NDG, CC_DQ_GRID)), dim3(DQ_T), 0, ctx->stream,
-                               (const uint32_t*)T.ndeep, (const int32_t*)T.dlist, N, rkey, qk, gq, gend, boff, dgk,
-                               dgsize - 1, deep_gid);
+            klaunch(ctx, "k_deep_qsort", k_deep_qsort, (unsigned)std::min<int64_t>(NDG, CC_DQ_GRID), DQ_T, T.ndeep,
+                    T.dlist, N, rkey, qk, gq, gend, boff, dgk, dgsize - 1, deep_gid);
         }
         uint32_t* lst = plan_stripes(ctx, g, n_long, &brc);
         if (brc) return brc;
@@ -7024,12 +7032,10 @@ int ReadBamPass::pairing() {
         // records by k_scatter_stream (rq, and each record's stream slot spos)
         const bool small = sw.pc_tile ? sw.pc_tile == 512 : N < PC_SMALL_N;   // (CC_PC_TILE: measurements)
         const auto k_tile = small ? k_pair_coord_tile<512> : k_pair_coord_tile<1024>;
-        hipLaunchKernelGGL(k_tile, dim3(nblk(N, small ? 512 : 1024)), dim3(256), 0, ctx->stream, N, qk,
-                           g.ident ? (const int32_t*)nullptr : (const int32_t*)spos, rkey, T, partner, claims,
-                           mate_of, pflag, ltab, lsize - 1, lst, ctx->d_err, (const uint64_t*)gq,
-                           (const int32_t*)gend, (const uint32_t*)boff, (const unsigned long long*)dgk,
-                           dgsize - 1, pkeys, pcount, pcap);
-        hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, lst, n_long);
+        klaunch(ctx, k_tile, nblk(N, small ? 512 : 1024), 256, N, qk, g.ident ? nullptr : spos, rkey, T, partner,
+                claims, mate_of, pflag, ltab, lsize - 1, lst, ctx->d_err, gq, gend, boff, dgk, dgsize - 1, pkeys,
+                pcount, pcap);
+        klaunch(ctx, k_stripe_total, 1, 64, lst, n_long);
         uint32_t* st = plan_stripes(ctx, g, d_nresid, &brc);
         if (brc) return brc;
         // the residual keys appended as they are flagged (the table pairing's input without the scan)
@@ -7037,11 +7043,11 @@ int ReadBamPass::pairing() {
         rv_app = GB(pc_rv_app, S);
         n_app = plan_slot(ctx, g, PT::resid_app, &brc);   // (zeroed with the plan totals; not checked)
         if (brc) return brc;
-        hipLaunchKernelGGL(k_pair_resid, dim3((unsigned)((S + PD_TILE - 1) / PD_TILE)), dim3(256), 0, ctx->stream, S,
-                           skey, partner, claims, resid, st, ltab, lsize - 1, n_long, ctx->d_err, rk_app, rv_app, n_app);
+        klaunch(ctx, k_pair_resid, (unsigned)((S + PD_TILE - 1) / PD_TILE), 256, S, skey, partner, claims, resid, st,
+                ltab, lsize - 1, n_long, ctx->d_err, rk_app, rv_app, n_app);
         // a planned pass leaves the count striped: the end-of-pass check folds it (k_defer_pack)
         if (has_plan(g, PT::n_resid)) g.stripes_pending = true;
-        else hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, st, d_nresid);
+        else klaunch(ctx, k_stripe_total, 1, 64, st, d_nresid);
     }
     if (lpart) {   // the partitioned check for a qname in two found pairs
         uint32_t* hist = GB(lp_hist, (int64_t)LP_BUCKETS * LP_NB);
@@ -7049,18 +7055,11 @@ int ReadBamPass::pairing() {
         uint64_t* bkeys = GB(lp_bkeys, pcap);
         uint32_t* lp_tot = plan_slot(ctx, g, PT::lp_total, &brc);   // (the scan's total; not checked)
         if (brc) return brc;
-        {
-            ProfScope pl(ctx, "k_lp_check");
-            hipLaunchKernelGGL(k_lp_hist, dim3(LP_NB), dim3(LP_T), 0, ctx->stream, (const uint64_t*)pkeys,
-                               (const uint32_t*)pcount, pcap, hist);
-        }
-        RC(scan_launch(ctx, (const uint32_t*)hist, (int64_t)LP_BUCKETS * LP_NB, lp_tot, "k_lp_check",
-                              ScanStore{off}));
+        klaunch(ctx, "k_lp_check", k_lp_hist, LP_NB, LP_T, pkeys, pcount, pcap, hist);
+        RC(scan_launch(ctx, hist, (int64_t)LP_BUCKETS * LP_NB, lp_tot, "k_lp_check", ScanStore{off}));
         ProfScope pl(ctx, "k_lp_check");
-        hipLaunchKernelGGL(k_lp_scatter, dim3(LP_NB), dim3(LP_T), 0, ctx->stream, (const uint64_t*)pkeys,
-                           (const uint32_t*)pcount, pcap, (const uint32_t*)off, bkeys);
-        hipLaunchKernelGGL(k_lp_dups, dim3(LP_BUCKETS), dim3(LP_T), 0, ctx->stream, (const uint32_t*)pcount, pcap,
-                           (const uint32_t*)off, (const uint64_t*)bkeys, ctx->d_err);
+        klaunch(ctx, k_lp_scatter, LP_NB, LP_T, pkeys, pcount, pcap, off, bkeys);
+        klaunch(ctx, k_lp_dups, LP_BUCKETS, LP_T, pcount, pcap, off, bkeys, ctx->d_err);
     }
     int64_t NL = 0;   // the long pairs: the next planned pass sizes its table from them
     RC(planned_total(ctx, g, PT::n_long, n_long, &NL));
@@ -7075,10 +7074,10 @@ int ReadBamPass::pair_mark(int64_t n) {
     ProfScope ps(ctx, "k_pair_mark");
     uint32_t* mst = plan_stripes(ctx, g, d_nmulti, &brc);
     if (brc) return brc;
-    hipLaunchKernelGGL(k_pair_mark, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, skey2, sval2, g.ident, d_srec, T,
-                       mate_of, pflag, ctx->d_err, ctx->d_cnt, mst);
+    klaunch(ctx, k_pair_mark, nblk(n), 256, n, skey2, sval2, g.ident, d_srec, T, mate_of, pflag, ctx->d_err, ctx->d_cnt,
+            mst);
     sorted_pairing = true;
-    hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, mst, d_nmulti);
+    klaunch(ctx, k_stripe_total, 1, 64, mst, d_nmulti);
     return 0;
 }
 
@@ -7117,31 +7116,22 @@ int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_ap
     // seen three times or more) takes them compacted in stream order by the scan below
     const bool appended = !many && !sw.resid_scan;
     if (appended) {
-        ProfScope ps(ctx, "k_pair_resid");
-        hipLaunchKernelGGL(k_resid_insert, dim3(nblk(NR)), dim3(256), 0, ctx->stream, (const uint32_t*)n_app, NR,
-                           (const uint64_t*)rk_app, (const uint32_t*)rv_app, rht, hsize - 1, bloom, bsize - 1,
-                           hcnt, hmin, hmax, d_rmulti, ctx->d_err);
+        klaunch(ctx, "k_pair_resid", k_resid_insert, nblk(NR), 256, n_app, NR, rk_app, rv_app, rht, hsize - 1, bloom,
+                bsize - 1, hcnt, hmin, hmax, d_rmulti, ctx->d_err);
     } else {
         RC(scan_emit(ctx, g, resid, S, &NR2, PT::scan_resid,
                      EmitResid{skey, rk, rv, NR, rht, hsize - 1, bloom, bsize - 1, ctx->d_err, hcnt, hmin, hmax,
                                d_rmulti}));
     }
-    if (!many) {
-        ProfScope ps(ctx, "k_pair_resid");
-        hipLaunchKernelGGL(k_resid_probe, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, skey, resid,
-                           (const unsigned long long*)rht, hsize - 1, (const unsigned long long*)bloom, bsize - 1,
-                           ctx->d_err);
-    }
+    if (!many)
+        klaunch(ctx, "k_pair_resid", k_resid_probe, nblk(S), 256, S, skey, resid, rht, hsize - 1, bloom, bsize - 1,
+                ctx->d_err);
     int64_t nmulti_r = 1;
     if (!many) RC(planned_total(ctx, g, PT::resid_multi, d_rmulti, &nmulti_r));
     if (!many && nmulti_r == 0 && !sw.resid_sort) {
         // every residual key seen once or twice: paired through the table, no sort
-        ProfScope ps(ctx, "k_pair_mark");
-        hipLaunchKernelGGL(k_resid_pair, dim3(nblk(NR)), dim3(256), 0, ctx->stream, NR,
-                           (const uint64_t*)(appended ? rk_app : rk), (const uint32_t*)(appended ? rv_app : rv),
-                           (const unsigned long long*)rht, hsize - 1, (const uint32_t*)hcnt,
-                           (const uint32_t*)hmin, (const uint32_t*)hmax, g.ident, d_srec, T, mate_of, pflag,
-                           ctx->d_err, ctx->d_cnt);
+        klaunch(ctx, "k_pair_mark", k_resid_pair, nblk(NR), 256, NR, appended ? rk_app : rk, appended ? rv_app : rv, rht,
+                hsize - 1, hcnt, hmin, hmax, g.ident, d_srec, T, mate_of, pflag, ctx->d_err, ctx->d_cnt);
         return 0;
     }
     if (appended)   // (stream order for the sort: the scan's compaction, without the table again)
@@ -7149,11 +7139,8 @@ int ReadBamPass::pair_residual(int64_t NR, const uint8_t* resid, uint64_t* rk_ap
                      EmitResid{skey, rk, rv, NR, nullptr, 0, nullptr, 0, ctx->d_err, nullptr, nullptr, nullptr,
                                nullptr}));
     RC(sort_pairs(ctx, rk, skey2, rv, sval2, NR, "sort_qname_resid"));
-    if (many) {
-        ProfScope ps(ctx, "k_pair_resid");
-        hipLaunchKernelGGL(k_resid_probe_sorted, dim3(nblk(S)), dim3(256), 0, ctx->stream, S, skey, resid,
-                           (const uint64_t*)skey2, NR, ctx->d_err);
-    }
+    if (many)
+        klaunch(ctx, "k_pair_resid", k_resid_probe_sorted, nblk(S), 256, S, skey, resid, skey2, NR, ctx->d_err);
     return pair_mark(NR);
 }
 
@@ -7193,11 +7180,9 @@ int ReadBamPass::pair_keys() {
     if (g.coord_sorted && R > 0) bigE = GB(grp_bigE, R);   // (every entry written by k_pair_keys)
     if (R > 0 && !pre_ends) RC(fill.add(cflag, ((size_t)R + 15) & ~(size_t)15, 0u));
     RC(fill.launch());
-    if (P > 0) {
-        ProfScope ps(ctx, "k_pair_keys");
-        hipLaunchKernelGGL(k_pair_keys, dim3(nblk(P)), dim3(256), 0, ctx->stream, P, PV, T, g.seed, chash, thash,
-                           tval, pr_tag, rhash, (uint2*)bigE, rtag);
-    }
+    if (P > 0)
+        klaunch(ctx, "k_pair_keys", k_pair_keys, nblk(P), 256, P, PV, T, g.seed, chash, thash, tval, pr_tag, rhash,
+                (uint2*)bigE /* as pairs */, rtag);
     return 0;
 }
 
@@ -7218,22 +7203,19 @@ int ReadBamPass::grouping() {
         uint32_t* st = plan_stripes(ctx, g, d_nbig, &brc);
         if (brc) return brc;
         if (sw.group_staged)   // (the staged classification: a measurement / test switch)
-            hipLaunchKernelGGL(k_group_flags, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, N, rkey, rec_e, tsmall, st);
+            klaunch(ctx, k_group_flags, nblk(N, GT), GT, N, rkey, rec_e, tsmall, st);
         else
-            hipLaunchKernelGGL(k_group_count, dim3(nblk(N, GT * GC_TILES)), dim3(GT), 0, ctx->stream, N, (const int32_t*)rec_e,
-                               (const uint8_t*)T.rdeep, tsmall, st);
+            klaunch(ctx, k_group_count, nblk(N, GT * GC_TILES), GT, N, rec_e, T.rdeep, tsmall, st);
         if (has_plan(g, PT::n_big)) g.stripes_pending = true;
-        else hipLaunchKernelGGL(k_stripe_total, dim3(1), dim3(64), 0, ctx->stream, st, d_nbig);
+        else klaunch(ctx, k_stripe_total, 1, 64, st, d_nbig);
     }
     int64_t NS = 0, NB = 0;
     uint32_t* tpre = GB(grp_tile_pre, NT);
     RC(scan_total(ctx, g, tsmall, tpre, NT, &NS, PT::scan_small));
     if (NS > 0) {
-        ProfScope ps(ctx, "k_group_rank");
         const auto k_rank = rtag ? k_group_rank<true> : k_group_rank<false>;   // (the compare's fields by record, or by pair)
-        hipLaunchKernelGGL(k_rank, dim3(nblk(N, GT)), dim3(GT), 0, ctx->stream, N, rkey, rec_e,
-                           (const uint64_t*)rhash, (const uint32_t*)tpre, rs_key, rs_val, mem_rec, PV,
-                           (const int4*)rtag, T, segf, mem_valid, mem_meta, ctx->d_err);
+        klaunch(ctx, "k_group_rank", k_rank, nblk(N, GT), GT, N, rkey, rec_e, rhash, tpre, rs_key, rs_val, mem_rec, PV,
+                rtag, T, segf, mem_valid, mem_meta, ctx->d_err);
     }
     n_known = NS;
     RC(planned_total(ctx, g, PT::n_big, d_nbig, &NB));
@@ -7256,15 +7238,14 @@ int ReadBamPass::grouping() {
         uint32_t* bval = GB(grp_bval, NB);
         // group-major keys when this pass's coordinate search numbered the deep groups
         // (k_deep_qsort), else the full tag hash.  (The same keys with the hash bits in 16..63 and
-        // a sort over bits 16..63 split c4 families on the GPU: rocPRIM's begin_bit is not used.)
+        // a sort over bits 16..63 split c4 families on the GPU: the sorts start at bit 0.)
         constexpr int KEY_BITS = 48;   // the group-major keys' width (k_big_keys): six radix passes, not eight
         int gbits = 1;
         while ((1LL << gbits) < NDG) ++gbits;
         const bool by_group = deep_gid != nullptr && gbits <= 24;
         deep_same_group = by_group;
-        hipLaunchKernelGGL(k_big_keys, dim3(nblk(R)), dim3(256), 0, ctx->stream, R, bigE, bx,
-                           (const uint64_t*)rhash, PV, (const uint32_t*)(by_group ? deep_gid : nullptr), gbits,
-                           by_group ? KEY_BITS : 64, bkey, bval);
+        klaunch(ctx, k_big_keys, nblk(R), 256, R, bigE, bx, rhash, PV, by_group ? deep_gid : nullptr, gbits,
+                by_group ? KEY_BITS : 64, bkey, bval);
         RC(sort_pairs(ctx, bkey, rs_key + NS, bval, rs_val + NS, NB, "sort_tags_big", 0u, by_group ? (unsigned)KEY_BITS : 64u));
     }
     return 0;
@@ -7284,42 +7265,26 @@ int ReadBamPass::rank_deep_in_place(int64_t NS, int64_t NB) {
     uint32_t* d_big = plan_slot(ctx, g, PT::deep_big, &brc);
     if (brc) return brc;
     const DeepOut dout{R, rs_val, mem_rec, segf, mem_valid, mem_meta};
-    {
-        ProfScope ps(ctx, "k_deep_count");
-        hipLaunchKernelGGL(k_deep_count, dim3((unsigned)std::min<int64_t>(NDG, 4096)), dim3(256), 0, ctx->stream,
-                           (const uint32_t*)T.ndeep, (const int32_t*)T.dlist, (const int32_t*)gend, (const int32_t*)rec_e,
-                           gcnt);
-    }
+    klaunch(ctx, "k_deep_count", k_deep_count, (unsigned)std::min<int64_t>(NDG, 4096), 256, T.ndeep, T.dlist, gend,
+            rec_e, gcnt);
     int64_t nd = 0;
     RC(scan_total(ctx, g, gcnt, goff, NDG, &nd, PT::scan_deep));
     if (nd != NB) {
         ctx->err = "deep position groups: end count differs from the group partition";
         return CC_E_INVALID;
     }
-    {
-        ProfScope ps(ctx, "k_deep_fam");
-        hipLaunchKernelGGL(k_deep_fam, dim3((unsigned)std::min<int64_t>(NDG, CC_DF_GRID)), dim3(DF_T), 0, ctx->stream,
-                           (const uint32_t*)T.ndeep, (const int32_t*)T.dlist, (const int32_t*)gend, (const int32_t*)rec_e,
-                           (const uint64_t*)rhash, (const uint32_t*)goff, NS, PV, T, se, items, d_items, bigit,
-                           d_big, d_ovf, ctx->d_err);
-    }
+    klaunch(ctx, "k_deep_fam", k_deep_fam, (unsigned)std::min<int64_t>(NDG, CC_DF_GRID), DF_T, T.ndeep, T.dlist, gend,
+            rec_e, rhash, goff, NS, PV, T, se, items, d_items, bigit, d_big, d_ovf, ctx->d_err);
     int64_t novf = 0;
     RC(planned_total(ctx, g, PT::deep_ovf, d_ovf, &novf));
     if (novf != 0) return 0;
-    {
-        ProfScope ps(ctx, "k_deep_emit");
-        hipLaunchKernelGGL(k_deep_emit, dim3((unsigned)std::min<int64_t>(NB / 256 + 1, 8192)), dim3(256), 0,
-                           ctx->stream, (const int4*)items, (const uint32_t*)d_items, (const uint32_t*)se, PV,
-                           T, dout, ctx->d_err);
-    }
+    klaunch(ctx, "k_deep_emit", k_deep_emit, (unsigned)std::min<int64_t>(NB / 256 + 1, 8192), 256, items, d_items, se,
+            PV, T, dout, ctx->d_err);
     int64_t nbig = 0;
     RC(planned_total(ctx, g, PT::deep_big, d_big, &nbig));
-    if (nbig > 0) {
-        ProfScope ps(ctx, "k_deep_sortfam");
-        hipLaunchKernelGGL(k_deep_sortfam, dim3((unsigned)std::min<int64_t>(nbig, CC_DS_GRID)), dim3(DF_ST), 0,
-                           ctx->stream, (const int4*)bigit, (const uint32_t*)d_big, (const uint32_t*)se, PV, T,
-                           dout, ctx->d_err);
-    }
+    if (nbig > 0)
+        klaunch(ctx, "k_deep_sortfam", k_deep_sortfam, (unsigned)std::min<int64_t>(nbig, CC_DS_GRID), DF_ST, bigit,
+                d_big, se, PV, T, dout, ctx->d_err);
     deep_ranked = true;
     return 0;
 }
@@ -7331,13 +7296,12 @@ int ReadBamPass::families() {
         ProfScope ps(ctx, "k_fam_mark");
         // the small groups' slots [0, n_known) were marked by k_group_rank
         if (R > n_known && !deep_ranked)
-            hipLaunchKernelGGL(k_fam_mark, dim3(nblk(R - n_known)), dim3(256), 0, ctx->stream, R, n_known, n_known, rs_key,
-                               rs_val, PV, T, segf, mem_valid, mem_rec, mem_meta, ctx->d_err, deep_same_group ? 1 : 0);
+            klaunch(ctx, k_fam_mark, nblk(R - n_known), 256, R, n_known, n_known, rs_key, rs_val, PV, T, segf,
+                    mem_valid, mem_rec, mem_meta, ctx->d_err, deep_same_group ? 1 : 0);
         // qnames seen more than twice exist only where the exact pairing (k_pair_mark) ran this pass
         if (sorted_pairing)
-            hipLaunchKernelGGL(k_fam_dedup, dim3(std::min<unsigned>(nblk(R), 1024u)), dim3(256), 0, ctx->stream, R,
-                               (const uint32_t*)d_nmulti, (const uint8_t*)segf, mem_valid, (const int32_t*)mem_rec,
-                               (const uint32_t*)rs_val, (const int32_t*)pr_rec1, (const uint64_t*)T.rdig, mem_meta);
+            klaunch(ctx, k_fam_dedup, std::min<unsigned>(nblk(R), 1024u), 256, R, d_nmulti, segf, mem_valid, mem_rec,
+                    rs_val, pr_rec1, T.rdig, mem_meta);
     }
     // family starts compacted in the scan's store phase (EmitFamStarts): fam_beg and fam_drop take
     // their capacity first (F is the scan's total)
@@ -7364,14 +7328,10 @@ int ReadBamPass::families() {
         fam_tag = GB(fam_tag, F);
         fam_rec = GB(fam_rec, F);
     }
-    if (F > 0) {
-        ProfScope ps(ctx, "k_fam_build");
-        hipLaunchKernelGGL(k_fam_build, dim3(nblk(F)), dim3(256), 0, ctx->stream, F, R, n_known,
-                           (int)(g.n_regions == 1), fam_beg, fam_drop,
-                           rs_val, rs_key, pr_region, (const uint64_t*)rhash,
-                           (const int32_t*)mem_rec, fam_end, fam_n, fam_first, fam_region, fam_hash, cflag,
-                           cfam, fam_o, PV, T, fam_tag, fam_rec);
-    }
+    if (F > 0)
+        klaunch(ctx, "k_fam_build", k_fam_build, nblk(F), 256, F, R, n_known, (int)(g.n_regions == 1), fam_beg,
+                fam_drop, rs_val, rs_key, pr_region, rhash, mem_rec, fam_end, fam_n, fam_first, fam_region, fam_hash,
+                cflag, cfam, fam_o, PV, T, fam_tag, fam_rec);
     g.fam_tags_built = fam_tag != nullptr;
     RC(planned_total(ctx, g, PT::n_drop, d_ndrop, &V));
     V = R - V;   // members kept
@@ -7403,12 +7363,8 @@ int ReadBamPass::csn() {
         if (brc) return brc;
         if (!pre_csn) RC(fill.add(cht, sizeof(unsigned long long) * size, ~0u));
         RC(fill.launch());
-        {
-            ProfScope ps(ctx, "k_csn_fast");
-            hipLaunchKernelGGL(k_csn_fast, dim3((unsigned)((F + CT - 1) / CT)), dim3(256), 0, ctx->stream, F, pair_by_k,
-                               chash, tiles ? (const uint32_t*)bigE : (const uint32_t*)nullptr,
-                               cht, size - 1, emark, e1k, shared);
-        }
+        klaunch(ctx, "k_csn_fast", k_csn_fast, (unsigned)((F + CT - 1) / CT), 256, F, pair_by_k, chash,
+                tiles ? bigE : nullptr, cht, size - 1, emark, e1k, shared);
         int64_t sh = 0;
         RC(planned_total(ctx, g, PT::csn_shared, shared, &sh));
         fast_ok = sh == 0;
@@ -7418,14 +7374,13 @@ int ReadBamPass::csn() {
         uint32_t* eval = GB(eval, F);
         uint64_t* es_key = GB(es_key, F);
         uint32_t* es_val = GB(es_val, F);
-        hipLaunchKernelGGL(k_csn_keys, dim3(nblk(F)), dim3(256), 0, ctx->stream, F, fam_by_k, fam_first, chash, ekey, eval);
+        klaunch(ctx, k_csn_keys, nblk(F), 256, F, fam_by_k, fam_first, chash, ekey, eval);
         RC(sort_pairs(ctx, ekey, es_key, eval, es_val, F, "sort_csn"));
         HIPCHK(hipMemsetAsync(emark, 0, std::max<int64_t>(F, 1), ctx->stream));
         ProfScope ps(ctx, "k_csn");
-        hipLaunchKernelGGL(k_csn_mark, dim3(nblk(F)), dim3(256), 0, ctx->stream, F, es_key, es_val, fam_by_k,
-                           fam_first, PV, T, csegf, ctx->d_err);
-        hipLaunchKernelGGL(k_csn_entries, dim3(nblk(F)), dim3(256), 0, ctx->stream, F, csegf, es_val, fam_by_k,
-                           fam_region, g.badread ? 0 : 1, emark, e1k, ctx->d_cnt);
+        klaunch(ctx, k_csn_mark, nblk(F), 256, F, es_key, es_val, fam_by_k, fam_first, PV, T, csegf, ctx->d_err);
+        klaunch(ctx, k_csn_entries, nblk(F), 256, F, csegf, es_val, fam_by_k, fam_region, g.badread ? 0 : 1, emark, e1k,
+                ctx->d_cnt);
     }
     g.csn_fast = fast_ok;
     int32_t* ent_f = GB(ent_f, 2 * F);   // capacity; sized E below
@@ -7441,9 +7396,8 @@ int ReadBamPass::csn() {
     // earlier (a record fetched by two overlapping regions, or a pair whose ends sit in two regions
     // joining a family its other end's position group completed before)
     if (g.n_regions > 1 && g.badread && E > 0)
-        hipLaunchKernelGGL(k_overlap_keyerror, dim3(nblk(E)), dim3(256), 0, ctx->stream, E, (const int32_t*)ent_f,
-                           (const int32_t*)fam_beg, (const int32_t*)fam_end, (const int32_t*)fam_region,
-                           (const uint32_t*)rs_val, (const int32_t*)pr_region, ctx->d_err);
+        klaunch(ctx, k_overlap_keyerror, nblk(E), 256, E, ent_f, fam_beg, fam_end, fam_region, rs_val, pr_region,
+                ctx->d_err);
     return 0;
 }
 
@@ -7507,8 +7461,7 @@ extern "C" {
 int cc_read_bam(cc_ctx* ctx, int32_t table_id, int64_t S, const int32_t* stream_rec, const int32_t* stream_region,
                 int32_t n_regions, const int32_t* region_run, const cc_read_bam_params* prm, int32_t* group_id) {
     if (!ctx || !prm || !group_id || !ctx->tables.count(table_id) || S < 0 || S >= INT32_MAX / 2) return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     int32_t gid = ctx->next_id++;
     ctx->groups[gid].reset(new Group());
     Group& g = *ctx->groups[gid];
@@ -7551,7 +7504,7 @@ int cc_read_bam(cc_ctx* ctx, int32_t table_id, int64_t S, const int32_t* stream_
 // Re-run read_bam on a group whose stream is already resident (bench steps), with a new seed.
 int cc_read_bam_rerun(cc_ctx* ctx, int32_t group_id, uint64_t seed) {
     if (!ctx || !ctx->groups.count(group_id)) return CC_E_INVALID;
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     ctx->groups[group_id]->seed = seed;
     return read_bam_run(ctx, group_id);
 }
@@ -7582,8 +7535,7 @@ int cc_group_free(cc_ctx* ctx, int32_t group_id) {
 // both families; size 1 -> singleton record renamed, else consensus_maker.
 int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_out) {
     if (!ctx || !ctx->groups.count(group_id)) return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     Group& g = *ctx->groups[group_id];
     auto pass = [&]() -> int {
         RC(flush_derive(ctx, g.table));
@@ -7593,8 +7545,7 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
         if (!g.members_built) {   // a pass that did not write the member records (see read_bam_pass)
             uint4* mm = GB(mem_meta, R);
             if (R > 0)
-                hipLaunchKernelGGL(k_mem_meta, dim3(nblk(R)), dim3(256), 0, ctx->stream, R,
-                                   g.ptr<B::mem_rec>(), g.ptr<B::mem_valid>(), T, mm);
+                klaunch(ctx, k_mem_meta, nblk(R), 256, R, g.ptr<B::mem_rec>(), g.ptr<B::mem_valid>(), T, mm);
             g.members_built = true;
         }
         const uint8_t* has2 = g.ptr<B::has2>();   // by the pass's entry scan (EmitEntries)
@@ -7608,11 +7559,10 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
             uint64_t* sk = GB(emit_skey, E);
             uint32_t* ev = GB(emit_eval, E);
             uint32_t* sv = GB(emit_sval, E);
-            hipLaunchKernelGGL(k_emit_keys, dim3(nblk(E)), dim3(256), 0, ctx->stream, E, has2,
-                               g.ptr<B::ent_f>(), g.ptr<B::fam_region>(), ek, ev);
+            klaunch(ctx, k_emit_keys, nblk(E), 256, E, has2, g.ptr<B::ent_f>(), g.ptr<B::fam_region>(), ek, ev);
             RC(sort_pairs(ctx, ek, sk, ev, sv, E, "sort_emit"));
             if (E2 > 0)
-                hipLaunchKernelGGL(k_emit_rank, dim3(nblk(E2)), dim3(256), 0, ctx->stream, E2, (const uint32_t*)sv, hx);
+                klaunch(ctx, k_emit_rank, nblk(E2), 256, E2, sv, hx);
         }
         const int64_t NE = 2 * E2;
         int32_t* emit_fam = GB(emit_fam, NE);
@@ -7622,13 +7572,10 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
         uint8_t* needv = GB(needv, (NE + 15) & ~15LL);   // byte flags (16-B padded for the scan)
         int2* emit_span = GB(emit_span, NE);
         uint32_t* vxs = GB(vxs, (NE + 3) & ~3LL);
-        if (E > 0) {
-            ProfScope ps(ctx, "k_sscs_emit");
-            hipLaunchKernelGGL(k_sscs_emit, dim3(nblk(E)), dim3(256), 0, ctx->stream, E, g.ptr<B::ent_f>(),
-                               g.ptr<B::ent_pair>(), has2, hx, g.ptr<B::fam_n>(), g.ptr<B::fam_beg>(),
-                               g.ptr<B::fam_end>(), g.ptr<B::mem_rec>(), emit_fam, emit_n, emit_rec, needv, emit_span,
-                               pair_view(g), T, emit_ckey);
-        }
+        if (E > 0)
+            klaunch(ctx, "k_sscs_emit", k_sscs_emit, nblk(E), 256, E, g.ptr<B::ent_f>(), g.ptr<B::ent_pair>(), has2, hx,
+                    g.ptr<B::fam_n>(), g.ptr<B::fam_beg>(), g.ptr<B::fam_end>(), g.ptr<B::mem_rec>(), emit_fam, emit_n,
+                    emit_rec, needv, emit_span, pair_view(g), T, emit_ckey);
         int64_t NV = 0;
         RC(vote_families(ctx, g, T, NE, needv, vxs, emit_fam, emit_span, cutoff, &NV));
         // badReads list + read_families sizes (host formats the text)
@@ -7641,20 +7588,14 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
                          EmitGather{g.ptr<B::stream_rec>(), bad_rec}));
         bad_rec = GB(bad_rec, NB);
         // (fam_sizes_by_creation: written by the pass's creation scan, EmitCreation)
-        uint32_t bits = 0;
-        bool plan_ok = true;
-        RC(finish_pass(ctx, g, &bits, false, &plan_ok));
-        if (!plan_ok) return CC_E_PLAN;
-        if (n_out) *n_out = NE;
-        return err_code(ctx, bits);
+        return finish_stage(ctx, g, n_out, NE);
     };
     return run_planned(ctx, g, ST_SSCS, pass);
 }
 
 int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, int32_t n_bc, int64_t* n_out) {
     if (!ctx || !ctx->groups.count(group_id) || (!bc_swap && n_bc > 0)) return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     Group& g = *ctx->groups[group_id];
     auto pass = [&]() -> int {
         RC(flush_derive(ctx, g.table));
@@ -7672,26 +7613,18 @@ int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, i
             ProfScope ps(ctx, "k_dcs_decide");
             // a local grouping: per family, its position group staged in LDS; otherwise per entry
             if (G.local && !ctx->sw.dcs_per_entry)
-                hipLaunchKernelGGL(k_dcs_decide_fam, dim3((unsigned)((std::max<int64_t>(g.F, Q) + DD_T - 1) / DD_T)),
-                                   dim3(DD_T), 0, ctx->stream, Q, G, d_swap, n_bc, dec, t_rec, p_rec, fl_dcs, ctx->d_err);
+                klaunch(ctx, k_dcs_decide_fam, (unsigned)((std::max<int64_t>(g.F, Q) + DD_T - 1) / DD_T), DD_T, Q, G,
+                        d_swap, n_bc, dec, t_rec, p_rec, fl_dcs, ctx->d_err);
             else
-                hipLaunchKernelGGL(k_dcs_decide, dim3(nblk(Q)), dim3(256), 0, ctx->stream, Q, G, d_swap, n_bc, dec, t_rec,
-                                   p_rec, fl_dcs, ctx->d_err);
+                klaunch(ctx, k_dcs_decide, nblk(Q), 256, Q, G, d_swap, n_bc, dec, t_rec, p_rec, fl_dcs, ctx->d_err);
         }
         if (g.n_regions > 1 && g.F > 0) {   // tags deleted at a region's end, then completed again later
             int32_t* fdel = GB(fam_del, g.F);
-            hipLaunchKernelGGL(k_dcs_deleted, dim3(nblk(g.F)), dim3(256), 0, ctx->stream, g.F,
-                               g.ptr<B::fam_o>(), g.ptr<B::fam_region>(), Q,
-                               (const int32_t*)dec, fdel);
+            klaunch(ctx, k_dcs_deleted, nblk(g.F), 256, g.F, g.ptr<B::fam_o>(), g.ptr<B::fam_region>(), Q, dec, fdel);
             RC(deleted_late(ctx, g, fdel));
         }
         RC(duplex_tail(ctx, g, d, Q, PT::scan_dcs, 0, T, T));
-        uint32_t bits = 0;
-        bool plan_ok = true;
-        RC(finish_pass(ctx, g, &bits, false, &plan_ok));
-        if (!plan_ok) return CC_E_PLAN;
-        if (n_out) *n_out = Q;
-        return err_code(ctx, bits);
+        return finish_stage(ctx, g, n_out, Q);
     };
     return run_planned(ctx, g, ST_DCS, pass);
 }
@@ -7700,8 +7633,7 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
                             int64_t* n_out) {
     if (!ctx || !ctx->groups.count(sgroup) || !ctx->groups.count(ssgroup) || (!bc_swap && n_bc > 0))
         return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     Group& g = *ctx->groups[sgroup];
     Group& s = *ctx->groups[ssgroup];
     auto pass = [&]() -> int {
@@ -7742,12 +7674,9 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
             if (brc) return brc;
             HIPCHK(hipMemsetAsync(sdel, 0x7f, sizeof(int32_t) * std::max<int64_t>(s.F, 1), ctx->stream));
         }
-        if (Q > 0) {
-            ProfScope ps(ctx, "k_sc_decide");
-            hipLaunchKernelGGL(k_sc_decide, dim3(nblk(Q)), dim3(256), 0, ctx->stream, Q, G, SV,
-                               g.ptr<B::region_run>(), d_swap, n_bc, dec, t_rec, p_rec, fl, gdel, sdel,
-                               ctx->d_err);
-        }
+        if (Q > 0)
+            klaunch(ctx, "k_sc_decide", k_sc_decide, nblk(Q), 256, Q, G, SV, g.ptr<B::region_run>(), d_swap, n_bc, dec,
+                    t_rec, p_rec, fl, gdel, sdel, ctx->d_err);
         if (ov) {
             RC(deleted_late(ctx, g, gdel));
             if (s.F > 0) RC(deleted_late(ctx, s, sdel));
@@ -7757,23 +7686,17 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
         int32_t* q_pair = GB(q_pair, Q);
         int32_t* q_ckey = GB(q_ckey, 9 * Q);
         if (Q > 0) {
-            hipLaunchKernelGGL(k_q_pairs, dim3(nblk(Q)), dim3(256), 0, ctx->stream, Q, g.ptr<B::ent_pair>(),
-                               q_pair);
-            hipLaunchKernelGGL(k_ckey_out, dim3(nblk(Q)), dim3(256), 0, ctx->stream, Q, q_pair, pair_view(g),
-                               ctx->tables[g.table], q_ckey);
+            klaunch(ctx, k_q_pairs, nblk(Q), 256, Q, g.ptr<B::ent_pair>(), q_pair);
+            klaunch(ctx, k_ckey_out, nblk(Q), 256, Q, q_pair, pair_view(g), ctx->tables[g.table], q_ckey);
         }
-        uint32_t bits = 0;
-        bool plan_ok = true;
-        RC(finish_pass(ctx, g, &bits, false, &plan_ok));
-        if (!plan_ok) return CC_E_PLAN;
-        if (n_out) *n_out = Q;
-        return err_code(ctx, bits);
+        return finish_stage(ctx, g, n_out, Q);
     };
     return run_planned(ctx, g, ST_SC, pass);
 }
 
 int64_t cc_fetch(cc_ctx* ctx, int32_t group_id, const char* name, void* dst, int64_t cap) {
     if (!ctx || !ctx->groups.count(group_id) || !name) return CC_E_INVALID;
+    RC(enter(ctx));
     Group& g = *ctx->groups[group_id];
     const int id = name_id(BUF_IDS, name);
     if (id < 0 || !g.buf[id].p) {   // (a buffer this group has never allocated: no such array)
@@ -7801,11 +7724,8 @@ int64_t cc_fetch(cc_ctx* ctx, int32_t group_id, const char* name, void* dst, int
 
 namespace {
 int function_prep(cc_ctx* ctx, const DevTable& T) {
-    if (T.n > 0) {
-        ProfScope ps(ctx, "k_build_meta");
-        hipLaunchKernelGGL(k_build_meta, dim3(1), dim3(BC_T), 0, ctx->stream, T, (int32_t*)nullptr, ctx->d_err,
-                           (int32_t*)nullptr, (uint32_t*)nullptr, (int64_t)0);   // the table's error bits
-    }
+    if (T.n > 0)   // the table's error bits
+        klaunch(ctx, "k_build_meta", k_build_meta, 1, BC_T, T, nullptr, ctx->d_err, nullptr, nullptr, (int64_t)0);
     return 0;
 }
 
@@ -7835,8 +7755,7 @@ int cc_sscs_vote(cc_ctx* ctx, int32_t table_id, const int32_t* member_index, con
                                                                          !out_meta)))
         return CC_E_INVALID;
     if (nfam > 0 && fam_offsets[nfam] > 0 && !member_index) return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     RC(flush_derive(ctx, table_id));
     const DevTable T = ctx->tables[table_id];
     if (out_stride < T.max_len || (out_stride & 1)) {
@@ -7891,8 +7810,7 @@ int cc_sscs_vote(cc_ctx* ctx, int32_t table_id, const int32_t* member_index, con
     }
     RC(function_prep(ctx, T));
     if (R > 0)
-        hipLaunchKernelGGL(k_mem_meta, dim3(nblk(R)), dim3(256), 0, ctx->stream, R, (const int32_t*)mem_rec,
-                           (const uint32_t*)mem_valid, T, mem_meta);
+        klaunch(ctx, k_mem_meta, nblk(R), 256, R, mem_rec, mem_valid, T, mem_meta);
     int64_t NV = 0;
     g.R = R;   // the member arrays' length (the vote kernels' guards)
     RC(vote_families(ctx, g, T, nfam, needv, vxs, d_fam, d_span, cutoff, &NV));
@@ -7915,7 +7833,7 @@ int cc_pair_vote(cc_ctx* ctx, int32_t mode, int32_t table_a, int32_t table_b, co
     if (!ctx || !ctx->tables.count(table_a) || !ctx->tables.count(table_b) || (mode != 0 && mode != 1) || n < 0 ||
         (n > 0 && (!rec_a || !rec_b || !out_seq || !out_qual || !out_meta)))
         return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
+    RC(enter(ctx));
     RC(flush_derive(ctx, table_a));
     RC(flush_derive(ctx, table_b));
     const DevTable TA = ctx->tables[table_a], TB = ctx->tables[table_b];
@@ -8203,8 +8121,7 @@ int cc_group(cc_ctx* ctx, int64_t n, const void* keys, int32_t key_bytes, int32_
     if (!ctx || n < 0 || n >= INT32_MAX || !out_nfam || (n > 0 && (!keys || !out_perm || !out_fam_offsets)))
         return CC_E_INVALID;
     if (!key_args_ok(ctx, key_bytes)) return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     *out_nfam = 0;
     if (n == 0) {
         if (out_fam_offsets) out_fam_offsets[0] = 0;
@@ -8237,14 +8154,12 @@ int cc_group(cc_ctx* ctx, int64_t n, const void* keys, int32_t key_bytes, int32_
         RC(fill.add(fam_size, sizeof(uint32_t) * ((n + 3) & ~3LL), 0u));
         RC(fill.launch());
     }
-    hipLaunchKernelGGL(k_key_insert, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)dk, kw,
-                       (uint64_t)0x243f6a8885a308d3ULL, tab, mask, slot_of, slot_first, slot_cnt, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_group_starts, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const int32_t*)slot_of,
-                       (const int32_t*)slot_first, start);
+    klaunch(ctx, k_key_insert, nblk(n), 256, n, dk, kw, (uint64_t)0x243f6a8885a308d3ULL, tab, mask, slot_of, slot_first,
+            slot_cnt, nullptr);
+    klaunch(ctx, k_group_starts, nblk(n), 256, n, slot_of, slot_first, start);
     int64_t F = 0;
     RC(scan_total(ctx, g, start, fx, n, &F, PT::grp_scan_fam));
-    hipLaunchKernelGGL(k_group_fams, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const int32_t*)slot_of,
-                       (const int32_t*)slot_first, (const int32_t*)slot_cnt, (const uint32_t*)fx, fam_size, fkey, fval);
+    klaunch(ctx, k_group_fams, nblk(n), 256, n, slot_of, slot_first, slot_cnt, fx, fam_size, fkey, fval);
     int64_t tot = 0;
     RC(scan_total(ctx, g, fam_size, fam_off, F, &tot, PT::grp_scan_off));
     // members in input order inside their family: a stable sort by family number (radix sorts are
@@ -8286,7 +8201,7 @@ int cc_duplex_join(cc_ctx* ctx, int32_t mode, int64_t n, const void* keys, const
         for (int64_t k = 0; mode == 1 && k < m; ++k)
             if (rec_x[k] < 0 || rec_x[k] >= ctx->tables[table_x].n) { ctx->err = "rec_x outside table_x"; return CC_E_INVALID; }
     }
-    HIPCHK(hipSetDevice(ctx->device));
+    RC(enter(ctx));
     if (n == 0) return 0;
     if (vote) {
         RC(flush_derive(ctx, table_a));
@@ -8324,18 +8239,13 @@ int cc_duplex_join(cc_ctx* ctx, int32_t mode, int64_t n, const void* keys, const
         RC(fill.launch());
     }
     const uint64_t seed = 0x13198a2e03707344ULL;
-    hipLaunchKernelGGL(k_key_insert, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)dk, kw, seed, tab, mask,
-                       (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, flags);
-    hipLaunchKernelGGL(k_key_probe, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)dp, (const uint32_t*)dk,
-                       kw, seed, (const int32_t*)tab, mask, p, (int32_t*)nullptr, indeg);
+    klaunch(ctx, k_key_insert, nblk(n), 256, n, dk, kw, seed, tab, mask, nullptr, nullptr, nullptr, flags);
+    klaunch(ctx, k_key_probe, nblk(n), 256, n, dp, dk, kw, seed, tab, mask, p, nullptr, indeg);
     if (mx > 0) {
-        hipLaunchKernelGGL(k_key_insert, dim3(nblk(mx)), dim3(256), 0, ctx->stream, mx, (const uint32_t*)dx, kw, seed, xtab,
-                           xmask, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, flags);
-        hipLaunchKernelGGL(k_key_probe, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)dp,
-                           (const uint32_t*)dx, kw, seed, (const int32_t*)xtab, xmask, xs, xfirst, (int32_t*)nullptr);
+        klaunch(ctx, k_key_insert, nblk(mx), 256, mx, dx, kw, seed, xtab, xmask, nullptr, nullptr, nullptr, flags);
+        klaunch(ctx, k_key_probe, nblk(n), 256, n, dp, dx, kw, seed, xtab, xmask, xs, xfirst, nullptr);
     }
-    hipLaunchKernelGGL(k_join_decide, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, mode, (const int32_t*)p,
-                       (const int32_t*)xs, (const int32_t*)xfirst, (const int32_t*)indeg, dec, part, flags + 1, ctx->d_err);
+    klaunch(ctx, k_join_decide, nblk(n), 256, n, mode, p, xs, xfirst, indeg, dec, part, flags + 1, ctx->d_err);
     uint32_t hf[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(hf, flags, 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -8344,8 +8254,7 @@ int cc_duplex_join(cc_ctx* ctx, int32_t mode, int64_t n, const void* keys, const
         Fills fill(ctx);
         RC(fill.add(ctx->d_err, 64, 0u));
         RC(fill.launch());
-        hipLaunchKernelGGL(k_join_serial, dim3(1), dim3(64), 0, ctx->stream, n, mx, mode, (const int32_t*)p,
-                           (const int32_t*)xs, used, gone, xgone, dec, part, ctx->d_err);
+        klaunch(ctx, k_join_serial, 1, 64, n, mx, mode, p, xs, used, gone, xgone, dec, part, ctx->d_err);
     }
     uint32_t bits = 0;
     RC(read_err(ctx, &bits));
@@ -8390,11 +8299,10 @@ int cc_duplex_join(cc_ctx* ctx, int32_t mode, int64_t n, const void* keys, const
     RC(function_prep(ctx, TA));
     if (TX.payload != TA.payload) RC(function_prep(ctx, TX));
     {
-        ProfScope ps(ctx, mode ? "k_duplex_vote_sc" : "k_duplex_vote_dcs");
         const int32_t chunks = std::min(64, std::max(1, (ml + SV_POS - 1) / SV_POS));
         const int32_t fpw = 64 / chunks;
-        hipLaunchKernelGGL(k_duplex_vote_swar, dim3(nblk((nv + fpw - 1) / fpw, 4)), dim3(256), 0, ctx->stream, nv, mode,
-                           fpw, chunks, (const int4*)vpair, TA, TX, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
+        klaunch(ctx, mode ? "k_duplex_vote_sc" : "k_duplex_vote_dcs", k_duplex_vote_swar, nblk((nv + fpw - 1) / fpw, 4),
+                256, nv, mode, fpw, chunks, vpair, TA, TX, qstride, cons_seq, cons_qual, vmeta, ctx->d_err);
     }
     RC(read_err(ctx, &bits));
     if (bits) return err_code(ctx, bits);
@@ -8581,7 +8489,7 @@ int cc_extract_barcodes(cc_ctx* ctx, int64_t n, const uint8_t* h1, const uint8_t
         (n > 0 && (!h1 || !h2 || !len1 || !len2 || !out_status || !out_bc || !out_cut1 || !out_cut2)) ||
         (!pattern && n > 0 && (!out_bad1 || !out_bad2)))
         return CC_E_INVALID;
-    HIPCHK(hipSetDevice(ctx->device));
+    RC(enter(ctx));
     EbParams P;
     memset(&P, 0, sizeof P);
     P.list = pattern ? 0 : 1;
@@ -8660,10 +8568,8 @@ int cc_extract_barcodes(cc_ctx* ctx, int64_t n, const uint8_t* h1, const uint8_t
     HIPCHK(hipMemcpyAsync(tval, hval.data(), sizeof(int32_t) * EB_SLOTS, hipMemcpyHostToDevice, ctx->stream));
     if (n > 0) {
         ProfScope ps(ctx, "k_extract_barcodes");
-        hipLaunchKernelGGL(k_extract_barcodes, dim3(nblk(n)), dim3(256), 0, ctx->stream, n, (const uint8_t*)d1,
-                           (const uint8_t*)d2, (const int32_t*)dl1, (const int32_t*)dl2, P,
-                           (const unsigned long long*)tkey, (const int32_t*)tval, dst, dbc, dc1, dc2, db1, db2, dcnt,
-                           dh, dh + std::max(nh, 1));
+        klaunch(ctx, k_extract_barcodes, nblk(n), 256, n, d1, d2, dl1, dl2, P, tkey, tval, dst, dbc, dc1, dc2, db1, db2,
+                dcnt, dh, dh + std::max(nh, 1));
         HIPCHK(hipMemcpyAsync(out_status, dst, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(out_bc, dbc, (size_t)n * EB_BC, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(out_cut1, dc1, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -8759,7 +8665,7 @@ int cc_comm_init(cc_ctx* ctx, int32_t world, int32_t rank, const char* id, cc_co
     if (!ctx || !out || !id || world < 1 || rank < 0 || rank >= world) return CC_E_INVALID;
     Rccl* r = rccl(&ctx->err);
     if (!r) return CC_E_UNSUPPORTED;
-    HIPCHK(hipSetDevice(ctx->device));
+    RC(enter(ctx));
     std::unique_ptr<cc_comm> c(new cc_comm());
     c->world = world;
     c->rank = rank;
@@ -8793,7 +8699,7 @@ int cc_reduce_stats(cc_ctx* ctx, cc_comm* comm, int64_t* counters, int32_t n_cou
     if (!comm) return 0;
     Rccl* r = rccl(&ctx->err);
     if (!r) return CC_E_UNSUPPORTED;
-    HIPCHK(hipSetDevice(ctx->device));
+    RC(enter(ctx));
     const int64_t nsum = (int64_t)n_counters + fam_len, ntot = nsum + fam_len;
     if (ntot == 0) return 0;
     int brc = 0;
@@ -8832,7 +8738,7 @@ int cc_allreduce_max(cc_ctx* ctx, cc_comm* comm, int64_t* v, int32_t n) {
     if (!comm || n == 0) return 0;
     Rccl* r = rccl(&ctx->err);
     if (!r) return CC_E_UNSUPPORTED;
-    HIPCHK(hipSetDevice(ctx->device));
+    RC(enter(ctx));
     int brc = 0;
     if (!ctx->scratch) ctx->scratch.reset(new Group());
     Group& g = *ctx->scratch;

@@ -198,8 +198,7 @@ int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint
         return CC_E_INVALID;
     }
     if (n > (int64_t)INT32_MAX) { ctx->err = "cc_table_unpack: more than 2^31 - 1 records"; return CC_E_UNSUPPORTED; }
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->sw = read_switches();
+    RC(enter(ctx));
     const int32_t id = ctx->next_id++;
     std::vector<void*>& al = ctx->table_allocs[id];
     UnpackGuard guard{ctx, id};
@@ -245,14 +244,11 @@ int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint
         UnpackStatus* d_st = nullptr;
         RC(dev_alloc(ctx, guard.tmp, &d_st, 1));
         HIPCHK(hipMemcpyAsync(d_st, h_st, sizeof(UnpackStatus), hipMemcpyHostToDevice, ctx->stream));
-        {
-            ProfScope ps(ctx, "k_unpack_sizes");
-            hipLaunchKernelGGL(k_unpack_sizes, dim3(nblk(n, UPK_T)), dim3(UPK_T), 0, ctx->stream, d_recs, bytes, d_off, n,
-                               d_rf, T, sz16, sz8, d_st);
-            HIPCHK(hipGetLastError());
-        }
-        RC(scan_launch(ctx, (const uint32_t*)sz16, n, &d_st->tot16, "unpack_scan_pay", ScanStore{off16}));
-        RC(scan_launch(ctx, (const uint32_t*)sz8, n, &d_st->tot8, "unpack_scan_qn", ScanStore{off8}));
+        klaunch(ctx, "k_unpack_sizes", k_unpack_sizes, nblk(n, UPK_T), UPK_T, d_recs, bytes, d_off, n, d_rf, T, sz16, sz8,
+                d_st);
+        HIPCHK(hipGetLastError());
+        RC(scan_launch(ctx, sz16, n, &d_st->tot16, "unpack_scan_pay", ScanStore{off16}));
+        RC(scan_launch(ctx, sz8, n, &d_st->tot8, "unpack_scan_qn", ScanStore{off8}));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_st, d_st, sizeof(UnpackStatus), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -284,9 +280,7 @@ int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint
     HIPCHK(hipMemsetAsync(T.qn_blob + T.qn_bytes, 0, 16, ctx->stream));
     HIPCHK(hipMemsetAsync(T.payload + T.pay_bytes, 0, 64, ctx->stream));
     if (n > 0) {
-        ProfScope ps(ctx, "k_unpack_copy");
-        hipLaunchKernelGGL(k_unpack_copy, dim3(nblk(n, UPK_T / UPK_LANES)), dim3(UPK_T), 0, ctx->stream, d_recs, d_off, n,
-                           T, off16, off8);
+        klaunch(ctx, "k_unpack_copy", k_unpack_copy, nblk(n, UPK_T / UPK_LANES), UPK_T, d_recs, d_off, n, T, off16, off8);
         HIPCHK(hipGetLastError());
     }
     // the derived columns: as cc_table_upload without the decoder's layout
