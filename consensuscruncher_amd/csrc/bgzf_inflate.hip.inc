@@ -1,6 +1,7 @@
-// The device BGZF inflater (cc_bgzf_inflate, cc_bgzf_inflate_hook): included by cc_engine.hip after
+// The device BGZF inflater (cc_bgzf_inflate, cc_bgzf_inflate_hook) and the resident streams it can
+// leave on the device (cc_bgzf_inflate_keep, cc_resident_*): included by cc_engine.hip after
 // bgzf_deflate.hip.inc, whose streams, mutex and "nothing more on the device after a HIP error" latch
-// it shares.
+// they share.
 //
 // k_bgzf_inflate: one wave (a 64-thread workgroup) per member, many members in flight.  DEFLATE is
 // serial in bit order, so a member advances in batches of three steps:
@@ -77,7 +78,9 @@ struct BiCtl {   // a member's state between batches
     uint64_t buf;
 };
 
-// desc[j] = {offset in `in`, clen, offset in `out`, ulen}; status[j] = 1 when member j is good
+// desc[j] = {offset in `in`, clen, offset in `out`, ulen}; status[j] = 1 when member j is good.  `out`
+// is the round's base: the round's own output buffer, or the round's lowest offset in a resident
+// stream (the stores are byte stores, so neither it nor a member's offset need be aligned).
 __global__ __launch_bounds__(BI_T) void k_bgzf_inflate(const uint8_t* __restrict__ in, const uint4* __restrict__ desc,
                                                        uint8_t* __restrict__ out, uint32_t* __restrict__ status,
                                                        int members) {
@@ -183,8 +186,18 @@ __global__ __launch_bounds__(BI_T) void k_bgzf_inflate(const uint8_t* __restrict
 
 }  // namespace
 
+// A resident stream: the inflated file at its own offsets in a device buffer the context owns.
+// `total` usable bytes, align16(total) + 32 allocated, the bytes behind total zero (DevSrc's contract
+// in table_unpack.hip.inc).  Ids are unique across contexts, so another context's id is unknown here.
+struct Resident {
+    uint8_t* p = nullptr;
+    uint64_t total = 0;
+};
+std::atomic<int64_t> g_resident_next{1};
+
 struct BgzfDec {
     bool ready = false;
+    std::map<int64_t, Resident> res;   // under the encoder's mutex
     uint8_t* h_in[2] = {nullptr, nullptr};
     uint8_t* h_out[2] = {nullptr, nullptr};
     uint4* h_desc[2] = {nullptr, nullptr};
@@ -234,6 +247,7 @@ void bgzf_dec_free(BgzfDec* D) {   // the streams are idle (bgzf_free synchronis
         for (int k = 0; k < 6; ++k)
             if (D->ev[b][k]) (void)hipEventDestroy(D->ev[b][k]);
     }
+    for (auto& r : D->res) (void)hipFree(r.second.p);
     delete D;
 }
 
@@ -254,43 +268,71 @@ void bgzf_dec_prof(cc_ctx* ctx, bool reset, double* ms, int64_t* n, double* h2d,
     if (d2h) *d2h = D->d2h_ms;
 }
 
+// the device (and the inflater's buffers) ready for a call on the encoder's streams
+int bgzf_dec_enter(cc_ctx* ctx, BgzfEnc* E) {
+    if (E->broken) return CC_E_HIP;
+    BGCHK(hipSetDevice(ctx->device));   // (not enter(): a reader's thread, the switches are the engine thread's)
+    if (!E->dec) E->dec = new BgzfDec();
+    if (!E->dec->ready) RC(bgzf_dec_init(E, E->dec));
+    return 0;
+}
+
+Resident* resident_find(BgzfEnc* E, int64_t id) {
+    if (!E->dec) return nullptr;
+    auto it = E->dec->res.find(id);
+    return it == E->dec->res.end() ? nullptr : &it->second;
+}
+
 // cc_bgzf_inflate's work.  Rounds of at most BI_ROUND members (and BI_IN_CAP / BI_OUT_CAP bytes)
 // alternate between the two streams, each with its own pinned and device buffers: while one round's
 // kernel runs, the previous round's bytes are copied out to the caller and the next one's are packed.
+// With a resident stream R (cc_bgzf_inflate_keep) the kernel writes member j at R's byte uoff[j]
+// instead of into the round's output buffer: the round's base is its first member's uoff, desc.z the
+// 32-bit distance from it, and the round's download is its span of R.
 int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen,
-                    const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok) {
+                    const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok,
+                    const Resident* R = nullptr) {
     if (members == 0) return 0;
     if (members < 0 || !comp || !coff || !clen || !uoff || !ulen || !out || !ok) {
         E->err = "cc_bgzf_inflate: null argument or a negative member count";
         return CC_E_INVALID;
     }
-    if (E->broken) return CC_E_HIP;
-    BGCHK(hipSetDevice(ctx->device));   // (not enter(): a reader's thread, the switches are the engine thread's)
-    if (!E->dec) E->dec = new BgzfDec();
+    RC(bgzf_dec_enter(ctx, E));
     BgzfDec* D = E->dec;
-    if (!D->ready) RC(bgzf_dec_init(E, D));
     const bool prof = ctx->profiling;
     // the rounds: [first[k], first[k + 1]) of the members the device takes (BGZF's bounds; others stay ok = 0)
     std::vector<int64_t> idx, first;
+    std::vector<uint64_t> rbase, rspan;   // with R: each round's lowest byte of R and the bytes it spans
     {
         size_t in_b = 0, out_b = 0;
+        uint64_t base = 0;
         int n = 0;
         first.push_back(0);
         for (int64_t j = 0; j < members; ++j) {
             ok[j] = 0;
             if (clen[j] > BI_MEMBER || ulen[j] > BI_MEMBER) continue;
-            const size_t ib = bi_align(clen[j]), ob = bi_align(ulen[j]);
-            if (n == BI_ROUND || in_b + ib > BI_IN_CAP || out_b + ob > BI_OUT_CAP) {
+            const size_t ib = bi_align(clen[j]);
+            // the round's output bytes with this member: packed 16-B slots, or with R the span from its base
+            const bool below = R && uoff[j] < base;
+            auto with = [&](size_t have, uint64_t from) {
+                return R ? std::max(have, (size_t)(uoff[j] - from) + ulen[j]) : have + bi_align(ulen[j]);
+            };
+            if (n > 0 && (n == BI_ROUND || in_b + ib > BI_IN_CAP || below || with(out_b, base) > BI_OUT_CAP)) {
                 first.push_back((int64_t)idx.size());
+                rbase.push_back(base);
+                rspan.push_back(out_b);
                 in_b = out_b = 0;
                 n = 0;
             }
+            if (n == 0) base = uoff[j];
             idx.push_back(j);
             in_b += ib;
-            out_b += ob;
+            out_b = with(out_b, base);
             ++n;
         }
         first.push_back((int64_t)idx.size());
+        rbase.push_back(base);
+        rspan.push_back(out_b);
     }
     const int64_t rounds = (int64_t)first.size() - 1;
     if (idx.empty()) return members;
@@ -301,21 +343,23 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
         for (int i = 0; i < n; ++i) {
             const int64_t j = idx[(size_t)(first[k] + i)];
             memcpy(D->h_in[b] + in_b, comp + coff[j], clen[j]);
-            D->h_desc[b][i] = make_uint4((uint32_t)in_b, clen[j], (uint32_t)out_b, ulen[j]);
+            D->h_desc[b][i] = make_uint4((uint32_t)in_b, clen[j], R ? (uint32_t)(uoff[j] - rbase[k]) : (uint32_t)out_b, ulen[j]);
             in_b += bi_align(clen[j]);
             out_b += bi_align(ulen[j]);
         }
+        uint8_t* const d_base = R ? R->p + rbase[k] : D->d_out[b];
+        if (R) out_b = (size_t)rspan[k];
         D->timed[b] = prof;
         if (prof) BGCHK(hipEventRecord(D->ev[b][2], E->st[b]));
         if (in_b) BGCHK(hipMemcpyAsync(D->d_in[b], D->h_in[b], in_b, hipMemcpyHostToDevice, E->st[b]));
         BGCHK(hipMemcpyAsync(D->d_desc[b], D->h_desc[b], (size_t)n * sizeof(uint4), hipMemcpyHostToDevice, E->st[b]));
         if (prof) BGCHK(hipEventRecord(D->ev[b][3], E->st[b]));
         if (prof) BGCHK(hipEventRecord(D->ev[b][0], E->st[b]));
-        klaunch(E->st[b], k_bgzf_inflate, (unsigned)n, BI_T, D->d_in[b], D->d_desc[b], D->d_out[b], D->d_ok[b], n);
+        klaunch(E->st[b], k_bgzf_inflate, (unsigned)n, BI_T, D->d_in[b], D->d_desc[b], d_base, D->d_ok[b], n);
         BGCHK(hipGetLastError());
         if (prof) BGCHK(hipEventRecord(D->ev[b][1], E->st[b]));
         if (prof) BGCHK(hipEventRecord(D->ev[b][4], E->st[b]));
-        if (out_b) BGCHK(hipMemcpyAsync(D->h_out[b], D->d_out[b], out_b, hipMemcpyDeviceToHost, E->st[b]));
+        if (out_b) BGCHK(hipMemcpyAsync(D->h_out[b], d_base, out_b, hipMemcpyDeviceToHost, E->st[b]));
         BGCHK(hipMemcpyAsync(D->h_ok[b], D->d_ok[b], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[b]));
         if (prof) BGCHK(hipEventRecord(D->ev[b][5], E->st[b]));
         return 0;
@@ -360,6 +404,76 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
     return members - good;
 }
 
+// cc_bgzf_inflate_keep's work: the members' ranges checked against total and each other, a resident
+// stream allocated (its tail zeroed) and bgzf_decode run into it.  Without device memory for it the
+// call is cc_bgzf_inflate's and *id stays 0.
+int64_t bgzf_decode_keep(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen,
+                         const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok,
+                         uint64_t total, int64_t* id) {
+    *id = 0;
+    if (members < 0 || (members > 0 && (!comp || !coff || !clen || !uoff || !ulen || !out || !ok))) {
+        E->err = "cc_bgzf_inflate_keep: null argument or a negative member count";
+        return CC_E_INVALID;
+    }
+    bool ordered = true;   // (the readers' members come in file order: no sort then)
+    for (int64_t j = 0; j < members; ++j) {
+        if (uoff[j] > total || ulen[j] > total - uoff[j]) {
+            E->err = "cc_bgzf_inflate_keep: member " + std::to_string((long long)j) + " does not lie inside total";
+            return CC_E_INVALID;
+        }
+        if (j > 0 && uoff[j] < uoff[j - 1] + ulen[j - 1]) ordered = false;
+    }
+    if (!ordered) {
+        std::vector<int64_t> by;
+        for (int64_t j = 0; j < members; ++j)
+            if (ulen[j]) by.push_back(j);
+        std::sort(by.begin(), by.end(), [&](int64_t a, int64_t b) { return uoff[a] < uoff[b]; });
+        for (size_t i = 1; i < by.size(); ++i)
+            if (uoff[by[i]] < uoff[by[i - 1]] + ulen[by[i - 1]]) {
+                E->err = "cc_bgzf_inflate_keep: members " + std::to_string((long long)by[i - 1]) + " and " +
+                         std::to_string((long long)by[i]) + " overlap";
+                return CC_E_INVALID;
+            }
+    }
+    RC(bgzf_dec_enter(ctx, E));
+    Resident R;
+    R.total = total;
+    const size_t padded = bi_align((size_t)total) + 32;
+    if (hipMalloc((void**)&R.p, padded) != hipSuccess) {
+        (void)hipGetLastError();   // (out of memory is no reason for the latch)
+        return bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok);
+    }
+    int64_t r = CC_E_HIP;
+    hipError_t e = hipMemsetAsync(R.p + total, 0, padded - (size_t)total, E->st[0]);
+    if (e == hipSuccess) e = hipStreamSynchronize(E->st[0]);
+    if (e != hipSuccess) {
+        E->err = std::string("HIP error ") + hipGetErrorString(e) + " zeroing a resident stream's tail";
+        E->broken = true;
+    } else {
+        r = bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, &R);
+    }
+    if (r < 0) {   // (bgzf_decode drained both streams)
+        (void)hipFree(R.p);
+        return r;
+    }
+    *id = g_resident_next.fetch_add(1);
+    E->dec->res[*id] = R;
+    return r;
+}
+
+int resident_patch(cc_ctx* ctx, BgzfEnc* E, int64_t id, uint64_t off, const uint8_t* bytes, uint64_t n) {
+    const Resident* R = resident_find(E, id);
+    if (!R || off > R->total || n > R->total - off || (n > 0 && !bytes)) {
+        E->err = R ? "cc_resident_patch: the range does not lie inside the stream" : "cc_resident_patch: unknown id";
+        return CC_E_INVALID;
+    }
+    if (n == 0) return 0;
+    RC(bgzf_dec_enter(ctx, E));
+    BGCHK(hipMemcpyAsync(R->p + off, bytes, (size_t)n, hipMemcpyHostToDevice, E->st[0]));
+    BGCHK(hipStreamSynchronize(E->st[0]));
+    return 0;
+}
+
 // ccio_inflate_fn over a context: a HIP failure is a nonzero return (the readers then use the host codec)
 int bgzf_inflate_hook_fn(void* user, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen, const uint64_t* uoff,
                          const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok) {
@@ -368,6 +482,24 @@ int bgzf_inflate_hook_fn(void* user, const uint8_t* comp, const uint64_t* coff, 
     BgzfEnc* E = bgzf_get(ctx);
     std::lock_guard<std::mutex> lk(E->mu);
     return bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok) < 0 ? 1 : 0;
+}
+
+// ccio_inflate_keep_fn and ccio_resident_patch_fn over a context, likewise
+int bgzf_keep_hook_fn(void* user, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen, const uint64_t* uoff,
+                      const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok, uint64_t total, int64_t* token) {
+    cc_ctx* ctx = (cc_ctx*)user;
+    if (!ctx || !token) return 1;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    return bgzf_decode_keep(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, total, token) < 0 ? 1 : 0;
+}
+
+int bgzf_patch_hook_fn(void* user, int64_t token, uint64_t off, const uint8_t* bytes, uint64_t n) {
+    cc_ctx* ctx = (cc_ctx*)user;
+    if (!ctx) return 1;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    return resident_patch(ctx, E, token, off, bytes, n) ? 1 : 0;
 }
 
 }  // namespace
@@ -389,6 +521,76 @@ int cc_bgzf_inflate_hook(cc_ctx* ctx, ccio_inflate_fn* fn, void** user) {
     *fn = bgzf_inflate_hook_fn;
     *user = ctx;
     return 0;
+}
+
+int64_t cc_bgzf_inflate_keep(cc_ctx* ctx, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen,
+                             const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok,
+                             uint64_t total, int64_t* resident_id) {
+    if (!ctx || !resident_id) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const int64_t r = bgzf_decode_keep(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, total, resident_id);
+    if (r < 0) ctx->err = E->err;
+    return r;
+}
+
+int cc_bgzf_inflate_keep_hook(cc_ctx* ctx, ccio_inflate_keep_fn* keep, ccio_resident_patch_fn* patch, void** user) {
+    if (!ctx || !keep || !patch || !user) return CC_E_INVALID;
+    *keep = bgzf_keep_hook_fn;
+    *patch = bgzf_patch_hook_fn;
+    *user = ctx;
+    return 0;
+}
+
+int cc_resident_patch(cc_ctx* ctx, int64_t id, uint64_t off, const uint8_t* bytes, uint64_t n) {
+    if (!ctx) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const int rc = resident_patch(ctx, E, id, off, bytes, n);
+    if (rc) ctx->err = E->err;
+    return rc;
+}
+
+int cc_resident_free(cc_ctx* ctx, int64_t id) {
+    if (!ctx) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const Resident* R = resident_find(E, id);
+    if (!R) { ctx->err = "cc_resident_free: unknown id"; return CC_E_INVALID; }
+    (void)hipSetDevice(ctx->device);
+    for (int b = 0; b < 2; ++b)   // (every call that touches a stream waits before it returns: idle already)
+        if (E->st[b]) (void)hipStreamSynchronize(E->st[b]);
+    (void)hipFree(R->p);
+    E->dec->res.erase(id);
+    return 0;
+}
+
+// test hooks: a resident stream's bytes (its total; at most cap of them go to dst), and how many live
+int64_t cc_resident_fetch(cc_ctx* ctx, int64_t id, uint8_t* dst, uint64_t cap) {
+    if (!ctx) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const Resident* R = resident_find(E, id);
+    if (!R) { ctx->err = "cc_resident_fetch: unknown id"; return CC_E_INVALID; }
+    const size_t nb = (size_t)std::min<uint64_t>(cap, R->total);
+    if (dst && nb) {
+        RC(bgzf_dec_enter(ctx, E));
+        hipError_t e = hipMemcpyAsync(dst, R->p, nb, hipMemcpyDeviceToHost, E->st[0]);
+        if (e == hipSuccess) e = hipStreamSynchronize(E->st[0]);
+        if (e != hipSuccess) {
+            E->broken = true;
+            ctx->err = E->err = std::string("HIP error ") + hipGetErrorString(e) + " fetching a resident stream";
+            return CC_E_HIP;
+        }
+    }
+    return (int64_t)R->total;
+}
+
+int64_t cc_resident_count(cc_ctx* ctx) {
+    if (!ctx) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    return E->dec ? (int64_t)E->dec->res.size() : 0;
 }
 
 }  // extern "C"

@@ -231,22 +231,42 @@ void parallel_chunks(int64_t n, int nthreads, int64_t grain, const std::function
 std::mutex g_ihook_mu;
 ccio_inflate_fn g_ihook_fn = nullptr;
 void* g_ihook_user = nullptr;
+// the hook that keeps its own copy of what it inflated (ccio_set_inflate_keep_hook): the whole-file open's
+ccio_inflate_keep_fn g_khook_keep = nullptr;
+ccio_resident_patch_fn g_khook_patch = nullptr;
+void* g_khook_user = nullptr;
+
+// what a keep hook's copy of an inflated file needs: its size going in; coming out, the token and the
+// pair to patch it through (token 0: nothing was kept)
+struct KeptCopy {
+    uint64_t total = 0;
+    int64_t token = 0;
+    ccio_resident_patch_fn patch = nullptr;
+    void* user = nullptr;
+};
 
 // The non-empty members of blk (fields coff / clen / doff / dlen by the accessors) through the hook.
 // done[i] = 1 for every member the hook reports inflated AND whose bytes have the CRC32 the member
-// carries (the word behind its payload); every other member is left to the host codec.
+// carries (the word behind its payload); every other member is left to the host codec.  With kept
+// (the whole-file open) and a keep hook set, that hook is called in the plain one's place.
 template <class Blk, class C, class L, class U, class N>
 void hook_inflate(const uint8_t* comp, uint8_t* out, const std::vector<Blk>& blk, C coff, L clen, U doff, N dlen,
-                  int nthreads, std::vector<uint8_t>& done) {
+                  int nthreads, std::vector<uint8_t>& done, KeptCopy* kept = nullptr) {
     done.assign(blk.size(), 0);
     ccio_inflate_fn fn;
+    ccio_inflate_keep_fn keep = nullptr;
     void* user;
     {
         std::lock_guard<std::mutex> lk(g_ihook_mu);
         fn = g_ihook_fn;
         user = g_ihook_user;
+        if (kept && g_khook_keep) {
+            keep = g_khook_keep;
+            kept->patch = g_khook_patch;
+            kept->user = user = g_khook_user;
+        }
     }
-    if (!fn) return;
+    if (!fn && !keep) return;
     std::vector<size_t> which;
     std::vector<uint64_t> co, uo;
     std::vector<uint32_t> cl, ul;
@@ -260,7 +280,15 @@ void hook_inflate(const uint8_t* comp, uint8_t* out, const std::vector<Blk>& blk
     }
     if (which.empty()) return;
     std::vector<uint8_t> ok(which.size(), 0);
-    if (fn(user, comp, co.data(), cl.data(), uo.data(), ul.data(), (int64_t)which.size(), out, ok.data()) != 0) return;
+    if (keep) {
+        if (keep(user, comp, co.data(), cl.data(), uo.data(), ul.data(), (int64_t)which.size(), out, ok.data(),
+                 kept->total, &kept->token) != 0) {
+            kept->token = 0;
+            return;
+        }
+    } else if (fn(user, comp, co.data(), cl.data(), uo.data(), ul.data(), (int64_t)which.size(), out, ok.data()) != 0) {
+        return;
+    }
     parallel_chunks((int64_t)which.size(), nthreads, 64, [&](int64_t b, int64_t e) {
         Codec c;
         for (int64_t j = b; j < e; ++j) {
@@ -272,8 +300,9 @@ void hook_inflate(const uint8_t* comp, uint8_t* out, const std::vector<Blk>& blk
     });
 }
 
+// token (the whole-file open): the keep hook's name for its copy of the inflated file, 0 without one
 template <class CVec, class Vec>
-bool bgzf_inflate_all(const CVec& comp, Vec& out, int nthreads, std::string& err) {
+bool bgzf_inflate_all(const CVec& comp, Vec& out, int nthreads, std::string& err, int64_t* token = nullptr) {
     struct Blk { size_t coff, clen, doff, dlen; };
     std::vector<Blk> blocks;
     size_t off = 0, total = 0;
@@ -306,9 +335,11 @@ bool bgzf_inflate_all(const CVec& comp, Vec& out, int nthreads, std::string& err
     }
     out.resize(total);   // Vec's allocator leaves bytes uninitialised: every one is inflated below
     std::vector<uint8_t> done;
+    KeptCopy kept;
+    kept.total = total;
     hook_inflate((const uint8_t*)comp.data(), (uint8_t*)out.data(), blocks, [](const Blk& k) { return k.coff; },
                  [](const Blk& k) { return k.clen; }, [](const Blk& k) { return k.doff; },
-                 [](const Blk& k) { return k.dlen; }, nthreads, done);
+                 [](const Blk& k) { return k.dlen; }, nthreads, done, token ? &kept : nullptr);
     std::atomic<bool> bad(false);
     parallel_chunks((int64_t)blocks.size(), nthreads, 16, [&](int64_t b, int64_t e) {
         Codec c;
@@ -322,6 +353,15 @@ bool bgzf_inflate_all(const CVec& comp, Vec& out, int nthreads, std::string& err
         err = "BGZF inflate failed";
         return false;
     }
+    // the kept copy gets every member the host codec inflated; a failed patch leaves the handle without one
+    for (size_t i = 0; i < blocks.size() && kept.token; ++i) {
+        const Blk& k = blocks[i];
+        if (k.dlen == 0 || done[i]) continue;
+        if (!kept.patch || kept.patch(kept.user, kept.token, (uint64_t)k.doff, (const uint8_t*)out.data() + k.doff,
+                                      (uint64_t)k.dlen) != 0)
+            kept.token = 0;
+    }
+    if (token) *token = kept.token;
     return true;
 }
 
@@ -504,6 +544,8 @@ struct ccio_bam {
     std::vector<const uint8_t*> rec;  // every record's block_size, in record order
     std::vector<int64_t> origin;      // ccio_bam_combine: each record's index in the combined inputs
     std::shared_ptr<Bytes> packed;    // ccio_bam_decode_ids: a view's records packed into one stream
+    int64_t res_token = 0;            // the keep hook's copy of `data` (ccio_bam_open; 0: none), never freed here
+    uint64_t res_base = 0;            // where the records start in it: the header's size
     std::shared_future<int> pending;  // CCIO_W_ASYNC: the write of the file this handle's stream is
                                       // being compressed into (it reads `data`: waited for first)
     ~ccio_bam() {
@@ -710,6 +752,15 @@ void ccio_set_inflate_hook(ccio_inflate_fn fn, void* user) {
     std::lock_guard<std::mutex> lk(g_ihook_mu);
     g_ihook_fn = fn;
     g_ihook_user = fn ? user : nullptr;
+}
+
+// keep inflates the members of every file ccio_bam_open reads from now on and keeps a copy, which
+// patch corrects (NULL keep: the plain hook, or the host codec alone, again)
+void ccio_set_inflate_keep_hook(ccio_inflate_keep_fn keep, ccio_resident_patch_fn patch, void* user) {
+    std::lock_guard<std::mutex> lk(g_ihook_mu);
+    g_khook_keep = keep;
+    g_khook_patch = keep ? patch : nullptr;
+    g_khook_user = keep ? user : nullptr;
 }
 
 // waits for every CCIO_W_ASYNC write; -1 (ccio_last_error: the first failure) when one failed
@@ -948,10 +999,11 @@ bool scan_records(const uint8_t* d, size_t n, size_t from, int T, std::vector<co
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-// ------------------------------------------------------------------ reading
-ccio_bam* ccio_bam_open(const char* path, int nthreads) {
+// ccio_bam_open's work; keep: the open is the caller's own (the keep hook applies), not one of the
+// sorters' and mergers', whose handles nobody could ask for a token
+ccio_bam* bam_open(const char* path, int nthreads, bool keep) {
     wait_path(path);
     PhaseTimer pt;
     const int fd = open(path, O_RDONLY);
@@ -977,7 +1029,10 @@ ccio_bam* ccio_bam_open(const char* path, int nthreads) {
     std::unique_ptr<ccio_bam> bam(new ccio_bam());
     bam->data = std::make_shared<Bytes>();
     std::string err;
-    if (!bgzf_inflate_all(comp, *bam->data, hw_threads(nthreads), err)) { set_err(err + ": " + path); return nullptr; }
+    if (!bgzf_inflate_all(comp, *bam->data, hw_threads(nthreads), err, keep ? &bam->res_token : nullptr)) {
+        set_err(err + ": " + path);
+        return nullptr;
+    }
     comp.clear();
     comp.shrink_to_fit();
     pt.lap("open: inflate");
@@ -996,12 +1051,30 @@ ccio_bam* ccio_bam_open(const char* path, int nthreads) {
         bam->refs.emplace_back(name, lr);
     }
     bam->header_raw.assign(d.begin(), d.begin() + off);
+    bam->res_base = off;
     if (!scan_records(d.data(), d.size(), off, hw_threads(nthreads), bam->rec)) {
         set_err("truncated BAM record");
         return nullptr;
     }
     pt.lap("open: record walk");
     return bam.release();
+}
+
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------ reading
+ccio_bam* ccio_bam_open(const char* path, int nthreads) { return bam_open(path, nthreads, true); }
+
+// the keep hook's copy of b's stream: only while b's records are that stream's own, in place and in
+// order (ccio_bam_decode_ids packs anything else, and a packed stream is not the copy's)
+int ccio_bam_resident(ccio_bam* b, int64_t* token, uint64_t* base) {
+    if (!b || !token || !base || !b->res_token || !b->data || b->packed) return 0;
+    if (!b->rec.empty() && b->rec[0] != b->data->data() + b->res_base) return 0;
+    *token = b->res_token;
+    *base = b->res_base;
+    return 1;
 }
 
 void ccio_bam_close(ccio_bam* b) { delete b; }
@@ -1997,7 +2070,7 @@ int ccio_sort_bam(const char* in_path, const char* out_path, int level, int nthr
 int ccio_sort_bam_ex(const char* in_path, const char* out_path, int level, int nthreads, int flags) {
     wait_path(in_path);
     const int T = hw_threads(nthreads);
-    std::unique_ptr<ccio_bam> b(ccio_bam_open(in_path, nthreads));
+    std::unique_ptr<ccio_bam> b(bam_open(in_path, nthreads, false));
     if (!b) return -1;
     std::vector<const uint8_t*> recs(b->rec.size());
     for (size_t i = 0; i < recs.size(); ++i) recs[i] = b->rec[i];
@@ -2009,7 +2082,7 @@ int ccio_merge_bams(const char* out_path, const char* const* in_paths, int nin, 
     for (int i = 0; i < nin; ++i) wait_path(in_paths[i]);
     std::vector<ccio_bam*> bs;
     for (int i = 0; i < nin; ++i) {
-        ccio_bam* b = ccio_bam_open(in_paths[i], nthreads);
+        ccio_bam* b = bam_open(in_paths[i], nthreads, false);
         if (!b) { for (auto x : bs) ccio_bam_close(x); return -1; }
         bs.push_back(b);
     }
@@ -2041,7 +2114,7 @@ int ccio_concat_bams(const char* out_path, const char* const* in_paths, int nin,
     // peak memory is one part, not the whole output
     bool ok = true;
     for (int i = 0; i < nin && ok; ++i) {
-        ccio_bam* b = ccio_bam_open(in_paths[i], nthreads);
+        ccio_bam* b = bam_open(in_paths[i], nthreads, false);
         if (!b) { fclose(f); return -1; }
         const uint8_t* beg = b->rec.empty() ? b->data->data() + b->data->size() : b->rec[0];
         const size_t nrec = (size_t)(b->data->data() + b->data->size() - beg);

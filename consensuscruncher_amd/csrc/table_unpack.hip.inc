@@ -1,5 +1,7 @@
 // cc_table_unpack: a table's record columns and blobs built on the device from raw BAM records
 // (included by cc_engine.hip after cc_table_upload, whose result it reproduces byte for byte).
+// cc_table_unpack_resident: the same from records that already lie on the device, in a resident
+// stream the inflater left there (bgzf_inflate.hip.inc).
 //   k_unpack_sizes  a record per thread: the shared parser (unpack_core.h) checks the record and gives
 //                   its fields; the integer columns, qlen, qn_len, rflags, rdig, the slot sizes in
 //                   16-B (payload) and 8-B (qname) units, and per block the largest l_seq and tid
@@ -74,7 +76,9 @@ struct DevSrc {
     }
 };
 
-__global__ __launch_bounds__(UPK_T) void k_unpack_sizes(const uint8_t* __restrict__ recs, uint64_t bytes,
+// recs is the 16-B aligned base of the padded buffer; the records are its bytes [shift, shift + bytes)
+// and rec_off counts from shift (0 for an uploaded stream, the first record's offset in a resident one)
+__global__ __launch_bounds__(UPK_T) void k_unpack_sizes(const uint8_t* __restrict__ recs, uint64_t shift, uint64_t bytes,
                                                         const uint64_t* __restrict__ rec_off, int64_t n,
                                                         const uint8_t* __restrict__ rf_host, DevTable T,
                                                         uint32_t* __restrict__ sz16, uint32_t* __restrict__ sz8,
@@ -86,10 +90,11 @@ __global__ __launch_bounds__(UPK_T) void k_unpack_sizes(const uint8_t* __restric
     __syncthreads();
     const int64_t r = (int64_t)blockIdx.x * UPK_T + threadIdx.x;
     if (r < n) {
-        const uint64_t off = rec_off[r];
-        bool ok = off < bytes && (r == 0 || rec_off[r - 1] < off);
+        const uint64_t rel = rec_off[r];
+        bool ok = rel < bytes && (r == 0 || rec_off[r - 1] < rel);
+        const uint64_t off = shift + rel;   // (used only when rel < bytes)
         upk::Rec f;
-        ok = ok && upk::parse(recs + off, bytes - off, f);
+        ok = ok && upk::parse(recs + off, bytes - rel, f);
         uint32_t err = ok ? 0u : UE_BAD, p16 = 0, q8 = 0;
         if (ok && f.lseq > 0xffff) { err = UE_TOO_LONG; ok = false; }
         if (ok) {
@@ -129,14 +134,14 @@ __global__ __launch_bounds__(UPK_T) void k_unpack_sizes(const uint8_t* __restric
 
 // UPK_LANES lanes per record, UPK_T / UPK_LANES records per block; every record was accepted by
 // k_unpack_sizes, and off16 / off8 are the scans of the sizes it wrote, so each slot lies in its blob.
-__global__ __launch_bounds__(UPK_T) void k_unpack_copy(const uint8_t* __restrict__ recs,
+__global__ __launch_bounds__(UPK_T) void k_unpack_copy(const uint8_t* __restrict__ recs, uint64_t shift,
                                                        const uint64_t* __restrict__ rec_off, int64_t n, DevTable T,
                                                        const uint32_t* __restrict__ off16,
                                                        const uint32_t* __restrict__ off8) {
     const int64_t r = (int64_t)blockIdx.x * (UPK_T / UPK_LANES) + (threadIdx.x / UPK_LANES);
     const uint32_t j = threadIdx.x % UPK_LANES;
     if (r >= n) return;
-    const uint64_t off = rec_off[r];
+    const uint64_t off = shift + rec_off[r];
     const int32_t lseq = T.lseq[r];
     const int32_t qn_len = T.qn_len[r];
     const uint8_t* rec = recs + off;
@@ -185,15 +190,14 @@ int dev_alloc(cc_ctx* ctx, std::vector<void*>& allocs, T** dst, int64_t count, s
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint64_t* rec_off, int64_t n,
-                    const int32_t* cigar_id, const int32_t* bc_id, const int32_t* rg_id, const uint8_t* rflags,
-                    int32_t* max_len, int32_t* table_id) {
+// cc_table_unpack's and cc_table_unpack_resident's work.  The records are either recs[0 .. bytes) in
+// host memory (resident null: uploaded here into a padded buffer of the call's own) or the resident
+// buffer's bytes [shift, shift + bytes), read in place.
+int table_unpack(cc_ctx* ctx, const uint8_t* recs, const uint8_t* resident, uint64_t shift, uint64_t bytes,
+                 const uint64_t* rec_off, int64_t n, const int32_t* cigar_id, const int32_t* bc_id, const int32_t* rg_id,
+                 const uint8_t* rflags, int32_t* max_len, int32_t* table_id) {
     if (!ctx || !max_len || !table_id || n < 0) return CC_E_INVALID;
-    if (n > 0 && (!recs || !rec_off || !cigar_id || !bc_id || !rg_id || !rflags)) {
+    if (n > 0 && ((!recs && !resident) || !rec_off || !cigar_id || !bc_id || !rg_id || !rflags)) {
         ctx->err = "cc_table_unpack: null argument";
         return CC_E_INVALID;
     }
@@ -226,15 +230,21 @@ int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint
     *h_st = UnpackStatus{};
     h_st->first_bad = ~0ULL;
     h_st->max_tid = -1;
-    uint8_t *d_recs = nullptr, *d_rf = nullptr;
+    const uint8_t* d_recs = resident;
+    uint8_t* d_rf = nullptr;
     uint64_t* d_off = nullptr;
     uint32_t *sz16 = nullptr, *sz8 = nullptr, *off16 = nullptr, *off8 = nullptr;
     if (n > 0) {
-        // the stream, padded so the aligned 16-B words around its last bytes lie inside the buffer
-        const size_t padded = (size_t)((bytes + 15) & ~15ull) + 32;
-        RC(dev_alloc(ctx, guard.tmp, &d_recs, (int64_t)padded));
-        HIPCHK(hipMemcpyAsync(d_recs, recs, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemsetAsync(d_recs + bytes, 0, padded - (size_t)bytes, ctx->stream));
+        if (!resident) {
+            // the stream, padded so the aligned 16-B words around its last bytes lie inside the buffer
+            const size_t padded = (size_t)((bytes + 15) & ~15ull) + 32;
+            uint8_t* up = nullptr;
+            RC(dev_alloc(ctx, guard.tmp, &up, (int64_t)padded));
+            ProfScope ps(ctx, "unpack_stream_upload");
+            HIPCHK(hipMemcpyAsync(up, recs, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipMemsetAsync(up + bytes, 0, padded - (size_t)bytes, ctx->stream));
+            d_recs = up;
+        }
         RC(upload(ctx, guard.tmp, &d_off, rec_off, n));
         RC(upload(ctx, guard.tmp, &d_rf, rflags, n));
         RC(dev_alloc(ctx, guard.tmp, &sz16, n, 64));
@@ -244,8 +254,8 @@ int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint
         UnpackStatus* d_st = nullptr;
         RC(dev_alloc(ctx, guard.tmp, &d_st, 1));
         HIPCHK(hipMemcpyAsync(d_st, h_st, sizeof(UnpackStatus), hipMemcpyHostToDevice, ctx->stream));
-        klaunch(ctx, "k_unpack_sizes", k_unpack_sizes, nblk(n, UPK_T), UPK_T, d_recs, bytes, d_off, n, d_rf, T, sz16, sz8,
-                d_st);
+        klaunch(ctx, "k_unpack_sizes", k_unpack_sizes, nblk(n, UPK_T), UPK_T, d_recs, shift, bytes, d_off, n, d_rf, T, sz16,
+                sz8, d_st);
         HIPCHK(hipGetLastError());
         RC(scan_launch(ctx, sz16, n, &d_st->tot16, "unpack_scan_pay", ScanStore{off16}));
         RC(scan_launch(ctx, sz8, n, &d_st->tot8, "unpack_scan_qn", ScanStore{off8}));
@@ -280,7 +290,7 @@ int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint
     HIPCHK(hipMemsetAsync(T.qn_blob + T.qn_bytes, 0, 16, ctx->stream));
     HIPCHK(hipMemsetAsync(T.payload + T.pay_bytes, 0, 64, ctx->stream));
     if (n > 0) {
-        klaunch(ctx, "k_unpack_copy", k_unpack_copy, nblk(n, UPK_T / UPK_LANES), UPK_T, d_recs, d_off, n, T, off16, off8);
+        klaunch(ctx, "k_unpack_copy", k_unpack_copy, nblk(n, UPK_T / UPK_LANES), UPK_T, d_recs, shift, d_off, n, T, off16, off8);
         HIPCHK(hipGetLastError());
     }
     // the derived columns: as cc_table_upload without the decoder's layout
@@ -318,6 +328,36 @@ int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint
     *max_len = T.max_len;
     *table_id = id;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cc_table_unpack(cc_ctx* ctx, const uint8_t* recs, uint64_t bytes, const uint64_t* rec_off, int64_t n,
+                    const int32_t* cigar_id, const int32_t* bc_id, const int32_t* rg_id, const uint8_t* rflags,
+                    int32_t* max_len, int32_t* table_id) {
+    return table_unpack(ctx, recs, nullptr, 0, bytes, rec_off, n, cigar_id, bc_id, rg_id, rflags, max_len, table_id);
+}
+
+int cc_table_unpack_resident(cc_ctx* ctx, int64_t id, uint64_t base, uint64_t bytes, const uint64_t* rec_off, int64_t n,
+                             const int32_t* cigar_id, const int32_t* bc_id, const int32_t* rg_id, const uint8_t* rflags,
+                             int32_t* max_len, int32_t* table_id) {
+    if (!ctx) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    // held throughout: the stream cannot be freed, nor the inflater run, while the kernels read it
+    std::lock_guard<std::mutex> lk(E->mu);
+    const Resident* R = resident_find(E, id);
+    if (!R) { ctx->err = "cc_table_unpack_resident: unknown id"; return CC_E_INVALID; }
+    if (base > R->total || bytes > R->total - base) {
+        ctx->err = "cc_table_unpack_resident: the records do not lie inside the stream";
+        return CC_E_INVALID;
+    }
+    if (E->broken) { ctx->err = E->err; return CC_E_HIP; }
+    HIPCHK(hipSetDevice(ctx->device));
+    for (int b = 0; b < 2; ++b)   // the inflater's and the patches' writes are done before the first kernel
+        if (E->st[b]) HIPCHK(hipStreamSynchronize(E->st[b]));
+    return table_unpack(ctx, nullptr, R->p, base, bytes, rec_off, n, cigar_id, bc_id, rg_id, rflags, max_len, table_id);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ dec codes: DCS 0 = duplex made, 1 = SSCS singleton, 2 = partner already used, 3 
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -104,6 +105,11 @@ class Bam(object):
         if not h:
             raise IOError(N.io_error())
         self.h = h
+        self._res_owner = None   # the engine that holds this handle's resident stream (resident)
+        if _KEEP_OWNER is not None:
+            tok = C.c_int64()
+            if N.io().ccio_bam_resident(self.h, C.byref(tok), C.byref(C.c_uint64())):
+                self._res_owner = weakref.ref(_KEEP_OWNER)
         self.n = int(N.io().ccio_bam_nrec(self.h))
         self.refs = []
         buf = C.create_string_buffer(4096)
@@ -194,8 +200,33 @@ class Bam(object):
                                   int(key), 0)
         return Bam._handle(h)
 
+    def resident(self):
+        """(engine, id, base) when the engine's inflater kept this file's inflated bytes on the device
+        (Engine.device_resident) and the handle's records are still that stream's own, from byte base
+        on (ccio_bam_resident); None otherwise: views, combined handles, region opens, a handle whose
+        stream was consumed (resident_done) or whose engine is closed."""
+        eng = self._res_owner() if self._res_owner is not None else None
+        if eng is None or not eng.h or not self.h:
+            return None
+        tok, base = C.c_int64(), C.c_uint64()
+        if not N.io().ccio_bam_resident(self.h, C.byref(tok), C.byref(base)):
+            return None
+        return eng, int(tok.value), int(base.value)
+
+    def resident_done(self):
+        """The resident stream is freed (Engine.unpack): close has nothing left to free."""
+        self._res_owner = None
+
     def close(self):
         if self.h:
+            # a resident stream nobody unpacked (a stats-only open) goes with the handle while its engine
+            # lives; cc_destroy frees it otherwise
+            eng = self._res_owner() if getattr(self, "_res_owner", None) is not None else None
+            if eng is not None and eng.h:
+                tok = C.c_int64()
+                if N.io().ccio_bam_resident(self.h, C.byref(tok), C.byref(C.c_uint64())):
+                    eng.lib.cc_resident_free(eng.h, tok.value)
+            self._res_owner = None
             N.io().ccio_bam_close(self.h)
             self.h = None
 
@@ -301,6 +332,7 @@ def coord_sorted(records):
 
 _BGZF_OWNER = None   # the engine whose encoder libccio's (process-wide) deflate hook points at
 _INFLATE_OWNER = None   # likewise for the inflate hook
+_KEEP_OWNER = None   # and for the inflate hook that keeps resident streams
 
 
 class Engine(object):
@@ -318,6 +350,10 @@ class Engine(object):
         self._bgzf_effort = 1
         self.inflate_device = False
         self.decode_device = False
+        self.resident_device = False
+        self._keep_wired = False
+        if os.environ.get("CC_RESIDENT_DEVICE") == "1":
+            self.device_resident(True)
         if os.environ.get("CC_BGZF_EFFORT"):   # the encoder's effort, for CC_BGZF_DEVICE and bgzf_deflate alike
             self._set_bgzf_effort(os.environ["CC_BGZF_EFFORT"])
         if os.environ.get("CC_BGZF_DEVICE") == "1":   # opt-in, in the style of CC_EXTRACT_GPU
@@ -334,7 +370,44 @@ class Engine(object):
         Returns the previous state."""
         was = self.decode_device
         self.decode_device = bool(on)
+        self._sync_keep()
         return was
+
+    def device_resident(self, on):
+        """Switches the resident path on or off (off is the default): a whole-file open leaves the
+        bytes the device inflater produced in a device buffer (cc_bgzf_inflate_keep), and unpack has
+        cc_table_unpack_resident read the records there instead of uploading them again.  It has
+        effect only together with device_inflate and device_decode: while either is off nothing is
+        wired, no resident stream is made and every path is as without the switch (no error is
+        raised).  The tables, and every file written from them, are the same either way.  Returns
+        the previous state."""
+        was = self.resident_device
+        self.resident_device = bool(on)
+        self._sync_keep()
+        return was
+
+    def _sync_keep(self):
+        """libccio's keep hook (cc_bgzf_inflate_keep_hook -> ccio_set_inflate_keep_hook) wired exactly
+        while this engine has device_inflate, device_decode and device_resident on, with the inflate
+        hook's one-owner rules."""
+        global _KEEP_OWNER
+        want = bool(self.h) and self.inflate_device and self.decode_device and self.resident_device
+        if want == self._keep_wired:
+            return
+        io = N.io()
+        if want:
+            keep, patch, user = N.P(), N.P(), N.P()
+            self._check(self.lib.cc_bgzf_inflate_keep_hook(self.h, C.byref(keep), C.byref(patch), C.byref(user)))
+            prev = _KEEP_OWNER
+            if prev is not None and prev is not self:
+                prev._keep_wired = False
+            io.ccio_set_inflate_keep_hook(keep, patch, user)
+            _KEEP_OWNER = self
+            self._keep_wired = True
+            return
+        io.ccio_set_inflate_keep_hook(None, None, None)
+        _KEEP_OWNER = None
+        self._keep_wired = False
 
     @property
     def bgzf_effort(self):
@@ -407,8 +480,9 @@ class Engine(object):
         so the bytes read are the same either way.  The hook is one per process, with device_bgzf's
         ownership rules: the last engine to wire it serves the readers, the engine it took the hook
         from reads inflate_device False from then on, and that engine's close or unwiring leaves the
-        new owner's hook alone.  Reads are synchronous, so there is nothing to wait for.  Returns the
-        previous state."""
+        new owner's hook alone.  Reads are synchronous, so there is nothing to wait for.  With
+        device_decode and device_resident on as well, the hook that keeps resident streams is wired
+        with it (and unwired with it).  Returns the previous state."""
         global _INFLATE_OWNER
         was = self.inflate_device
         on = bool(on)
@@ -421,13 +495,16 @@ class Engine(object):
             prev = _INFLATE_OWNER
             if prev is not None and prev is not self:
                 prev.inflate_device = False
+                prev._sync_keep()
             io.ccio_set_inflate_hook(fn, user)
             _INFLATE_OWNER = self
             self.inflate_device = True
+            self._sync_keep()
             return was
         io.ccio_set_inflate_hook(None, None)
         _INFLATE_OWNER = None
         self.inflate_device = False
+        self._sync_keep()
         return was
 
     def bgzf_inflate(self, raw):
@@ -492,7 +569,8 @@ class Engine(object):
     def close(self):
         if self.h:
             try:
-                self.device_inflate(False)   # the hooks must not outlive the context
+                self.device_resident(False)   # the hooks must not outlive the context; the resident streams
+                self.device_inflate(False)    # that are left go with it (cc_destroy)
                 self.device_bgzf(False)
             finally:
                 self.lib.cc_destroy(self.h)
@@ -571,14 +649,43 @@ class Engine(object):
                                              N.ptr(cols[3]), C.byref(ml), C.byref(tid)))
         return tid.value, ml.value
 
+    def unpack_resident(self, rid, base, nbytes, rec_off, cigar_id, bc_id, rg_id, rflags):
+        """cc_table_unpack_resident on caller-given arrays: unpack_raw with the records read from bytes
+        [base, base + nbytes) of resident stream rid.  The stream is not freed."""
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        n = len(off)
+        cols = [np.ascontiguousarray(a, t) for a, t in ((cigar_id, np.int32), (bc_id, np.int32), (rg_id, np.int32),
+                                                        (rflags, np.uint8))]
+        assert all(len(c) >= n for c in cols)
+        ml, tid = C.c_int32(), C.c_int32()
+        self._check(self.lib.cc_table_unpack_resident(self.h, int(rid), int(base), int(nbytes),
+                                                      N.ptr(off) if n else None, n, N.ptr(cols[0]), N.ptr(cols[1]),
+                                                      N.ptr(cols[2]), N.ptr(cols[3]), C.byref(ml), C.byref(tid)))
+        return tid.value, ml.value
+
     def unpack(self, bam, interner, mode, delim="|"):
         """The device decode of bam: (records, table).  libccio's slim pass (Bam.decode_ids) keeps the
         string work (interned cigar, barcode and RG ids, the string-derived record flags); the raw
         records go to the device, where cc_table_unpack builds every other column and both blobs of
         the table that bam.decode + upload would have given.  records holds the host integer columns
-        only."""
+        only.  When this engine's inflater kept bam's bytes on the device (device_resident,
+        bam.resident) the records are read there (cc_table_unpack_resident) and the resident stream
+        is freed, whether the unpack succeeds or not; an id the engine does not know falls back to the
+        upload."""
         rec, stream, off = bam.decode_ids(interner, mode, delim)
-        table, ml = self.unpack_raw(stream, off, rec.cigar_id, rec.bc_id, rec.rg_id, rec.rflags)
+        res = bam.resident()
+        got = None
+        if res is not None and res[0] is self:
+            try:
+                got = self.unpack_resident(res[1], res[2], stream.size, off, rec.cigar_id, rec.bc_id, rec.rg_id,
+                                           rec.rflags)
+            except N.CCError as e:
+                if e.code != N.CC_E_INVALID:   # (records the device refuses are refused again below)
+                    raise
+            finally:
+                self.lib.cc_resident_free(self.h, res[1])
+                bam.resident_done()
+        table, ml = got or self.unpack_raw(stream, off, rec.cigar_id, rec.bc_id, rec.rg_id, rec.rflags)
         if rec.n and ml != rec.max_len:
             self.lib.cc_table_free(self.h, table)
             raise N.CCError(-1, "device and host disagree on the longest read")

@@ -18,6 +18,7 @@ CC_E = {
     -10: "CC_E_COLLISION", -11: "CC_E_UNSUPPORTED", -12: "CC_E_KEYERROR",
     -13: "CC_E_REPLAY",
 }
+CC_E_INVALID = -1
 CC_E_N_HIGHQ = -3
 CC_E_COLLISION = -10
 CC_E_KEYERROR = -12
@@ -80,6 +81,11 @@ DEFLATE_FN = C.CFUNCTYPE(C.c_int, P, P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c
 # ccio_inflate_fn: user, comp, coff, clen, uoff, ulen, members, out, ok
 INFLATE_FN = C.CFUNCTYPE(C.c_int, P, P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                          C.POINTER(C.c_uint32), C.c_int64, P, C.POINTER(C.c_uint8))
+# ccio_inflate_keep_fn: the same, then total, token; ccio_resident_patch_fn: user, token, off, bytes, n
+INFLATE_KEEP_FN = C.CFUNCTYPE(C.c_int, P, P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                              C.POINTER(C.c_uint32), C.c_int64, P, C.POINTER(C.c_uint8), C.c_uint64,
+                              C.POINTER(C.c_int64))
+RESIDENT_PATCH_FN = C.CFUNCTYPE(C.c_int, P, C.c_int64, C.c_uint64, P, C.c_uint64)
 
 _io = None
 _amd = None
@@ -89,6 +95,8 @@ IO_SIGS = {
     "ccio_flush": (C.c_int, []),
     "ccio_set_deflate_hook": (None, [P, P]),
     "ccio_set_inflate_hook": (None, [P, P]),
+    "ccio_set_inflate_keep_hook": (None, [P, P, P]),
+    "ccio_bam_resident": (C.c_int, [P, i64p, C.POINTER(C.c_uint64)]),
     "ccio_value_census": (C.c_int, [P, C.c_int64, C.c_int32, P, P]),
     "ccio_interner_new": (P, []),
     "ccio_interner_free": (None, [P]),
@@ -158,6 +166,12 @@ AMD_SIGS = {
     "cc_bgzf_set_effort": (C.c_int, [P, C.c_int]),
     "cc_bgzf_inflate": (C.c_int64, [P, P, P, P, P, P, C.c_int64, P, P]),
     "cc_bgzf_inflate_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
+    "cc_bgzf_inflate_keep": (C.c_int64, [P, P, P, P, P, P, C.c_int64, P, P, C.c_uint64, i64p]),
+    "cc_bgzf_inflate_keep_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
+    "cc_resident_patch": (C.c_int, [P, C.c_int64, C.c_uint64, P, C.c_uint64]),
+    "cc_resident_free": (C.c_int, [P, C.c_int64]),
+    "cc_resident_fetch": (C.c_int64, [P, C.c_int64, P, C.c_uint64]),
+    "cc_resident_count": (C.c_int64, [P]),
     "cc_defer": (C.c_int, [P, C.c_int]),
     "cc_commit": (C.c_int, [P]),
     "cc_debug_skew_plan": (C.c_int, [P, C.c_int32, C.c_char_p, C.c_int64]),
@@ -165,6 +179,8 @@ AMD_SIGS = {
     "cc_launch_count": (C.c_int64, []),
     "cc_table_upload": (C.c_int, [P, C.POINTER(cc_records), C.c_int32, i32p]),
     "cc_table_unpack": (C.c_int, [P, P, C.c_uint64, P, C.c_int64, P, P, P, P, i32p, i32p]),
+    "cc_table_unpack_resident": (C.c_int, [P, C.c_int64, C.c_uint64, C.c_uint64, P, C.c_int64, P, P, P, P, i32p,
+                                           i32p]),
     "cc_table_free": (C.c_int, [P, C.c_int32]),
     "cc_table_derive": (C.c_int, [P, C.c_int32]),
     "cc_table_fetch": (C.c_int64, [P, C.c_int32, C.c_char_p, P, C.c_int64]),

@@ -52,7 +52,7 @@ def cleanup(sd, identifier, scorrect):
 
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
-                       bgzf="host", inflate="host", decode="host", bgzf_effort=1):
+                       bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host"):
     """bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
     output files: same records, other compressed bytes and .bai offsets).  bgzf_effort: the device
     encoder's effort, 1 (the default) or 2 (smaller files, a slower kernel); 2 needs bgzf="device",
@@ -60,7 +60,10 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
     default) or "device" (the engine's BGZF inflater reads the input and stage files: same bytes read,
     so the same outputs).  decode: "host" (the default) or "device" (the stage tables are built by
     the engine's record unpacker from the raw records, Engine.unpack: the same tables, so the same
-    outputs).  Each option is wired for this call only; see _consensus_pipeline."""
+    outputs).  resident: "host" (the default) or "device" (the bytes the device inflater produced stay
+    in a device buffer that the record unpacker reads in place, Engine.device_resident: the same
+    tables again); it engages only with inflate="device" and decode="device" and is otherwise without
+    effect.  Each option is wired for this call only; see _consensus_pipeline."""
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
     if bgzf_effort not in (1, 2):
@@ -71,6 +74,16 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
         raise ValueError('inflate must be "host" or "device"')
     if decode not in ("host", "device"):
         raise ValueError('decode must be "host" or "device"')
+    if resident not in ("host", "device"):
+        raise ValueError('resident must be "host" or "device"')
+    if resident == "device":
+        engine = engine or get_engine()
+        was_res = engine.device_resident(True)
+        try:
+            return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                      cleanup_files, all_unique_sscs, bgzf, inflate, decode, bgzf_effort)
+        finally:
+            engine.device_resident(was_res)
     if decode == "device":
         engine = engine or get_engine()
         was_dec = engine.device_decode(True)

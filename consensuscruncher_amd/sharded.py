@@ -621,11 +621,14 @@ def to_owners(comm, geo, parts):
 
 def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|", scorrect="True", level=6,
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
-                     cuts=None, bgzf="host", inflate="host", decode="host", bgzf_effort=1):
+                     cuts=None, bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host"):
     """bgzf: "host" (the default) or "device": this rank's output files deflated by the engine's BGZF
     encoder, at bgzf_effort 1 (the default) or 2 (2 needs bgzf="device").  inflate: "host" (the default) or "device": this rank's reads inflated by the engine's
     BGZF inflater.  decode: "host" (the default) or "device": this rank's stage tables built by the
-    engine's record unpacker (pipeline.consensus_pipeline's options); see _sharded_pipeline."""
+    engine's record unpacker.  resident: "host" (the default) or "device": a whole-file read's inflated
+    bytes stay on the device for the unpacker (Engine.device_resident; only with inflate="device" and
+    decode="device", and only for whole-file opens: a rank's region reads and combined handles are
+    uploaded as before).  These are pipeline.consensus_pipeline's options; see _sharded_pipeline."""
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
     if bgzf_effort not in (1, 2):
@@ -636,6 +639,16 @@ def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|
         raise ValueError('inflate must be "host" or "device"')
     if decode not in ("host", "device"):
         raise ValueError('decode must be "host" or "device"')
+    if resident not in ("host", "device"):
+        raise ValueError('resident must be "host" or "device"')
+    if resident == "device":
+        was_res = engine.device_resident(True)
+        try:
+            return sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                    blocks, held, refs, keep, finalize, timings, cuts, bgzf, inflate, decode,
+                                    bgzf_effort)
+        finally:
+            engine.device_resident(was_res)
     if decode == "device":
         was_dec = engine.device_decode(True)
         try:

@@ -33,7 +33,8 @@ def get_engine():
 
 def _decode(eng, bam, it, mode, delim="|"):
     """bam's records by the decoder eng is switched to (Engine.device_decode): the host decoder, or the
-    device unpacker, whose records come with their table already built (_upload)."""
+    device unpacker, whose records come with their table already built (_upload); the unpacker reads
+    them from the inflater's resident stream when bam has one (Engine.device_resident)."""
     if eng.decode_device:
         return eng.unpack(bam, it, mode, delim)[0]
     return bam.decode(it, mode, delim)

@@ -224,6 +224,25 @@ void ccio_set_deflate_hook(ccio_deflate_fn fn, void *user);
 typedef int (*ccio_inflate_fn)(void *user, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
                                const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out, uint8_t *ok);
 void ccio_set_inflate_hook(ccio_inflate_fn fn, void *user);
+/* The inflate hook that also keeps what it inflated (the device inflater's resident streams:
+ * cc_bgzf_inflate_keep_hook below).  Only the whole-file open (ccio_bam_open) uses it, in place of
+ * the plain hook; the region reads, the header read and ccio_index_bam keep to the plain one.  keep
+ * has ccio_inflate_fn's contract and also receives total, the inflated file's size; through *token
+ * it names its copy of the file, in which every member with ok[j] == 1 lies at uoff[j] (0: it kept
+ * none).  After the CRC checks libccio sends every member the host codec inflated instead (ok[j] ==
+ * 0, or another CRC) through patch(user, token, off, bytes, n): the copy's [off, off + n) becomes
+ * bytes[0 .. n).  When keep returns nonzero or a patch fails, the handle carries no token and the
+ * open proceeds as with the plain hook.  libccio never frees a token: closing a handle calls nothing.
+ * NULL keep unsets the pair. */
+typedef int (*ccio_inflate_keep_fn)(void *user, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
+                                    const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out,
+                                    uint8_t *ok, uint64_t total, int64_t *token);
+typedef int (*ccio_resident_patch_fn)(void *user, int64_t token, uint64_t off, const uint8_t *bytes, uint64_t n);
+void ccio_set_inflate_keep_hook(ccio_inflate_keep_fn keep, ccio_resident_patch_fn patch, void *user);
+/* 1, with the keep hook's token and the offset of b's first record in the inflated file (where its
+ * records end for a file without any), when b came from ccio_bam_open with the keep hook set and its
+ * records are still that stream's own; 0 for views, combined handles and region opens. */
+int ccio_bam_resident(ccio_bam *b, int64_t *token, uint64_t *base);
 /* per value 0..maxv of v[0..n): count and first index (n when absent), one pass (read_families.txt) */
 int ccio_value_census(const int32_t *v, int64_t n, int32_t maxv, int64_t *first, int64_t *count);
 int ccio_write_bam_ex(const char *path, ccio_bam *tmpl, ccio_interner *it, int64_t n, const cc_out_spec *spec,
@@ -390,6 +409,28 @@ int64_t cc_bgzf_inflate(cc_ctx *ctx, const uint8_t *comp, const uint64_t *coff, 
                         const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out, uint8_t *ok);
 /* the pair to hand to ccio_set_inflate_hook; unset the hook before cc_destroy */
 int cc_bgzf_inflate_hook(cc_ctx *ctx, ccio_inflate_fn *fn, void **user);
+/* cc_bgzf_inflate that also leaves the inflated bytes on the device.  out and ok are cc_bgzf_inflate's;
+ * in addition every member with ok[j] == 1 lies at [uoff[j], uoff[j] + ulen[j]) of a new resident
+ * stream: a device buffer of `total` bytes the context owns, named by *resident_id (> 0), which the
+ * kernel writes directly (the rounds' downloads read it).  A refused member's range of it is
+ * unspecified until cc_resident_patch fills it.  Every [uoff[j], uoff[j] + ulen[j]) must lie inside
+ * total and no two may overlap: otherwise CC_E_INVALID, before any launch.  Without device memory
+ * for the stream the call is cc_bgzf_inflate and *resident_id = 0.  cc_destroy frees the streams
+ * that are left. */
+int64_t cc_bgzf_inflate_keep(cc_ctx *ctx, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
+                             const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out, uint8_t *ok,
+                             uint64_t total, int64_t *resident_id);
+/* the pair (and their user) to hand to ccio_set_inflate_keep_hook; unset it before cc_destroy */
+int cc_bgzf_inflate_keep_hook(cc_ctx *ctx, ccio_inflate_keep_fn *keep, ccio_resident_patch_fn *patch, void **user);
+/* [off, off + n) of a resident stream overwritten from host memory (a member the host codec
+ * inflated); done when the call returns.  An id that is unknown, freed or another context's is
+ * CC_E_INVALID here and in every call that takes one, and nothing else happens. */
+int cc_resident_patch(cc_ctx *ctx, int64_t id, uint64_t off, const uint8_t *bytes, uint64_t n);
+int cc_resident_free(cc_ctx *ctx, int64_t id);
+/* test hooks: a resident stream's size, at most cap of its bytes copied to dst (NULL: none); the
+ * number of resident streams the context holds */
+int64_t cc_resident_fetch(cc_ctx *ctx, int64_t id, uint8_t *dst, uint64_t cap);
+int64_t cc_resident_count(cc_ctx *ctx);
 /* Deferred end-of-pass checks (no reference counterpart: the reference has no device).  With
  * deferral on, a stage call that re-runs a planned pass (cc_read_bam_rerun, cc_consensus_maker,
  * cc_duplex_consensus, cc_singleton_correction on a group that ran before) enqueues its check and
@@ -468,6 +509,15 @@ int cc_table_upload(cc_ctx *ctx, const cc_records *rec, int32_t max_len, int32_t
 int cc_table_unpack(cc_ctx *ctx, const uint8_t *recs, uint64_t bytes, const uint64_t *rec_off, int64_t n,
                     const int32_t *cigar_id, const int32_t *bc_id, const int32_t *rg_id, const uint8_t *rflags,
                     int32_t *max_len, int32_t *table_id);
+/* cc_table_unpack with the records read in place from a resident stream (cc_bgzf_inflate_keep): they
+ * are its bytes [base, base + bytes), which must lie inside it (else CC_E_INVALID), and rec_off counts
+ * from base, as ccio_bam_decode_ids gives it.  Checks, errors and the table are cc_table_unpack's;
+ * only rec_off and the four columns are uploaded.  The call waits for the inflater's streams first
+ * and does not free the resident stream.  With profiling on, cc_kernel_times reports cc_table_unpack's
+ * upload of the record stream as "unpack_stream_upload"; this call never adds to it. */
+int cc_table_unpack_resident(cc_ctx *ctx, int64_t id, uint64_t base, uint64_t bytes, const uint64_t *rec_off,
+                             int64_t n, const int32_t *cigar_id, const int32_t *bc_id, const int32_t *rg_id,
+                             const uint8_t *rflags, int32_t *max_len, int32_t *table_id);
 int cc_table_free(cc_ctx *ctx, int32_t table_id);
 /* the table's derived columns (member records, position keys, qname digests, record cores and deep
  * bits, the deep-group list) built again from its record columns, on the context's stream without a
