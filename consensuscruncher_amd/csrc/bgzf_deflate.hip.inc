@@ -17,7 +17,9 @@
 //   pass 2: token bit lengths are prefix-summed per tile and each token ORs its bits into the LDS
 //     words the piece occupied (the piece is dead by then); the words are copied out with plain
 //     vector stores.
-// The CRC32 field is left to the host (it runs while the device encodes).
+// The CRC32 field is left to the host (it runs while the device encodes) unless cc_bgzf_set_crc is on:
+// then k_crc32 (bgzf_crc32.hip.inc) takes the pieces' CRCs from the device input buffer and they come
+// back with the lengths.
 //
 // The kernel is a template over the effort (cc_bgzf_set_effort).  Effort 1 is the encoder above.
 // Effort 2 replaces pass 1's match finder and adds a lazy step; everything from the parse on is
@@ -484,6 +486,10 @@ struct BgzfEnc {
     std::mutex mu;          // one caller at a time (the writers' and readers' threads call concurrently)
     bool ready = false, broken = false, streams = false;
     int effort = 1;         // cc_bgzf_set_effort: read once per round, under mu
+    bool crc_on = false;    // cc_bgzf_set_crc: likewise
+    CrcBufs cb;             // the encoder's CRC values (made by the first round with crc_on)
+    double crc_ms = 0;      // k_crc32 of every caller on these streams (scope bgzf_crc32)
+    int64_t crc_n = 0;
     BgzfDec* dec = nullptr;
     std::string err;
     hipStream_t st[2] = {nullptr, nullptr};
@@ -559,6 +565,7 @@ void bgzf_free(cc_ctx* ctx) {
     for (int b = 0; b < 2; ++b)
         if (E->st[b]) (void)hipStreamSynchronize(E->st[b]);
     bgzf_dec_free(E->dec);
+    crc_bufs_free(&E->cb);
     for (int b = 0; b < 2; ++b) {
         if (E->h_in[b]) (void)hipHostFree(E->h_in[b]);
         if (E->h_out[b]) (void)hipHostFree(E->h_out[b]);
@@ -599,9 +606,35 @@ void bgzf_prof(cc_ctx* ctx, bool reset, double* ms, int64_t* n, double* h2d = nu
     if (n) *n = E->prof_n;
 }
 
+// k_crc32's time so far on the coders' streams (or its reset)
+void bgzf_crc_prof(cc_ctx* ctx, bool reset, double* ms, int64_t* n) {
+    BgzfEnc* E;
+    {
+        std::lock_guard<std::mutex> lk(ctx->bgzf_mu);
+        E = ctx->bgzf;
+    }
+    if (!E) return;
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (reset) { E->crc_ms = 0; E->crc_n = 0; }
+    if (ms) *ms = E->crc_ms;
+    if (n) *n = E->crc_n;
+}
+
+// a finished, timed k_crc32 launch of set B's stream b added to the scope
+int crc_prof_add(BgzfEnc* E, CrcBufs* B, int b) {
+    if (!B->timed[b]) return 0;
+    float ms = 0;
+    BGCHK(hipEventElapsedTime(&ms, B->ev[b][0], B->ev[b][1]));
+    E->crc_ms += ms;
+    E->crc_n += 1;
+    B->timed[b] = false;
+    return 0;
+}
+
 // cc_bgzf_deflate's work.  Launches of BG_CHUNK pieces alternate between two streams, each with
 // its own pinned and device buffers: while one launch encodes, the previous one's members are
-// downloaded and framed and the next one's input is staged; the CRCs are computed meanwhile.
+// downloaded and framed and the next one's input is staged; the CRCs are computed meanwhile, by the
+// calling thread or (crc_on) by k_crc32 over the launch's input buffer, behind its encoder kernels.
 int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, uint8_t* stage, uint64_t slot,
                     uint32_t* out_len, int64_t cap) {
     const int64_t np = (int64_t)((n + BG_PIECE - 1) / BG_PIECE);
@@ -614,9 +647,11 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
     BGCHK(hipSetDevice(ctx->device));   // (not enter(): a writer's thread, the switches are the engine thread's)
     if (!E->ready) RC(bgzf_init(E));
     const bool prof = ctx->profiling;
+    const bool dev_crc = E->crc_on;   // the whole round one way
+    if (dev_crc) BGCHK(crc_bufs_init(&E->cb, BG_CHUNK));
     const auto kernel = E->effort == 2 ? k_bgzf_deflate<2> : k_bgzf_deflate<1>;   // the whole round at one effort
     const int64_t nchunks = (np + BG_CHUNK - 1) / BG_CHUNK;
-    std::vector<uint32_t> crcs((size_t)np);
+    std::vector<uint32_t> crcs(dev_crc ? 0 : (size_t)np);
     auto pieces_of = [&](int64_t k) { return (int)std::min<int64_t>(BG_CHUNK, np - k * BG_CHUNK); };
     auto launch = [&](int64_t k) -> int {
         const int b = (int)(k & 1), pc = pieces_of(k);
@@ -633,6 +668,11 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
         klaunch(E->st[b], k_bgzf_pack, (unsigned)pc, 256, E->d_out[b], E->d_len[b], E->d_pack[b]);
         BGCHK(hipGetLastError());
         BGCHK(hipMemcpyAsync(E->h_len[b], E->d_len[b], (size_t)pc * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[b]));
+        if (dev_crc) {
+            E->cb.timed[b] = prof;
+            BGCHK(crc_launch(E->st[b], prof ? E->cb.ev[b] : nullptr, E->d_in[b], nullptr, CR_PIECE, bytes, E->cb.d[b], pc));
+            BGCHK(hipMemcpyAsync(E->cb.h[b], E->cb.d[b], (size_t)pc * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[b]));
+        }
         return 0;
     };
     auto finish = [&](int64_t k) -> int {
@@ -646,6 +686,7 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
             BGCHK(hipEventElapsedTime(&ms, E->ev[b][2], E->ev[b][3]));
             E->h2d_ms += ms;
         }
+        if (dev_crc) RC(crc_prof_add(E, &E->cb, b));
         uint64_t words = 0;
         for (int j = 0; j < pc; ++j) {
             const uint32_t ln = E->h_len[b][j];
@@ -668,7 +709,7 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
         uint64_t w = 0;
         for (int j = 0; j < pc; ++j) {
             const int64_t p = k * BG_CHUNK + j;
-            const uint32_t ln = E->h_len[b][j], crc = crcs[(size_t)p];
+            const uint32_t ln = E->h_len[b][j], crc = dev_crc ? E->cb.h[b][j] : crcs[(size_t)p];
             uint8_t* m = stage + (uint64_t)p * slot;
             memcpy(m, E->h_out[b] + 4 * w, ln);
             for (int q = 0; q < 4; ++q) m[ln - 8 + q] = (uint8_t)(crc >> (8 * q));
@@ -687,7 +728,7 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
     for (int64_t k = 0; k < nchunks; ++k) {
         BGRC(launch(k));
         const int64_t p0 = k * BG_CHUNK;
-        for (int j = 0; j < pieces_of(k); ++j) {
+        for (int j = 0; !dev_crc && j < pieces_of(k); ++j) {
             const uint64_t o = (uint64_t)(p0 + j) * BG_PIECE;
             crcs[(size_t)(p0 + j)] = E->crc(data + o, (size_t)std::min<uint64_t>(BG_PIECE, n - o));
         }
@@ -731,6 +772,14 @@ int cc_bgzf_set_effort(cc_ctx* ctx, int effort) {
     BgzfEnc* E = bgzf_get(ctx);
     std::lock_guard<std::mutex> lk(E->mu);   // a running round holds it: it finishes at its own effort
     E->effort = effort;
+    return 0;
+}
+
+int cc_bgzf_set_crc(cc_ctx* ctx, int on) {
+    if (!ctx) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);   // a running round holds it: it finishes the way it began
+    E->crc_on = on != 0;
     return 0;
 }
 

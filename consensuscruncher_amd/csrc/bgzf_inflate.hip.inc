@@ -1,7 +1,9 @@
 // The device BGZF inflater (cc_bgzf_inflate, cc_bgzf_inflate_hook) and the resident streams it can
 // leave on the device (cc_bgzf_inflate_keep, cc_resident_*): included by cc_engine.hip after
 // bgzf_deflate.hip.inc, whose streams, mutex and "nothing more on the device after a HIP error" latch
-// they share.
+// they share.  With a crc pointer (cc_bgzf_inflate_crc, cc_bgzf_inflate_keep_crc) every round is followed
+// by k_crc32 (bgzf_crc32.hip.inc); cc_crc32 and cc_resident_crc32, that kernel's function-level entry
+// points, are at the end of this file because they need the streams and the resident table.
 //
 // k_bgzf_inflate: one wave (a 64-thread workgroup) per member, many members in flight.  DEFLATE is
 // serial in bit order, so a member advances in batches of three steps:
@@ -210,6 +212,7 @@ struct BgzfDec {
     bool timed[2] = {false, false};
     double prof_ms = 0, h2d_ms = 0, d2h_ms = 0;   // scopes bgzf_inflate, bgzf_in_upload, bgzf_in_download
     int64_t prof_n = 0;
+    CrcBufs cb;   // the members' CRCs (made by the first round that is asked for them)
 };
 
 namespace {
@@ -248,6 +251,7 @@ void bgzf_dec_free(BgzfDec* D) {   // the streams are idle (bgzf_free synchronis
             if (D->ev[b][k]) (void)hipEventDestroy(D->ev[b][k]);
     }
     for (auto& r : D->res) (void)hipFree(r.second.p);
+    crc_bufs_free(&D->cb);
     delete D;
 }
 
@@ -289,9 +293,12 @@ Resident* resident_find(BgzfEnc* E, int64_t id) {
 // With a resident stream R (cc_bgzf_inflate_keep) the kernel writes member j at R's byte uoff[j]
 // instead of into the round's output buffer: the round's base is its first member's uoff, desc.z the
 // 32-bit distance from it, and the round's download is its span of R.
+// With crc (cc_bgzf_inflate_crc, cc_bgzf_inflate_keep_crc) every round's k_bgzf_inflate is followed on
+// its stream by k_crc32 over the same descriptors and output base, and crc[j], the CRC32 of the bytes
+// the device wrote for member j, comes back with the status words (0 where ok[j] == 0).
 int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen,
                     const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok,
-                    const Resident* R = nullptr) {
+                    const Resident* R = nullptr, uint32_t* crc = nullptr) {
     if (members == 0) return 0;
     if (members < 0 || !comp || !coff || !clen || !uoff || !ulen || !out || !ok) {
         E->err = "cc_bgzf_inflate: null argument or a negative member count";
@@ -300,6 +307,7 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
     RC(bgzf_dec_enter(ctx, E));
     BgzfDec* D = E->dec;
     const bool prof = ctx->profiling;
+    if (crc) BGCHK(crc_bufs_init(&D->cb, BI_ROUND));
     // the rounds: [first[k], first[k + 1]) of the members the device takes (BGZF's bounds; others stay ok = 0)
     std::vector<int64_t> idx, first;
     std::vector<uint64_t> rbase, rspan;   // with R: each round's lowest byte of R and the bytes it spans
@@ -310,6 +318,7 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
         first.push_back(0);
         for (int64_t j = 0; j < members; ++j) {
             ok[j] = 0;
+            if (crc) crc[j] = 0;
             if (clen[j] > BI_MEMBER || ulen[j] > BI_MEMBER) continue;
             const size_t ib = bi_align(clen[j]);
             // the round's output bytes with this member: packed 16-B slots, or with R the span from its base
@@ -358,9 +367,14 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
         klaunch(E->st[b], k_bgzf_inflate, (unsigned)n, BI_T, D->d_in[b], D->d_desc[b], d_base, D->d_ok[b], n);
         BGCHK(hipGetLastError());
         if (prof) BGCHK(hipEventRecord(D->ev[b][1], E->st[b]));
+        if (crc) {
+            D->cb.timed[b] = prof;
+            BGCHK(crc_launch(E->st[b], prof ? D->cb.ev[b] : nullptr, d_base, D->d_desc[b], CR_MEMBER, 0, D->cb.d[b], n));
+        }
         if (prof) BGCHK(hipEventRecord(D->ev[b][4], E->st[b]));
         if (out_b) BGCHK(hipMemcpyAsync(D->h_out[b], d_base, out_b, hipMemcpyDeviceToHost, E->st[b]));
         BGCHK(hipMemcpyAsync(D->h_ok[b], D->d_ok[b], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[b]));
+        if (crc) BGCHK(hipMemcpyAsync(D->cb.h[b], D->cb.d[b], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[b]));
         if (prof) BGCHK(hipEventRecord(D->ev[b][5], E->st[b]));
         return 0;
     };
@@ -379,10 +393,12 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
             BGCHK(hipEventElapsedTime(&ms, D->ev[b][4], D->ev[b][5]));
             D->d2h_ms += ms;
         }
+        if (crc) RC(crc_prof_add(E, &D->cb, b));
         for (int i = 0; i < n; ++i) {
             if (D->h_ok[b][i] != 1) continue;
             const int64_t j = idx[(size_t)(first[k] + i)];
             memcpy(out + uoff[j], D->h_out[b] + D->h_desc[b][i].z, ulen[j]);
+            if (crc) crc[j] = D->cb.h[b][i];
             ok[j] = 1;
             ++good;
         }
@@ -409,7 +425,7 @@ int64_t bgzf_decode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t
 // call is cc_bgzf_inflate's and *id stays 0.
 int64_t bgzf_decode_keep(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen,
                          const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok,
-                         uint64_t total, int64_t* id) {
+                         uint64_t total, int64_t* id, uint32_t* crc = nullptr) {
     *id = 0;
     if (members < 0 || (members > 0 && (!comp || !coff || !clen || !uoff || !ulen || !out || !ok))) {
         E->err = "cc_bgzf_inflate_keep: null argument or a negative member count";
@@ -441,7 +457,7 @@ int64_t bgzf_decode_keep(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uin
     const size_t padded = bi_align((size_t)total) + 32;
     if (hipMalloc((void**)&R.p, padded) != hipSuccess) {
         (void)hipGetLastError();   // (out of memory is no reason for the latch)
-        return bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok);
+        return bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, nullptr, crc);
     }
     int64_t r = CC_E_HIP;
     hipError_t e = hipMemsetAsync(R.p + total, 0, padded - (size_t)total, E->st[0]);
@@ -450,7 +466,7 @@ int64_t bgzf_decode_keep(cc_ctx* ctx, BgzfEnc* E, const uint8_t* comp, const uin
         E->err = std::string("HIP error ") + hipGetErrorString(e) + " zeroing a resident stream's tail";
         E->broken = true;
     } else {
-        r = bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, &R);
+        r = bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, &R, crc);
     }
     if (r < 0) {   // (bgzf_decode drained both streams)
         (void)hipFree(R.p);
@@ -492,6 +508,80 @@ int bgzf_keep_hook_fn(void* user, const uint8_t* comp, const uint64_t* coff, con
     BgzfEnc* E = bgzf_get(ctx);
     std::lock_guard<std::mutex> lk(E->mu);
     return bgzf_decode_keep(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, total, token) < 0 ? 1 : 0;
+}
+
+// ccio_inflate_crc_fn and ccio_inflate_keep_crc_fn over a context: the two above with the members' CRCs
+int bgzf_inflate_crc_hook_fn(void* user, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen,
+                             const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok,
+                             uint32_t* crc) {
+    cc_ctx* ctx = (cc_ctx*)user;
+    if (!ctx || !crc) return 1;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    return bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, nullptr, crc) < 0 ? 1 : 0;
+}
+
+int bgzf_keep_crc_hook_fn(void* user, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen, const uint64_t* uoff,
+                          const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok, uint64_t total, int64_t* token,
+                          uint32_t* crc) {
+    cc_ctx* ctx = (cc_ctx*)user;
+    if (!ctx || !token || !crc) return 1;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    return bgzf_decode_keep(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, total, token, crc) < 0 ? 1 : 0;
+}
+
+// cc_crc32's and cc_resident_crc32's work: the CRC32 of n ranges of the device bytes [base, base +
+// limit), whose allocation covers every aligned 16-byte word that overlaps them.  A range longer
+// than a segment is cut on the host and its segments' CRCs are joined with crc_core.h's combine.
+int crc_ranges(cc_ctx* ctx, BgzfEnc* E, const char* who, const uint8_t* base, uint64_t limit, const uint64_t* off,
+               const uint64_t* len, int64_t n, uint32_t* out) {
+    std::vector<uint4> seg;
+    for (int64_t i = 0; i < n; ++i) {
+        if (off[i] > limit || len[i] > limit - off[i]) {
+            E->err = std::string(who) + ": range " + std::to_string((long long)i) + " does not lie inside the bytes";
+            return CC_E_INVALID;
+        }
+        for (uint64_t o = 0; o < len[i]; o += crc::SEGMENT) {
+            const uint64_t a = off[i] + o;
+            seg.push_back(make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)std::min<uint64_t>(crc::SEGMENT, len[i] - o), 0));
+        }
+    }
+    if (seg.size() > 0x7fffffffu) {
+        E->err = std::string(who) + ": too many segments for one call";
+        return CC_E_INVALID;
+    }
+    std::vector<uint32_t> got(seg.size());
+    if (!seg.empty()) {
+        const bool prof = ctx->profiling;
+        uint4* d_seg = nullptr;
+        uint32_t* d_crc = nullptr;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        hipError_t e = hipMalloc((void**)&d_seg, seg.size() * sizeof(uint4));
+        if (e == hipSuccess) e = hipMalloc((void**)&d_crc, seg.size() * sizeof(uint32_t));
+        for (int k = 0; k < 2 && prof && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_seg, seg.data(), seg.size() * sizeof(uint4), hipMemcpyHostToDevice, E->st[0]);
+        if (e == hipSuccess) e = crc_launch(E->st[0], prof ? ev : nullptr, base, d_seg, CR_SEG, 0, d_crc, (int)seg.size());
+        if (e == hipSuccess) e = hipMemcpyAsync(got.data(), d_crc, got.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[0]);
+        const hipError_t es = hipStreamSynchronize(E->st[0]);   // (also after a failure: the buffers are freed below)
+        if (e == hipSuccess) e = es;
+        float ms = 0;
+        if (e == hipSuccess && prof) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+        if (e == hipSuccess && prof) { E->crc_ms += ms; E->crc_n += 1; }
+        for (int k = 0; k < 2; ++k)
+            if (ev[k]) (void)hipEventDestroy(ev[k]);
+        if (d_seg) (void)hipFree(d_seg);
+        if (d_crc) (void)hipFree(d_crc);
+        BGCHK(e);
+    }
+    size_t s = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t c = 0;
+        for (uint64_t o = 0; o < len[i]; o += crc::SEGMENT, ++s)
+            c = o ? crc::combine(c, got[s], std::min<uint64_t>(crc::SEGMENT, len[i] - o)) : got[s];
+        out[i] = c;
+    }
+    return 0;
 }
 
 int bgzf_patch_hook_fn(void* user, int64_t token, uint64_t off, const uint8_t* bytes, uint64_t n) {
@@ -591,6 +681,97 @@ int64_t cc_resident_count(cc_ctx* ctx) {
     BgzfEnc* E = bgzf_get(ctx);
     std::lock_guard<std::mutex> lk(E->mu);
     return E->dec ? (int64_t)E->dec->res.size() : 0;
+}
+
+int64_t cc_bgzf_inflate_crc(cc_ctx* ctx, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen,
+                            const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok,
+                            uint32_t* crc) {
+    if (!ctx || (members > 0 && !crc)) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const int64_t r = bgzf_decode(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, nullptr, crc);
+    if (r < 0) ctx->err = E->err;
+    return r;
+}
+
+int cc_bgzf_inflate_crc_hook(cc_ctx* ctx, ccio_inflate_crc_fn* fn, void** user) {
+    if (!ctx || !fn || !user) return CC_E_INVALID;
+    *fn = bgzf_inflate_crc_hook_fn;
+    *user = ctx;
+    return 0;
+}
+
+int64_t cc_bgzf_inflate_keep_crc(cc_ctx* ctx, const uint8_t* comp, const uint64_t* coff, const uint32_t* clen,
+                                 const uint64_t* uoff, const uint32_t* ulen, int64_t members, uint8_t* out, uint8_t* ok,
+                                 uint64_t total, int64_t* resident_id, uint32_t* crc) {
+    if (!ctx || !resident_id || (members > 0 && !crc)) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const int64_t r = bgzf_decode_keep(ctx, E, comp, coff, clen, uoff, ulen, members, out, ok, total, resident_id, crc);
+    if (r < 0) ctx->err = E->err;
+    return r;
+}
+
+int cc_bgzf_inflate_keep_crc_hook(cc_ctx* ctx, ccio_inflate_keep_crc_fn* keep, ccio_resident_patch_fn* patch, void** user) {
+    if (!ctx || !keep || !patch || !user) return CC_E_INVALID;
+    *keep = bgzf_keep_crc_hook_fn;
+    *patch = bgzf_patch_hook_fn;
+    *user = ctx;
+    return 0;
+}
+
+int cc_crc32(cc_ctx* ctx, const uint8_t* data, uint64_t nbytes, const uint64_t* off, const uint64_t* len, int64_t n,
+             uint32_t* crc) {
+    if (!ctx) return CC_E_INVALID;
+    if (n == 0) return 0;
+    if (n < 0 || !off || !len || !crc || (nbytes > 0 && !data)) {
+        ctx->err = "cc_crc32: null argument or a negative range count";
+        return CC_E_INVALID;
+    }
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    auto work = [&]() -> int {
+        if (E->broken) return CC_E_HIP;
+        BGCHK(hipSetDevice(ctx->device));
+        RC(bgzf_streams(E));
+        // the upload, padded like a resident stream: every aligned word that overlaps a range is allocated
+        uint8_t* d = nullptr;
+        if (hipMalloc((void**)&d, bi_align((size_t)nbytes) + 32) != hipSuccess) {
+            (void)hipGetLastError();   // (out of memory is no reason for the latch)
+            E->err = "cc_crc32: no device memory for the bytes";
+            return CC_E_HIP;
+        }
+        hipError_t e = nbytes ? hipMemcpyAsync(d, data, (size_t)nbytes, hipMemcpyHostToDevice, E->st[0]) : hipSuccess;
+        int rc = 0;
+        if (e == hipSuccess) rc = crc_ranges(ctx, E, "cc_crc32", d, nbytes, off, len, n, crc);
+        (void)hipStreamSynchronize(E->st[0]);
+        (void)hipFree(d);
+        BGCHK(e);
+        return rc;
+    };
+    const int rc = work();
+    if (rc) ctx->err = E->err;
+    return rc;
+}
+
+int cc_resident_crc32(cc_ctx* ctx, int64_t id, const uint64_t* off, const uint64_t* len, int64_t n, uint32_t* crc) {
+    if (!ctx) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const Resident* R = resident_find(E, id);
+    int rc = 0;
+    if (!R) {
+        E->err = "cc_resident_crc32: unknown id";
+        rc = CC_E_INVALID;
+    } else if (n < 0 || (n > 0 && (!off || !len || !crc))) {
+        E->err = "cc_resident_crc32: null argument or a negative range count";
+        rc = CC_E_INVALID;
+    } else if (n > 0) {
+        rc = bgzf_dec_enter(ctx, E);
+        if (!rc) rc = crc_ranges(ctx, E, "cc_resident_crc32", R->p, R->total, off, len, n, crc);
+    }
+    if (rc) ctx->err = E->err;
+    return rc;
 }
 
 }  // extern "C"

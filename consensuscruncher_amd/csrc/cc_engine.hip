@@ -6125,6 +6125,7 @@ int duplex_tail(cc_ctx* ctx, Group& g, const DuplexBufs& d, int64_t Q, PT id, in
 
 }  // namespace
 
+#include "bgzf_crc32.hip.inc"
 #include "bgzf_deflate.hip.inc"
 #include "bgzf_inflate.hip.inc"
 
@@ -6193,6 +6194,7 @@ int cc_set_profiling(cc_ctx* ctx, int on) {
     if (on) ctx->prof.clear();
     if (on) bgzf_prof(ctx, true, nullptr, nullptr);
     if (on) bgzf_dec_prof(ctx, true, nullptr, nullptr, nullptr, nullptr);
+    if (on) bgzf_crc_prof(ctx, true, nullptr, nullptr);
     return 0;
 }
 
@@ -6231,6 +6233,12 @@ int cc_kernel_times(cc_ctx* ctx, char* names, int names_cap, double* ms, int64_t
             ctx->prof["bgzf_in_upload"] = {up, in};
             ctx->prof["bgzf_in_download"] = {down, in};
         }
+    }
+    {   // and the CRC kernel both of them (and cc_crc32) launch
+        double cms = 0;
+        int64_t cn = 0;
+        bgzf_crc_prof(ctx, false, &cms, &cn);
+        if (cn) ctx->prof["bgzf_crc32"] = {cms, cn};
     }
     int i = 0;
     std::string all;

@@ -235,6 +235,13 @@ void* g_ihook_user = nullptr;
 ccio_inflate_keep_fn g_khook_keep = nullptr;
 ccio_resident_patch_fn g_khook_patch = nullptr;
 void* g_khook_user = nullptr;
+// their siblings that bring a CRC of their own (ccio_set_inflate_crc_hook, ccio_set_inflate_keep_crc_hook):
+// while set, each takes its plain sibling's place
+ccio_inflate_crc_fn g_ichook_fn = nullptr;
+void* g_ichook_user = nullptr;
+ccio_inflate_keep_crc_fn g_kchook_keep = nullptr;
+ccio_resident_patch_fn g_kchook_patch = nullptr;
+void* g_kchook_user = nullptr;
 
 // what a keep hook's copy of an inflated file needs: its size going in; coming out, the token and the
 // pair to patch it through (token 0: nothing was kept)
@@ -248,25 +255,35 @@ struct KeptCopy {
 // The non-empty members of blk (fields coff / clen / doff / dlen by the accessors) through the hook.
 // done[i] = 1 for every member the hook reports inflated AND whose bytes have the CRC32 the member
 // carries (the word behind its payload); every other member is left to the host codec.  With kept
-// (the whole-file open) and a keep hook set, that hook is called in the plain one's place.
+// (the whole-file open) and a keep hook set, that hook is called in the plain one's place.  A crc hook
+// stands in for its plain sibling; its members are judged by the CRC it reports for its own bytes
+// (crc[j] against the member's field) and no CRC is computed here.
 template <class Blk, class C, class L, class U, class N>
 void hook_inflate(const uint8_t* comp, uint8_t* out, const std::vector<Blk>& blk, C coff, L clen, U doff, N dlen,
                   int nthreads, std::vector<uint8_t>& done, KeptCopy* kept = nullptr) {
     done.assign(blk.size(), 0);
     ccio_inflate_fn fn;
     ccio_inflate_keep_fn keep = nullptr;
+    ccio_inflate_crc_fn cfn;
+    ccio_inflate_keep_crc_fn ckeep = nullptr;
     void* user;
     {
         std::lock_guard<std::mutex> lk(g_ihook_mu);
         fn = g_ihook_fn;
         user = g_ihook_user;
-        if (kept && g_khook_keep) {
+        cfn = g_ichook_fn;
+        if (cfn) user = g_ichook_user;
+        if (kept && g_kchook_keep) {
+            ckeep = g_kchook_keep;
+            kept->patch = g_kchook_patch;
+            kept->user = user = g_kchook_user;
+        } else if (kept && g_khook_keep) {
             keep = g_khook_keep;
             kept->patch = g_khook_patch;
             kept->user = user = g_khook_user;
         }
     }
-    if (!fn && !keep) return;
+    if (!fn && !keep && !cfn && !ckeep) return;
     std::vector<size_t> which;
     std::vector<uint64_t> co, uo;
     std::vector<uint32_t> cl, ul;
@@ -280,6 +297,26 @@ void hook_inflate(const uint8_t* comp, uint8_t* out, const std::vector<Blk>& blk
     }
     if (which.empty()) return;
     std::vector<uint8_t> ok(which.size(), 0);
+    auto field = [&](int64_t j) {   // member j's CRC32 field: the word behind its payload
+        const uint8_t* t = comp + co[(size_t)j] + cl[(size_t)j];
+        return (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+    };
+    if (ckeep || (cfn && !keep)) {
+        std::vector<uint32_t> crc(which.size(), 0);
+        if (ckeep) {
+            if (ckeep(user, comp, co.data(), cl.data(), uo.data(), ul.data(), (int64_t)which.size(), out, ok.data(),
+                      kept->total, &kept->token, crc.data()) != 0) {
+                kept->token = 0;
+                return;
+            }
+        } else if (cfn(user, comp, co.data(), cl.data(), uo.data(), ul.data(), (int64_t)which.size(), out, ok.data(),
+                       crc.data()) != 0) {
+            return;
+        }
+        for (size_t j = 0; j < which.size(); ++j)
+            if (ok[j] == 1 && crc[j] == field((int64_t)j)) done[which[j]] = 1;
+        return;
+    }
     if (keep) {
         if (keep(user, comp, co.data(), cl.data(), uo.data(), ul.data(), (int64_t)which.size(), out, ok.data(),
                  kept->total, &kept->token) != 0) {
@@ -293,9 +330,7 @@ void hook_inflate(const uint8_t* comp, uint8_t* out, const std::vector<Blk>& blk
         Codec c;
         for (int64_t j = b; j < e; ++j) {
             if (!ok[(size_t)j]) continue;
-            const uint8_t* t = comp + co[(size_t)j] + cl[(size_t)j];
-            const uint32_t want = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-            if (c.crc32_of(out + uo[(size_t)j], ul[(size_t)j]) == want) done[which[(size_t)j]] = 1;
+            if (c.crc32_of(out + uo[(size_t)j], ul[(size_t)j]) == field(j)) done[which[(size_t)j]] = 1;
         }
     });
 }
@@ -761,6 +796,20 @@ void ccio_set_inflate_keep_hook(ccio_inflate_keep_fn keep, ccio_resident_patch_f
     g_khook_keep = keep;
     g_khook_patch = keep ? patch : nullptr;
     g_khook_user = keep ? user : nullptr;
+}
+
+// the same two with a CRC of their own: each stands in for its plain sibling while set
+void ccio_set_inflate_crc_hook(ccio_inflate_crc_fn fn, void* user) {
+    std::lock_guard<std::mutex> lk(g_ihook_mu);
+    g_ichook_fn = fn;
+    g_ichook_user = fn ? user : nullptr;
+}
+
+void ccio_set_inflate_keep_crc_hook(ccio_inflate_keep_crc_fn keep, ccio_resident_patch_fn patch, void* user) {
+    std::lock_guard<std::mutex> lk(g_ihook_mu);
+    g_kchook_keep = keep;
+    g_kchook_patch = keep ? patch : nullptr;
+    g_kchook_user = keep ? user : nullptr;
 }
 
 // waits for every CCIO_W_ASYNC write; -1 (ccio_last_error: the first failure) when one failed

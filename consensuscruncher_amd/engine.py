@@ -352,6 +352,9 @@ class Engine(object):
         self.decode_device = False
         self.resident_device = False
         self._keep_wired = False
+        self.crc_device = False
+        if os.environ.get("CC_CRC_DEVICE") == "1":   # before the hooks below are wired: they take the crc variants
+            self.device_crc(True)
         if os.environ.get("CC_RESIDENT_DEVICE") == "1":
             self.device_resident(True)
         if os.environ.get("CC_BGZF_EFFORT"):   # the encoder's effort, for CC_BGZF_DEVICE and bgzf_deflate alike
@@ -386,28 +389,74 @@ class Engine(object):
         self._sync_keep()
         return was
 
-    def _sync_keep(self):
+    def _sync_keep(self, rewire=False):
         """libccio's keep hook (cc_bgzf_inflate_keep_hook -> ccio_set_inflate_keep_hook) wired exactly
         while this engine has device_inflate, device_decode and device_resident on, with the inflate
-        hook's one-owner rules."""
+        hook's one-owner rules.  While device_crc is on the hook wired is its crc variant
+        (cc_bgzf_inflate_keep_crc_hook -> ccio_set_inflate_keep_crc_hook); rewire: the variant changed."""
         global _KEEP_OWNER
         want = bool(self.h) and self.inflate_device and self.decode_device and self.resident_device
-        if want == self._keep_wired:
+        if want == self._keep_wired and not (rewire and want):
             return
         io = N.io()
         if want:
             keep, patch, user = N.P(), N.P(), N.P()
-            self._check(self.lib.cc_bgzf_inflate_keep_hook(self.h, C.byref(keep), C.byref(patch), C.byref(user)))
+            get = self.lib.cc_bgzf_inflate_keep_crc_hook if self.crc_device else self.lib.cc_bgzf_inflate_keep_hook
+            self._check(get(self.h, C.byref(keep), C.byref(patch), C.byref(user)))
             prev = _KEEP_OWNER
             if prev is not None and prev is not self:
                 prev._keep_wired = False
-            io.ccio_set_inflate_keep_hook(keep, patch, user)
+            if self.crc_device:   # one variant at a time: the other is the previous owner's, or this engine's old one
+                io.ccio_set_inflate_keep_crc_hook(keep, patch, user)
+                io.ccio_set_inflate_keep_hook(None, None, None)
+            else:
+                io.ccio_set_inflate_keep_hook(keep, patch, user)
+                io.ccio_set_inflate_keep_crc_hook(None, None, None)
             _KEEP_OWNER = self
             self._keep_wired = True
             return
         io.ccio_set_inflate_keep_hook(None, None, None)
+        io.ccio_set_inflate_keep_crc_hook(None, None, None)
         _KEEP_OWNER = None
         self._keep_wired = False
+
+    def _wire_inflate(self):
+        """This engine's inflate hook handed to libccio: the plain one, or with device_crc on its crc
+        variant (cc_bgzf_inflate_crc_hook -> ccio_set_inflate_crc_hook); the other variant is unset."""
+        io = N.io()
+        fn, user = N.P(), N.P()
+        get = self.lib.cc_bgzf_inflate_crc_hook if self.crc_device else self.lib.cc_bgzf_inflate_hook
+        self._check(get(self.h, C.byref(fn), C.byref(user)))
+        if self.crc_device:
+            io.ccio_set_inflate_crc_hook(fn, user)
+            io.ccio_set_inflate_hook(None, None)
+        else:
+            io.ccio_set_inflate_hook(fn, user)
+            io.ccio_set_inflate_crc_hook(None, None)
+
+    def device_crc(self, on):
+        """Switches the device CRC32 (k_crc32) on or off (off is the default) for both BGZF directions.
+        While it is on, device_inflate and the resident path wire the crc variants of their hooks:
+        the device reports each member's CRC32 over the bytes it wrote (with a resident stream, the
+        bytes the unpacker reads) and libccio compares that with the member's field instead of
+        computing a CRC over the downloaded copy; and the device encoder (device_bgzf, bgzf_deflate)
+        takes its members' CRC32 fields from the device input buffer (cc_bgzf_set_crc) instead of
+        the calling thread.  The bytes read and the members written are the same either way.
+        Toggling while hooks are wired re-wires them; with device_bgzf on it first waits for the
+        background writes.  Without device_inflate or device_bgzf it has no effect and raises nothing.
+        A per-engine switch.  Returns the previous state."""
+        was = self.crc_device
+        on = bool(on)
+        if on == was:
+            return was
+        if self.bgzf_device and N.io().ccio_flush() != 0:   # a file's CRC fields come from one place throughout
+            raise IOError(N.io_error())
+        self._check(self.lib.cc_bgzf_set_crc(self.h, int(on)))
+        self.crc_device = on
+        if self.inflate_device:
+            self._wire_inflate()
+        self._sync_keep(rewire=True)
+        return was
 
     @property
     def bgzf_effort(self):
@@ -482,7 +531,9 @@ class Engine(object):
         from reads inflate_device False from then on, and that engine's close or unwiring leaves the
         new owner's hook alone.  Reads are synchronous, so there is nothing to wait for.  With
         device_decode and device_resident on as well, the hook that keeps resident streams is wired
-        with it (and unwired with it).  Returns the previous state."""
+        with it (and unwired with it).  With device_crc on, the hooks wired are their crc variants:
+        the device reports each member's CRC32 and libccio compares it with the member's field.
+        Returns the previous state."""
         global _INFLATE_OWNER
         was = self.inflate_device
         on = bool(on)
@@ -490,27 +541,27 @@ class Engine(object):
             return was
         io = N.io()
         if on:
-            fn, user = N.P(), N.P()
-            self._check(self.lib.cc_bgzf_inflate_hook(self.h, C.byref(fn), C.byref(user)))
             prev = _INFLATE_OWNER
             if prev is not None and prev is not self:
                 prev.inflate_device = False
                 prev._sync_keep()
-            io.ccio_set_inflate_hook(fn, user)
+            self._wire_inflate()
             _INFLATE_OWNER = self
             self.inflate_device = True
             self._sync_keep()
             return was
         io.ccio_set_inflate_hook(None, None)
+        io.ccio_set_inflate_crc_hook(None, None)
         _INFLATE_OWNER = None
         self.inflate_device = False
         self._sync_keep()
         return was
 
-    def bgzf_inflate(self, raw):
+    def bgzf_inflate(self, raw, crc=False):
         """cc_bgzf_inflate over the bytes of a BGZF file or run of members: (data, ok_list), data the
         members' inflated bytes side by side (ISIZE bytes each; a refused member's are unspecified),
-        ok_list one bool per member."""
+        ok_list one bool per member.  crc=True: cc_bgzf_inflate_crc, and (data, ok_list, crcs) with the
+        device's CRC32 of every member's bytes (meaningful where ok)."""
         raw = bytes(raw)
         coff, clen, uoff, ulen = [], [], [], []
         off = total = 0
@@ -539,11 +590,43 @@ class Engine(object):
         ok = np.zeros(max(n, 1), np.uint8)
         a = [np.asarray(v if n else [0], t) for v, t in ((coff, np.uint64), (clen, np.uint32), (uoff, np.uint64),
                                                          (ulen, np.uint32))]
-        got = int(self.lib.cc_bgzf_inflate(self.h, N.ptr(comp) if comp.size else None, N.ptr(a[0]), N.ptr(a[1]),
-                                           N.ptr(a[2]), N.ptr(a[3]), n, N.ptr(out), N.ptr(ok)))
+        args = (self.h, N.ptr(comp) if comp.size else None, N.ptr(a[0]), N.ptr(a[1]), N.ptr(a[2]), N.ptr(a[3]), n,
+                N.ptr(out), N.ptr(ok))
+        crcs = np.zeros(max(n, 1), np.uint32)
+        got = int(self.lib.cc_bgzf_inflate_crc(*(args + (N.ptr(crcs),))) if crc else self.lib.cc_bgzf_inflate(*args))
         if got < 0:
             raise N.CCError(got, self.lib.cc_last_error(self.h).decode(errors="replace"))
+        if crc:
+            return out[:total].tobytes(), [bool(v) for v in ok[:n]], [int(v) for v in crcs[:n]]
         return out[:total].tobytes(), [bool(v) for v in ok[:n]]
+
+    @staticmethod
+    def _ranges(ranges):
+        if any(int(r[0]) < 0 or int(r[1]) < 0 for r in ranges):
+            raise ValueError("a range is (offset, length), both >= 0")
+        off = np.asarray([int(r[0]) for r in ranges] or [0], np.uint64)
+        ln = np.asarray([int(r[1]) for r in ranges] or [0], np.uint64)
+        return off, ln
+
+    def crc32(self, data, ranges=None):
+        """cc_crc32: the CRC32 (zlib's) of every (offset, length) range of data (bytes-like), computed by
+        k_crc32, as a list of ints; ranges may overlap and be of any length.  ranges=None: the CRC of
+        the whole buffer, a list of one."""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        ranges = [(0, buf.size)] if ranges is None else list(ranges)
+        off, ln = self._ranges(ranges)
+        out = np.zeros(max(len(ranges), 1), np.uint32)
+        self._check(self.lib.cc_crc32(self.h, N.ptr(buf) if buf.size else None, buf.size, N.ptr(off), N.ptr(ln),
+                                      len(ranges), N.ptr(out)))
+        return [int(v) for v in out[:len(ranges)]]
+
+    def resident_crc32(self, rid, ranges):
+        """cc_resident_crc32: the same over the bytes of resident stream rid, in place."""
+        ranges = list(ranges)
+        off, ln = self._ranges(ranges)
+        out = np.zeros(max(len(ranges), 1), np.uint32)
+        self._check(self.lib.cc_resident_crc32(self.h, int(rid), N.ptr(off), N.ptr(ln), len(ranges), N.ptr(out)))
+        return [int(v) for v in out[:len(ranges)]]
 
     def bgzf_deflate(self, data, effort=None):
         """cc_bgzf_deflate: the framed BGZF members of data (bytes-like), one per 0xff00-byte piece,

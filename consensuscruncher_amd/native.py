@@ -86,6 +86,12 @@ INFLATE_KEEP_FN = C.CFUNCTYPE(C.c_int, P, P, C.POINTER(C.c_uint64), C.POINTER(C.
                               C.POINTER(C.c_uint32), C.c_int64, P, C.POINTER(C.c_uint8), C.c_uint64,
                               C.POINTER(C.c_int64))
 RESIDENT_PATCH_FN = C.CFUNCTYPE(C.c_int, P, C.c_int64, C.c_uint64, P, C.c_uint64)
+# ccio_inflate_crc_fn and ccio_inflate_keep_crc_fn: their plain siblings, then crc
+INFLATE_CRC_FN = C.CFUNCTYPE(C.c_int, P, P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                             C.POINTER(C.c_uint32), C.c_int64, P, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32))
+INFLATE_KEEP_CRC_FN = C.CFUNCTYPE(C.c_int, P, P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint32), C.c_int64, P, C.POINTER(C.c_uint8), C.c_uint64,
+                                  C.POINTER(C.c_int64), C.POINTER(C.c_uint32))
 
 _io = None
 _amd = None
@@ -96,6 +102,8 @@ IO_SIGS = {
     "ccio_set_deflate_hook": (None, [P, P]),
     "ccio_set_inflate_hook": (None, [P, P]),
     "ccio_set_inflate_keep_hook": (None, [P, P, P]),
+    "ccio_set_inflate_crc_hook": (None, [P, P]),
+    "ccio_set_inflate_keep_crc_hook": (None, [P, P, P]),
     "ccio_bam_resident": (C.c_int, [P, i64p, C.POINTER(C.c_uint64)]),
     "ccio_value_census": (C.c_int, [P, C.c_int64, C.c_int32, P, P]),
     "ccio_interner_new": (P, []),
@@ -172,6 +180,13 @@ AMD_SIGS = {
     "cc_resident_free": (C.c_int, [P, C.c_int64]),
     "cc_resident_fetch": (C.c_int64, [P, C.c_int64, P, C.c_uint64]),
     "cc_resident_count": (C.c_int64, [P]),
+    "cc_crc32": (C.c_int, [P, P, C.c_uint64, P, P, C.c_int64, P]),
+    "cc_resident_crc32": (C.c_int, [P, C.c_int64, P, P, C.c_int64, P]),
+    "cc_bgzf_inflate_crc": (C.c_int64, [P, P, P, P, P, P, C.c_int64, P, P, P]),
+    "cc_bgzf_inflate_keep_crc": (C.c_int64, [P, P, P, P, P, P, C.c_int64, P, P, C.c_uint64, i64p, P]),
+    "cc_bgzf_inflate_crc_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
+    "cc_bgzf_inflate_keep_crc_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
+    "cc_bgzf_set_crc": (C.c_int, [P, C.c_int]),
     "cc_defer": (C.c_int, [P, C.c_int]),
     "cc_commit": (C.c_int, [P]),
     "cc_debug_skew_plan": (C.c_int, [P, C.c_int32, C.c_char_p, C.c_int64]),

@@ -52,7 +52,7 @@ def cleanup(sd, identifier, scorrect):
 
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
-                       bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host"):
+                       bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host", crc="host"):
     """bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
     output files: same records, other compressed bytes and .bai offsets).  bgzf_effort: the device
     encoder's effort, 1 (the default) or 2 (smaller files, a slower kernel); 2 needs bgzf="device",
@@ -63,7 +63,21 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
     outputs).  resident: "host" (the default) or "device" (the bytes the device inflater produced stay
     in a device buffer that the record unpacker reads in place, Engine.device_resident: the same
     tables again); it engages only with inflate="device" and decode="device" and is otherwise without
-    effect.  Each option is wired for this call only; see _consensus_pipeline."""
+    effect.  crc: "host" (the default) or "device" (Engine.device_crc: the device inflater's members are
+    judged by a CRC32 the device computes over its own bytes, and the device encoder's CRC32 fields
+    come from the device; same bytes read, same files written); it engages only with inflate="device"
+    or bgzf="device" and is otherwise without effect.  Each option is wired for this call only; see
+    _consensus_pipeline."""
+    if crc not in ("host", "device"):
+        raise ValueError('crc must be "host" or "device"')
+    if crc == "device":
+        engine = engine or get_engine()
+        was_crc = engine.device_crc(True)
+        try:
+            return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                      cleanup_files, all_unique_sscs, bgzf, inflate, decode, bgzf_effort, resident)
+        finally:
+            engine.device_crc(was_crc)
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
     if bgzf_effort not in (1, 2):

@@ -621,14 +621,27 @@ def to_owners(comm, geo, parts):
 
 def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|", scorrect="True", level=6,
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
-                     cuts=None, bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host"):
+                     cuts=None, bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host",
+                     crc="host"):
     """bgzf: "host" (the default) or "device": this rank's output files deflated by the engine's BGZF
     encoder, at bgzf_effort 1 (the default) or 2 (2 needs bgzf="device").  inflate: "host" (the default) or "device": this rank's reads inflated by the engine's
     BGZF inflater.  decode: "host" (the default) or "device": this rank's stage tables built by the
     engine's record unpacker.  resident: "host" (the default) or "device": a whole-file read's inflated
     bytes stay on the device for the unpacker (Engine.device_resident; only with inflate="device" and
     decode="device", and only for whole-file opens: a rank's region reads and combined handles are
-    uploaded as before).  These are pipeline.consensus_pipeline's options; see _sharded_pipeline."""
+    uploaded as before).  crc: "host" (the default) or "device": this rank's device inflater and encoder
+    take their CRC32s from the device (Engine.device_crc; only with inflate="device" or bgzf="device").
+    These are pipeline.consensus_pipeline's options; see _sharded_pipeline."""
+    if crc not in ("host", "device"):
+        raise ValueError('crc must be "host" or "device"')
+    if crc == "device":
+        was_crc = engine.device_crc(True)
+        try:
+            return sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                    blocks, held, refs, keep, finalize, timings, cuts, bgzf, inflate, decode,
+                                    bgzf_effort, resident)
+        finally:
+            engine.device_crc(was_crc)
     if bgzf not in ("host", "device"):
         raise ValueError('bgzf must be "host" or "device"')
     if bgzf_effort not in (1, 2):

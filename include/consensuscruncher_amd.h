@@ -239,6 +239,25 @@ typedef int (*ccio_inflate_keep_fn)(void *user, const uint8_t *comp, const uint6
                                     uint8_t *ok, uint64_t total, int64_t *token);
 typedef int (*ccio_resident_patch_fn)(void *user, int64_t token, uint64_t off, const uint8_t *bytes, uint64_t n);
 void ccio_set_inflate_keep_hook(ccio_inflate_keep_fn keep, ccio_resident_patch_fn patch, void *user);
+/* The two inflate hooks with a CRC of their own (the device CRC32: cc_bgzf_inflate_crc_hook and
+ * cc_bgzf_inflate_keep_crc_hook below): the types above plus a trailing crc, where the hook leaves
+ * crc[j] = the CRC32 of the bytes it produced for member j (read only where ok[j] == 1).  While a crc
+ * hook is set it takes its plain sibling's place, whether or not that one is set too, and libccio
+ * accepts member j when ok[j] == 1 and crc[j] equals the member's CRC32 field; it computes no CRC over
+ * out.  Every other rule is the plain hooks': a refused member, a member whose CRC differs and every
+ * member after a nonzero return are inflated by the host codec, and those of a kept copy go through
+ * patch.  The trust this implies: the verdict is about the hook's own bytes (for the device inflater,
+ * the bytes in device memory, which with a kept copy are the bytes the unpacker reads); that out
+ * holds the same bytes is the hook's word, no longer checked here.  NULL unsets a crc hook and its
+ * plain sibling, if set, serves again. */
+typedef int (*ccio_inflate_crc_fn)(void *user, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
+                                   const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out, uint8_t *ok,
+                                   uint32_t *crc);
+typedef int (*ccio_inflate_keep_crc_fn)(void *user, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
+                                        const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out,
+                                        uint8_t *ok, uint64_t total, int64_t *token, uint32_t *crc);
+void ccio_set_inflate_crc_hook(ccio_inflate_crc_fn fn, void *user);
+void ccio_set_inflate_keep_crc_hook(ccio_inflate_keep_crc_fn keep, ccio_resident_patch_fn patch, void *user);
 /* 1, with the keep hook's token and the offset of b's first record in the inflated file (where its
  * records end for a file without any), when b came from ccio_bam_open with the keep hook set and its
  * records are still that stream's own; 0 for views, combined handles and region opens. */
@@ -431,6 +450,38 @@ int cc_resident_free(cc_ctx *ctx, int64_t id);
  * number of resident streams the context holds */
 int64_t cc_resident_fetch(cc_ctx *ctx, int64_t id, uint8_t *dst, uint64_t cap);
 int64_t cc_resident_count(cc_ctx *ctx);
+/* CRC-32 (zlib's) on the device (k_crc32: one workgroup of 256 threads per segment of at most 65,536
+ * bytes at any byte address; slice-by-4 tables and a "through 4,080 zero bytes" operator built in LDS
+ * from the polynomial; csrc/crc_core.h holds the arithmetic and the per-lane rule).  crc[i] = the
+ * CRC32 of data[off[i] .. off[i] + len[i]) for n ranges, which may overlap and may be of any length:
+ * data is uploaded once, a range longer than 65,536 bytes is cut into segments on the host and their
+ * CRCs are joined (crc32_combine's arithmetic); an empty range gives 0.  A range outside [0, nbytes)
+ * is CC_E_INVALID.  Runs on the encoder's streams, under its mutex and latch, like everything below;
+ * with profiling on, cc_kernel_times reports every launch of the kernel as "bgzf_crc32". */
+int cc_crc32(cc_ctx *ctx, const uint8_t *data, uint64_t nbytes, const uint64_t *off, const uint64_t *len, int64_t n,
+             uint32_t *crc);
+/* the same over a resident stream's bytes, in place (no upload) */
+int cc_resident_crc32(cc_ctx *ctx, int64_t id, const uint64_t *off, const uint64_t *len, int64_t n, uint32_t *crc);
+/* cc_bgzf_inflate and cc_bgzf_inflate_keep with one more output: crc[j] = the CRC32 of the bytes the
+ * device wrote for member j, defined where ok[j] == 1 (0 elsewhere).  In every round k_crc32 follows
+ * k_bgzf_inflate on the same stream, over the round's descriptors and its output base (the round's
+ * buffer, or the resident stream itself), and the values come back with the status words. */
+int64_t cc_bgzf_inflate_crc(cc_ctx *ctx, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
+                            const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out, uint8_t *ok,
+                            uint32_t *crc);
+int64_t cc_bgzf_inflate_keep_crc(cc_ctx *ctx, const uint8_t *comp, const uint64_t *coff, const uint32_t *clen,
+                                 const uint64_t *uoff, const uint32_t *ulen, int64_t members, uint8_t *out, uint8_t *ok,
+                                 uint64_t total, int64_t *resident_id, uint32_t *crc);
+/* what to hand to ccio_set_inflate_crc_hook and ccio_set_inflate_keep_crc_hook; unset them before cc_destroy */
+int cc_bgzf_inflate_crc_hook(cc_ctx *ctx, ccio_inflate_crc_fn *fn, void **user);
+int cc_bgzf_inflate_keep_crc_hook(cc_ctx *ctx, ccio_inflate_keep_crc_fn *keep, ccio_resident_patch_fn *patch,
+                                  void **user);
+/* The encoder's CRC32 fields: 0 (the default: the calling thread computes them on the host while the
+ * device encodes) or nonzero (k_crc32 computes them over the pieces in the device input buffer, four
+ * bytes per piece come back with the lengths, and the calling thread computes no CRC).  The members
+ * are byte for byte the same either way.  Holds like cc_bgzf_set_effort: for later cc_bgzf_deflate
+ * calls and hook rounds; a running round finishes the way it began. */
+int cc_bgzf_set_crc(cc_ctx *ctx, int on);
 /* Deferred end-of-pass checks (no reference counterpart: the reference has no device).  With
  * deferral on, a stage call that re-runs a planned pass (cc_read_bam_rerun, cc_consensus_maker,
  * cc_duplex_consensus, cc_singleton_correction on a group that ran before) enqueues its check and
