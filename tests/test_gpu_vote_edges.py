@@ -11,9 +11,9 @@ partly filled waves and blocks, per-position patterns at and below the cutoff's 
 count, the mode routines on both sides of their table sizes, the three defined errors on each vote
 path, and pairs across tables of different longest read.
 
-Not reachable through these two calls, and left to the pipeline tests: members dropped as a line
-read twice (the member record's valid bit clear), and singleton-correction pairs whose complement
-lies in the singleton table (b_in_a)."""
+Not reachable through these two calls: members dropped as a line read twice (the member record's
+valid bit clear), left to the pipeline tests, and singleton-correction pairs whose complement lies in
+the singleton table (b_in_a), covered by tests/test_gpu_duplex_edges.py."""
 import os
 import re
 
