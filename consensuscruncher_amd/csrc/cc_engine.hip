@@ -2535,6 +2535,14 @@ __global__ __launch_bounds__(DF_ST) void k_deep_sortfam(const int4* __restrict__
         const uint32_t m = (uint32_t)d.y;
         if (m > (uint32_t)DF_SORT) {   // too long for the LDS sort: the pass re-runs on the sorted path
             if (t == 0) atomicOr(err, EB_DEEPSORT);
+            // its slots all the same, in record order: the rest of this pass (family starts, creation
+            // order, csn entries) indexes by them before the error word is judged, and a slot left
+            // unwritten holds whatever the pooled buffer held
+            for (uint32_t i = t; i < m; i += DF_ST) {
+                const uint32_t v = se[d.x + i];
+                const int32_t r = CC_IDX((v & 1u) ? V.rec2[v >> 1] : V.rec1[v >> 1], T.n, DS_REC);
+                deep_put(out, V, T, d.z + (int64_t)i, v, r, i == 0, true, err);
+            }
             continue;
         }
         // Rank path: a family's ends lie close together in end order (its pairs complete at one

@@ -53,8 +53,8 @@ def window(s, T, n):
 
 # ---- tables ---------------------------------------------------------------------------------------
 class Table(object):
-    """Records as arrays: qname, tid, pos, mtid, mpos, flag, tlen and READ_LEN base codes (cigar one M,
-    every quality 40)."""
+    """Records as arrays: qname, tid, pos, mtid, mpos, flag, tlen and READ_LEN base codes (every quality
+    40; the cigar one M unless `cig` holds (op, length) tuples for the record)."""
 
     def __init__(self, n, seed=0):
         self.qname = [None] * n
@@ -65,6 +65,10 @@ class Table(object):
         self.flag = np.zeros(n, np.int32)
         self.tlen = np.zeros(n, np.int32)
         self.seq = np.random.default_rng(seed).choice((1, 2, 4, 8), (max(n, 1), READ_LEN)).astype(np.uint8)[:n]
+        self.cig = [None] * n
+
+    def cigar_of(self, i):
+        return self.cig[i] or [(0, READ_LEN)]
 
     def __len__(self):
         return len(self.qname)
@@ -73,6 +77,7 @@ class Table(object):
         """The table with its records in another order."""
         t = Table(len(order))
         t.qname = [self.qname[i] for i in order]
+        t.cig = [self.cig[i] for i in order]
         for name in ("tid", "pos", "mtid", "mpos", "flag", "tlen", "seq"):
             setattr(t, name, getattr(self, name)[np.asarray(order, np.int64)])
         return t
@@ -84,9 +89,11 @@ class Table(object):
         packed = ((c[0::2] << 4) | c[1::2]).astype(np.uint8).tobytes()
         qn = self.qname[i].encode() + b"\x00"
         p = int(self.pos[i])
-        body = struct.pack("<iiBBHHHiiii", int(self.tid[i]), p, len(qn), 60, pysam.reg2bin(p, p + READ_LEN), 1,
+        cig = self.cigar_of(i)
+        span = sum(ln for op, ln in cig if op in (0, 2, 3, 7, 8))
+        body = struct.pack("<iiBBHHHiiii", int(self.tid[i]), p, len(qn), 60, pysam.reg2bin(p, p + span), len(cig),
                            int(self.flag[i]), READ_LEN, int(self.mtid[i]), int(self.mpos[i]), int(self.tlen[i]))
-        body += qn + struct.pack("<I", (READ_LEN << 4) | 0) + packed + b"\x28" * READ_LEN
+        body += qn + b"".join(struct.pack("<I", (ln << 4) | op) for op, ln in cig) + packed + b"\x28" * READ_LEN
         return struct.pack("<i", len(body)) + body
 
     def header(self):
@@ -107,7 +114,7 @@ class Table(object):
         r.reference_id = int(self.tid[i])
         r.reference_start = int(self.pos[i])
         r.mapping_quality = 60
-        r.cigartuples = [(0, READ_LEN)]
+        r.cigartuples = list(self.cigar_of(i))
         r.next_reference_id = int(self.mtid[i])
         r.next_reference_start = int(self.mpos[i])
         r.template_length = int(self.tlen[i])
