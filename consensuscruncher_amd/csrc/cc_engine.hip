@@ -5481,6 +5481,7 @@ struct cc_ctx {
     uint8_t* d_defer = nullptr;           // the same area as the device sees it (k_defer_pack)
     BgzfEnc* bgzf = nullptr;              // made by the first cc_bgzf_deflate / hook call
     std::mutex bgzf_mu;                   // guards its creation (the writers' threads call the hook)
+    int32_t asm_group = -1;               // cc_bam_assemble_group: the assemble hook's next consensus source
 };
 
 namespace {
@@ -6625,6 +6626,7 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
 }  // extern "C"
 
 #include "table_unpack.hip.inc"
+#include "bam_assemble.hip.inc"
 
 namespace {
 // Per-pass table preparation (timed with the pass): the member records; on a coordinate-sorted table

@@ -413,6 +413,10 @@ bool bgzf_deflate_write(FILE* f, const uint8_t* data, size_t n, int level, int n
 std::mutex g_hook_mu;
 ccio_deflate_fn g_hook_fn = nullptr;
 void* g_hook_user = nullptr;
+// An alternative assembler for ccio_write_bam_ex (ccio_set_assemble_hook, hook_assemble below): the
+// device assembler of libccamd, or any function with its contract.
+ccio_assemble_fn g_asm_fn = nullptr;
+void* g_asm_user = nullptr;
 
 // One round through the hook: true when every member it reports is a framed BGZF member of its
 // piece (sizes and the BSIZE / ISIZE fields checked here); anything else leaves the round to the
@@ -783,6 +787,12 @@ void ccio_set_deflate_hook(ccio_deflate_fn fn, void* user) {
 }
 
 // fn inflates the readers' BGZF members first from now on (NULL: the host codec alone again)
+void ccio_set_assemble_hook(ccio_assemble_fn fn, void* user) {
+    std::lock_guard<std::mutex> lk(g_hook_mu);
+    g_asm_fn = fn;
+    g_asm_user = fn ? user : nullptr;
+}
+
 void ccio_set_inflate_hook(ccio_inflate_fn fn, void* user) {
     std::lock_guard<std::mutex> lk(g_ihook_mu);
     g_ihook_fn = fn;
@@ -1949,6 +1959,111 @@ std::vector<const uint8_t*> merge_order(const std::vector<const ccio_bam*>& bs, 
     return recs;
 }
 
+uint8_t* asm_alloc(void* actx, uint64_t total) {
+    Bytes* b = static_cast<Bytes*>(actx);
+    if (total == 0) return nullptr;
+    try {
+        b->resize((size_t)total);
+    } catch (...) {
+        return nullptr;
+    }
+    return b->data();
+}
+
+// ccio_write_bam_ex's records through the hook: true with the stream in `all` and its offsets in `at`
+// when a hook is set, every source's records lie in place and in order in its own stream, the hook
+// returned 0 and its result passed the checks; anything else leaves the write to the host.
+bool hook_assemble(const ccio_bam* tmpl, ccio_interner* it, int64_t n, const cc_out_spec* spec, ccio_bam* const* srcs,
+                   int nsrc, const char* names, const int64_t* name_off, const uint8_t* cons_seq, const uint8_t* cons_qual,
+                   int flags, int T, Bytes& all, std::vector<uint64_t>& at) {
+    ccio_assemble_fn fn;
+    void* user;
+    {
+        std::lock_guard<std::mutex> lk(g_hook_mu);
+        fn = g_asm_fn;
+        user = g_asm_user;
+    }
+    if (!fn) return false;
+    std::vector<cc_asm_src> ss((size_t)nsrc);
+    std::vector<std::vector<uint64_t>> offs((size_t)nsrc);
+    for (int f = 0; f < nsrc; ++f) {
+        ccio_bam* b = srcs[f];
+        if (!b || !b->data) return false;   // a view (ccio_bam_combine / ccio_bam_route)
+        const int64_t nr = (int64_t)b->rec.size();
+        const uint8_t* lo = b->data->data();
+        const uint8_t* hi = lo + b->data->size();
+        cc_asm_src& s = ss[(size_t)f];
+        s = cc_asm_src{lo, 0, 0, 0, nullptr, nr};
+        if (nr == 0) continue;
+        const uint8_t* first = b->rec[0];
+        if (first < lo || first >= hi) return false;
+        std::vector<uint64_t>& o = offs[(size_t)f];
+        o.resize((size_t)nr);
+        std::atomic<bool> bad(false);
+        parallel_chunks(nr, T, 65536, [&](int64_t s0, int64_t e0) {
+            for (int64_t i = s0; i < e0; ++i) {
+                const uint8_t* r = b->rec[i];
+                if (r < first || r + 4 > hi) { bad = true; return; }
+                const uint8_t* end = r + 4 + (uint64_t)(uint32_t)rd32(r);
+                if (end > hi || (i + 1 < nr && b->rec[i + 1] != end)) { bad = true; return; }
+                o[(size_t)i] = (uint64_t)(r - first);
+            }
+        });
+        if (bad) return false;
+        const uint8_t* last = b->rec[nr - 1];
+        s.stream = first;
+        s.bytes = (uint64_t)(last + 4 + (uint64_t)(uint32_t)rd32(last) - first);
+        s.rec_off = o.data();
+        int64_t tok = 0;
+        uint64_t base = 0;
+        if (ccio_bam_resident(b, &tok, &base)) {
+            s.resident_id = tok;
+            s.base = base;
+        }
+    }
+    // the extents the specs use of the caller's arrays (the host writer reads them without any)
+    int64_t n_names = 0, name_end = 0, cq = 0, cs = 0;
+    bool neg = false;
+    for (int64_t i = 0; i < n; ++i) {
+        const cc_out_spec& sp = spec[i];
+        if (sp.kind != CC_OUT_RAW && sp.name_id >= 0) {
+            n_names = std::max(n_names, sp.name_id + 1);
+            name_end = std::max(name_end, name_off[sp.name_id + 1]);
+        }
+        if (sp.kind == CC_OUT_NEW) {
+            if (sp.cons_off < 0 || sp.cons_len < 0) { neg = true; break; }
+            cq = std::max(cq, sp.cons_off + sp.cons_len);
+            cs = std::max(cs, sp.cons_off / 2 + ((int64_t)sp.cons_len + 1) / 2);
+        }
+    }
+    if (neg) return false;
+    const bool own_cons = !cons_seq && !cons_qual;
+    const std::vector<std::string>& rgs = it->t[2].strs;
+    std::string rg_blob;
+    std::vector<int64_t> rg_off(rgs.size() + 1, 0);
+    for (size_t i = 0; i < rgs.size(); ++i) {
+        rg_blob += rgs[i];
+        rg_off[i + 1] = (int64_t)rg_blob.size();
+    }
+    at.assign((size_t)n + 1, 0);
+    uint64_t total = 0;
+    const int rc = fn(user, tmpl->header_raw.data(), (uint64_t)tmpl->header_raw.size(), ss.data(), nsrc, spec, n, names,
+                      name_off, n_names, (uint64_t)name_end, cons_seq, own_cons ? 0 : (uint64_t)cs, cons_qual,
+                      own_cons ? 0 : (uint64_t)cq, rg_blob.data(), rg_off.data(), (int32_t)rgs.size(), flags & CCIO_W_SORT,
+                      asm_alloc, &all, at.data(), &total);
+    if (rc != 0 || total != all.size() || at[0] != tmpl->header_raw.size() || at[(size_t)n] != total ||
+        total < tmpl->header_raw.size() || memcmp(all.data(), tmpl->header_raw.data(), tmpl->header_raw.size()) != 0)
+        return false;
+    std::atomic<bool> bad(false);
+    parallel_chunks(n, T, 65536, [&](int64_t s0, int64_t e0) {
+        for (int64_t i = s0; i < e0; ++i) {
+            const uint64_t a = at[(size_t)i], e = at[(size_t)i + 1];
+            if (e <= a || e > total || e - a < 4 || (uint64_t)(uint32_t)rd32(all.data() + a) + 4 != e - a) { bad = true; return; }
+        }
+    });
+    return !bad;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1975,6 +2090,18 @@ int ccio_write_bam_ex(const char* path, ccio_bam* tmpl, ccio_interner* it, int64
     const int T = hw_threads(nthreads);
     for (int64_t i = 0; i < n; ++i)
         if (spec[i].src_file < 0 || spec[i].src_file >= nsrc) { set_err("bad output spec"); return -1; }
+    {
+        // the assemble hook first (ccio_set_assemble_hook); whatever it refuses is assembled below
+        Bytes hall;
+        std::vector<uint64_t> hat;
+        if (hook_assemble(tmpl, it, n, spec, srcs, nsrc, names, name_off, cons_seq, cons_qual, flags, T, hall, hat)) {
+            pt.lap("write: hook assemble");
+            return finish_stream(path, tmpl, std::move(hall), hat, level, T, flags, keep);
+        }
+    }
+    if (!cons_seq || !cons_qual)
+        for (int64_t i = 0; i < n; ++i)
+            if (spec[i].kind == CC_OUT_NEW) { set_err("write_bam: consensus records without consensus arrays"); return -2; }
     const std::vector<std::string>& rgs = it->t[2].strs;
     auto name_of = [&](const cc_out_spec& sp, const char** nm) -> size_t {
         *nm = "";

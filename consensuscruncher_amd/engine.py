@@ -333,6 +333,7 @@ def coord_sorted(records):
 _BGZF_OWNER = None   # the engine whose encoder libccio's (process-wide) deflate hook points at
 _INFLATE_OWNER = None   # likewise for the inflate hook
 _KEEP_OWNER = None   # and for the inflate hook that keeps resident streams
+_ASSEMBLE_OWNER = None   # and for the assemble hook
 
 
 class Engine(object):
@@ -353,6 +354,7 @@ class Engine(object):
         self.resident_device = False
         self._keep_wired = False
         self.crc_device = False
+        self.assemble_device = False
         if os.environ.get("CC_CRC_DEVICE") == "1":   # before the hooks below are wired: they take the crc variants
             self.device_crc(True)
         if os.environ.get("CC_RESIDENT_DEVICE") == "1":
@@ -365,6 +367,8 @@ class Engine(object):
             self.device_inflate(True)
         if os.environ.get("CC_DECODE_DEVICE") == "1":
             self.device_decode(True)
+        if os.environ.get("CC_ASSEMBLE_DEVICE") == "1":
+            self.device_assemble(True)
 
     def device_decode(self, on):
         """Switches table() between the host decoder (Bam.decode + upload, the default) and the device
@@ -521,6 +525,81 @@ class Engine(object):
             raise IOError(N.io_error())
         return was
 
+    def device_assemble(self, on):
+        """Wires (or unwires) this context's device record assembler into libccio's stage writer
+        (cc_bam_assemble_hook -> ccio_set_assemble_hook): every write_bam from now on whose sources
+        hold their records in place has its stream assembled by k_asm_sizes / k_asm_copy; libccio
+        checks the result and assembles whatever the device refused on the host, so the files are the
+        same either way.  The hook is one per process, with device_bgzf's ownership rules: the last
+        engine to wire it serves the writer, and the engine it took the hook from reads
+        assemble_device False from then on.  Assembly is synchronous, so there is nothing to wait
+        for.  Returns the previous state."""
+        global _ASSEMBLE_OWNER
+        was = self.assemble_device
+        on = bool(on)
+        if on == was:
+            return was
+        io = N.io()
+        if on:
+            fn, user = N.P(), N.P()
+            self._check(self.lib.cc_bam_assemble_hook(self.h, C.byref(fn), C.byref(user)))
+            prev = _ASSEMBLE_OWNER
+            if prev is not None and prev is not self:
+                prev.assemble_device = False
+            io.ccio_set_assemble_hook(fn, user)
+            _ASSEMBLE_OWNER = self
+            self.assemble_device = True
+            return was
+        io.ccio_set_assemble_hook(None, None)
+        _ASSEMBLE_OWNER = None
+        self.assemble_device = False
+        return was
+
+    def assemble(self, header, sources, specs, names=None, name_off=None, cons_seq=None, cons_qual=None, group=None,
+                 rg_values=(), sort=False):
+        """cc_bam_assemble: the output stream (header bytes, then the records of `specs`) and its
+        n + 1 record offsets, as (bytes, uint64 array).  sources: per source (stream, rec_off) with the
+        records' bytes and offsets in host memory, or (None, rec_off, resident id, base, nbytes) for a
+        resident stream.  The consensus arrays are cons_seq / cons_qual, or group's device buffers.
+        rg_values: the RG table's values (bytes), by rg_id.  sort: samtools-sort order."""
+        header = np.frombuffer(bytes(header), np.uint8)
+        specs = np.ascontiguousarray(specs, N.OUT_SPEC_DTYPE)
+        n = len(specs)
+        arr = (N.cc_asm_src * max(len(sources), 1))()
+        hold = []
+        for f, src in enumerate(sources):
+            off = np.ascontiguousarray(src[1], np.uint64)
+            hold.append(off)
+            if src[0] is None:
+                arr[f] = N.cc_asm_src(None, int(src[4]), int(src[2]), int(src[3]), off.ctypes.data, len(off))
+            else:
+                st = np.frombuffer(bytes(src[0]), np.uint8) if not isinstance(src[0], np.ndarray) else \
+                    np.ascontiguousarray(src[0], np.uint8)
+                hold.append(st)
+                arr[f] = N.cc_asm_src(st.ctypes.data if len(st) else None, len(st), 0, 0, off.ctypes.data, len(off))
+        names = np.zeros(0, np.uint8) if names is None else np.ascontiguousarray(names).view(np.uint8)
+        name_off = np.zeros(1, np.int64) if name_off is None else np.ascontiguousarray(name_off, np.int64)
+        cs = np.zeros(0, np.uint8) if cons_seq is None else np.ascontiguousarray(cons_seq, np.uint8)
+        cq = np.zeros(0, np.uint8) if cons_qual is None else np.ascontiguousarray(cons_qual, np.uint8)
+        rg = [bytes(v) for v in rg_values]
+        rg_off = np.zeros(len(rg) + 1, np.int64)
+        rg_off[1:] = np.cumsum([len(v) for v in rg]) if rg else []
+        rg_blob = np.frombuffer(b"".join(rg) + b"\0", np.uint8)
+
+        def call(out, cap, at, total):
+            return self.lib.cc_bam_assemble(
+                self.h, N.ptr(header) if len(header) else None, len(header), arr, len(sources), N.ptr(specs), n,
+                N.ptr(names) if len(names) else None, N.ptr(name_off), len(name_off) - 1, len(names),
+                N.ptr(cs) if len(cs) else None, len(cs), N.ptr(cq) if len(cq) else None, len(cq),
+                -1 if group is None else int(group), N.ptr(rg_blob), N.ptr(rg_off), len(rg), N.W_SORT if sort else 0,
+                out, cap, at, total)
+        total = C.c_uint64()
+        self._check(call(None, 0, None, C.byref(total)))
+        out = np.zeros(max(int(total.value), 1), np.uint8)
+        at = np.zeros(n + 1, np.uint64)
+        self._check(call(N.ptr(out), int(total.value), N.ptr(at), C.byref(total)))
+        return out[:int(total.value)].tobytes(), at
+
     def device_inflate(self, on):
         """Wires (or unwires) this context's device BGZF inflater into libccio's readers
         (cc_bgzf_inflate_hook -> ccio_set_inflate_hook): every BAM opened from now on (whole file,
@@ -655,6 +734,7 @@ class Engine(object):
                 self.device_resident(False)   # the hooks must not outlive the context; the resident streams
                 self.device_inflate(False)    # that are left go with it (cc_destroy)
                 self.device_bgzf(False)
+                self.device_assemble(False)
             finally:
                 self.lib.cc_destroy(self.h)
                 self.h = None
@@ -1039,10 +1119,35 @@ def dcs_names(bam, rec_tag, rec_ds):
 
 
 def write_bam(path, template, interner, specs, srcs, names=None, name_off=None, cons_seq=None, cons_qual=None,
-              level=6, nthreads=0, sink=None):
+              level=6, nthreads=0, sink=None, cons_group=None):
     """Assembles and writes one output BAM (ccio_write_bam).  sink (the orchestrator's fused
     sort_index, Sink) may redirect it: written sorted and indexed under its sorted name, and kept in
-    memory for the next stage.  Returns the path written."""
+    memory for the next stage.  cons_group, in place of cons_seq / cons_qual: (engine, group) whose
+    device consensus buffers the engine's assembler reads (Engine.device_assemble); when the
+    assembler does not take the write, the arrays are fetched and the host assembles as always.
+    Returns the path written."""
+    if cons_group is not None and cons_seq is None:
+        eng, g = cons_group
+        if eng.assemble_device:
+            eng._check(eng.lib.cc_bam_assemble_group(eng.h, int(g)))
+            try:
+                return _write_bam(path, template, interner, specs, srcs, names, name_off, None, None, level, nthreads,
+                                  sink, own_cons=True)
+            except _NeedCons:
+                pass
+            finally:
+                eng.lib.cc_bam_assemble_group(eng.h, -1)
+        cons_seq = eng.fetch(g, "cons_seq", np.uint8)
+        cons_qual = eng.fetch(g, "cons_qual", np.uint8)
+    return _write_bam(path, template, interner, specs, srcs, names, name_off, cons_seq, cons_qual, level, nthreads, sink)
+
+
+class _NeedCons(Exception):
+    """ccio_write_bam_ex's -2: consensus records, no host arrays, and no hook took the write."""
+
+
+def _write_bam(path, template, interner, specs, srcs, names, name_off, cons_seq, cons_qual, level, nthreads, sink,
+               own_cons=False):
     specs = np.ascontiguousarray(specs, N.OUT_SPEC_DTYPE)
     arr = (N.P * len(srcs))(*[s.h for s in srcs])
     dummy = np.zeros(1, np.uint8)
@@ -1054,9 +1159,11 @@ def write_bam(path, template, interner, specs, srcs, names=None, name_off=None, 
     rc = N.io().ccio_write_bam_ex(out.encode(), template.h, interner.h, len(specs), N.ptr(specs), arr, len(srcs),
                                   N.ptr(names if names is not None else dummy),
                                   N.ptr(name_off if name_off is not None else dummy_off),
-                                  N.ptr(cons_seq if cons_seq is not None and len(cons_seq) else dummy),
-                                  N.ptr(cons_qual if cons_qual is not None and len(cons_qual) else dummy),
+                                  None if own_cons else N.ptr(cons_seq if cons_seq is not None and len(cons_seq) else dummy),
+                                  None if own_cons else N.ptr(cons_qual if cons_qual is not None and len(cons_qual) else dummy),
                                   level, nthreads, flags, C.byref(keep) if keep is not None else None)
+    if rc == -2 and own_cons:
+        raise _NeedCons()
     if rc != 0:
         raise IOError(N.io_error())
     if keep is not None:

@@ -93,6 +93,20 @@ INFLATE_KEEP_CRC_FN = C.CFUNCTYPE(C.c_int, P, P, C.POINTER(C.c_uint64), C.POINTE
                                   C.POINTER(C.c_uint32), C.c_int64, P, C.POINTER(C.c_uint8), C.c_uint64,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_uint32))
 
+
+class cc_asm_src(C.Structure):
+    _fields_ = [("stream", P), ("bytes", C.c_uint64), ("resident_id", C.c_int64), ("base", C.c_uint64),
+                ("rec_off", P), ("nrec", C.c_int64)]
+
+
+# cc_asm_alloc_fn: actx, total -> the stream's buffer
+ASM_ALLOC_FN = C.CFUNCTYPE(P, P, C.c_uint64)
+# ccio_assemble_fn: user, header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes,
+# cons_seq, cons_seq_bytes, cons_qual, cons_qual_bytes, rg_blob, rg_off, n_rg, flags, alloc, actx, at, total
+ASSEMBLE_FN = C.CFUNCTYPE(C.c_int, P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, P, C.c_int64, P, P, C.c_int64,
+                          C.c_uint64, P, C.c_uint64, P, C.c_uint64, P, P, C.c_int32, C.c_int, ASM_ALLOC_FN, P,
+                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+
 _io = None
 _amd = None
 
@@ -100,6 +114,7 @@ IO_SIGS = {
     "ccio_last_error": (C.c_char_p, []),
     "ccio_flush": (C.c_int, []),
     "ccio_set_deflate_hook": (None, [P, P]),
+    "ccio_set_assemble_hook": (None, [P, P]),
     "ccio_set_inflate_hook": (None, [P, P]),
     "ccio_set_inflate_keep_hook": (None, [P, P, P]),
     "ccio_set_inflate_crc_hook": (None, [P, P]),
@@ -196,6 +211,11 @@ AMD_SIGS = {
     "cc_table_unpack": (C.c_int, [P, P, C.c_uint64, P, C.c_int64, P, P, P, P, i32p, i32p]),
     "cc_table_unpack_resident": (C.c_int, [P, C.c_int64, C.c_uint64, C.c_uint64, P, C.c_int64, P, P, P, P, i32p,
                                            i32p]),
+    "cc_bam_assemble": (C.c_int, [P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, P, C.c_int64, P, P, C.c_int64,
+                                  C.c_uint64, P, C.c_uint64, P, C.c_uint64, C.c_int32, P, P, C.c_int32, C.c_int, P,
+                                  C.c_uint64, P, C.POINTER(C.c_uint64)]),
+    "cc_bam_assemble_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
+    "cc_bam_assemble_group": (C.c_int, [P, C.c_int32]),
     "cc_table_free": (C.c_int, [P, C.c_int32]),
     "cc_table_derive": (C.c_int, [P, C.c_int32]),
     "cc_table_fetch": (C.c_int64, [P, C.c_int32, C.c_char_p, P, C.c_int64]),

@@ -52,8 +52,11 @@ def cleanup(sd, identifier, scorrect):
 
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
-                       bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host", crc="host"):
-    """bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
+                       bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host", crc="host",
+                       assemble="host"):
+    """assemble: "host" (libccio assembles the stage outputs' records, the default) or "device" (the
+    engine's record assembler builds each output stream from the votes' device buffers,
+    Engine.device_assemble: the same files).  bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
     output files: same records, other compressed bytes and .bai offsets).  bgzf_effort: the device
     encoder's effort, 1 (the default) or 2 (smaller files, a slower kernel); 2 needs bgzf="device",
     and the BGZF level does not select it.  inflate: "host" (the
@@ -68,6 +71,16 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
     come from the device; same bytes read, same files written); it engages only with inflate="device"
     or bgzf="device" and is otherwise without effect.  Each option is wired for this call only; see
     _consensus_pipeline."""
+    if assemble not in ("host", "device"):
+        raise ValueError('assemble must be "host" or "device"')
+    if assemble == "device":
+        engine = engine or get_engine()
+        was_asm = engine.device_assemble(True)
+        try:
+            return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                      cleanup_files, all_unique_sscs, bgzf, inflate, decode, bgzf_effort, resident, crc)
+        finally:
+            engine.device_assemble(was_asm)
     if crc not in ("host", "device"):
         raise ValueError('crc must be "host" or "device"')
     if crc == "device":

@@ -110,9 +110,11 @@ class SSCSRun(object):
         # one sscs_qname per entry, shared by the entry's two emitted records
         emit_ckey = np.repeat(eng.fetch(g, "emit_ckey", np.int32).reshape(-1, 9), 2, axis=0).reshape(-1)
         meta = eng.fetch(g, "vote_meta", np.int32).reshape(-1, 5)
-        cons_seq = eng.fetch(g, "cons_seq", np.uint8)
-        cons_qual = eng.fetch(g, "cons_qual", np.uint8)
-        bad_rec = eng.fetch(g, "bad_rec", np.int32)
+        # with the device assembler on, the consensus arrays stay on the device (write_bam: cons_group)
+        cgroup = (eng, g) if eng.assemble_device else None
+        cons_seq = None if cgroup else eng.fetch(g, "cons_seq", np.uint8)
+        cons_qual = None if cgroup else eng.fetch(g, "cons_qual", np.uint8)
+        bad_rec =eng.fetch(g, "bad_rec", np.int32)
         fam_sizes = eng.fetch(g, "fam_sizes_by_creation", np.int32)
         qstride = (rec.max_len + 15) & ~15
         ne = len(emit_n)
@@ -124,7 +126,8 @@ class SSCSRun(object):
         voted = emit_vslot >= 0
         # SSCS records (create_aligned_segment) and renamed singletons, in emission order
         sp = _new_specs(voted, emit_rec[voted], np.nonzero(voted)[0], emit_vslot[voted], meta, qstride)
-        write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink)
+        write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
+                  cons_group=cgroup)
         ss = make_specs(int((~voted).sum()))
         ss["kind"] = N.OUT_RENAME
         ss["src_rec"] = emit_rec[~voted]
@@ -331,8 +334,9 @@ class DCSRun(object):
         p_rec = eng.fetch(g, "p_rec", np.int32)
         vslot = eng.fetch(g, "vslot", np.int32)
         meta = eng.fetch(g, "vote_meta", np.int32).reshape(-1, 5)
-        cons_seq = eng.fetch(g, "cons_seq", np.uint8)
-        cons_qual = eng.fetch(g, "cons_qual", np.uint8)
+        cgroup = (eng, g) if eng.assemble_device else None   # (as SSCSRun.emit)
+        cons_seq = None if cgroup else eng.fetch(g, "cons_seq", np.uint8)
+        cons_qual = None if cgroup else eng.fetch(g, "cons_qual", np.uint8)
         qstride = (rec.max_len + 15) & ~15
         made = dec == 0
         nm = int(made.sum())
@@ -342,7 +346,8 @@ class DCSRun(object):
         self.times["emit_names"] = time.time() - t0
         t0 = time.time()
         sp = _new_specs(nm, t_rec[made], np.arange(nm), vslot[made], meta, qstride)
-        write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink)
+        write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
+                  cons_group=cgroup)
         single = dec == 1
         ss = make_specs(int(single.sum()))
         ss["kind"] = N.OUT_RAW
@@ -470,8 +475,9 @@ class SCRun(object):
         vslot = eng.fetch(gs, "vslot", np.int32)
         q_ckey = eng.fetch(gs, "q_ckey", np.int32).reshape(-1, 9)
         meta = eng.fetch(gs, "vote_meta", np.int32).reshape(-1, 5)
-        cons_seq = eng.fetch(gs, "cons_seq", np.uint8)
-        cons_qual = eng.fetch(gs, "cons_qual", np.uint8)
+        cgroup = (eng, gs) if eng.assemble_device else None   # (as SSCSRun.emit)
+        cons_seq = None if cgroup else eng.fetch(gs, "cons_seq", np.uint8)
+        cons_qual = None if cgroup else eng.fetch(gs, "cons_qual", np.uint8)
         qstride = (max(self.srec.max_len, self.xrec.max_len) + 15) & ~15
         outs = {}
         for code, name in ((0, "sscs.correction"), (1, "singleton.correction")):
@@ -480,7 +486,7 @@ class SCRun(object):
             names, name_off = csn_names(it, q_ckey[m], np.ones(k, np.int64))
             sp = _new_specs(k, t_rec[m], np.arange(k), vslot[m], meta, qstride)
             write_bam('{}.{}.bam'.format(base, name), sbam, it, sp, [sbam], names, name_off, cons_seq, cons_qual,
-                      level, sink=sink)
+                      level, sink=sink, cons_group=cgroup)
             outs[name] = k
         m = dec == 2
         us = make_specs(int(m.sum()))

@@ -262,8 +262,45 @@ void ccio_set_inflate_keep_crc_hook(ccio_inflate_keep_crc_fn keep, ccio_resident
  * records end for a file without any), when b came from ccio_bam_open with the keep hook set and its
  * records are still that stream's own; 0 for views, combined handles and region opens. */
 int ccio_bam_resident(ccio_bam *b, int64_t *token, uint64_t *base);
+/* An alternative assembler for ccio_write_bam_ex's records (the device assembler: cc_bam_assemble_hook
+ * below).  With a hook set, a write whose source handles all hold their records in place and in order
+ * in their own streams (ccio_bam_resident's condition on the records; views from ccio_bam_combine /
+ * ccio_bam_route never reach the hook) goes to fn first:
+ *   header, header_bytes    the output's encoded header;
+ *   srcs[nsrc]              each source's records: its stream (block_size first), their offsets in it
+ *                           and, when ccio_bam_resident names one, the keep hook's token and the offset
+ *                           of the first record in that copy;
+ *   spec[n], names, name_off, n_names, names_bytes, rg_blob, rg_off[n_rg + 1], flags (CCIO_W_SORT)
+ *                           ccio_write_bam_ex's own; the RG values side by side;
+ *   cons_seq, cons_qual     the caller's arrays with the extent the specs use, or both NULL when the
+ *                           caller passed none (the hook then brings its own: cc_bam_assemble_group);
+ *   alloc(actx, total)      called once, after fn knows the stream's size: the buffer the stream goes to;
+ *   at[n + 1], *total       each output record's offset in the stream, at[n] = *total = its size.
+ * fn returns 0 when the whole stream (header, then the records) is written.  libccio then checks, in
+ * one parallel pass, that at[0] is the header's size, at is strictly increasing, every record's
+ * block_size + 4 is at[i + 1] - at[i] and at[n] is the total.  On any other return or a failed check
+ * the host assembles the records exactly as without a hook: a file is never lost.  NULL unsets it. */
+typedef struct cc_asm_src {
+    const uint8_t *stream;   /* the records in host memory; may be NULL for a resident source */
+    uint64_t bytes;          /* their size */
+    int64_t resident_id;     /* the resident stream (cc_bgzf_inflate_keep) holding them, 0: none; with a
+                              * host stream as well, the resident one is read while it still exists */
+    uint64_t base;           /* where they start in it */
+    const uint64_t *rec_off; /* nrec offsets, from stream / base */
+    int64_t nrec;
+} cc_asm_src;
+typedef uint8_t *(*cc_asm_alloc_fn)(void *actx, uint64_t total);
+typedef int (*ccio_assemble_fn)(void *user, const uint8_t *header, uint64_t header_bytes, const cc_asm_src *srcs,
+                                int32_t nsrc, const cc_out_spec *spec, int64_t n, const char *names,
+                                const int64_t *name_off, int64_t n_names, uint64_t names_bytes, const uint8_t *cons_seq,
+                                uint64_t cons_seq_bytes, const uint8_t *cons_qual, uint64_t cons_qual_bytes,
+                                const char *rg_blob, const int64_t *rg_off, int32_t n_rg, int flags,
+                                cc_asm_alloc_fn alloc, void *actx, uint64_t *at, uint64_t *total);
+void ccio_set_assemble_hook(ccio_assemble_fn fn, void *user);
 /* per value 0..maxv of v[0..n): count and first index (n when absent), one pass (read_families.txt) */
 int ccio_value_census(const int32_t *v, int64_t n, int32_t maxv, int64_t *first, int64_t *count);
+/* (cons_seq and cons_qual both NULL with CC_OUT_NEW specs: only an assemble hook that brings its own
+ * consensus arrays can write the file; when it does not, nothing is written and the result is -2) */
 int ccio_write_bam_ex(const char *path, ccio_bam *tmpl, ccio_interner *it, int64_t n, const cc_out_spec *spec,
                       ccio_bam *const *srcs, int nsrc, const char *names, const int64_t *name_off,
                       const uint8_t *cons_seq, const uint8_t *cons_qual, int level, int nthreads, int flags,
@@ -560,6 +597,30 @@ int cc_table_upload(cc_ctx *ctx, const cc_records *rec, int32_t max_len, int32_t
 int cc_table_unpack(cc_ctx *ctx, const uint8_t *recs, uint64_t bytes, const uint64_t *rec_off, int64_t n,
                     const int32_t *cigar_id, const int32_t *bc_id, const int32_t *rg_id, const uint8_t *rflags,
                     int32_t *max_len, int32_t *table_id);
+/* The output stream of one stage file (the header's bytes, then n records) assembled on the device
+ * from ccio_write_bam_ex's specs, byte for byte what the host writer assembles (csrc/assemble_core.h).
+ *   srcs[nsrc]       the sources the specs' src_file indexes: a host stream, uploaded for the call, or
+ *                    (stream NULL) a resident stream read in place, as cc_table_unpack_resident reads it;
+ *   names, name_off[n_names + 1], names_bytes; rg_blob, rg_off[n_rg + 1]: the names and RG values;
+ *   cons_group < 0   cons_seq[cons_seq_bytes] / cons_qual[cons_qual_bytes] are host arrays;
+ *   cons_group >= 0  that group's cons_seq / cons_qual device buffers are read where they lie;
+ *   flags            CCIO_W_SORT: samtools-sort order, ties in spec order.
+ * out NULL is a size query (*total only).  Otherwise out[cap] receives the stream, at[n + 1] every
+ * record's offset (at[0] = header_bytes, at[n] = *total).  A spec the shared layout refuses (an index
+ * out of range, a template whose lengths do not fit its block_size, a consensus or RG range outside
+ * its array, a new name longer than 254 bytes) is CC_E_INVALID and cc_last_error names the first such
+ * spec; more than 2^31 - 1 records is CC_E_UNSUPPORTED.  After an error out holds nothing of use.
+ * CC_ASM_SLICE_BYTES (environment) lowers the bytes whose offsets one scan covers (default 2^32 - 1). */
+int cc_bam_assemble(cc_ctx *ctx, const uint8_t *header, uint64_t header_bytes, const cc_asm_src *srcs, int32_t nsrc,
+                    const cc_out_spec *spec, int64_t n, const char *names, const int64_t *name_off, int64_t n_names,
+                    uint64_t names_bytes, const uint8_t *cons_seq, uint64_t cons_seq_bytes, const uint8_t *cons_qual,
+                    uint64_t cons_qual_bytes, int32_t cons_group, const char *rg_blob, const int64_t *rg_off,
+                    int32_t n_rg, int flags, uint8_t *out, uint64_t cap, uint64_t *at, uint64_t *total);
+/* the pair to hand to ccio_set_assemble_hook; unset the hook before cc_destroy */
+int cc_bam_assemble_hook(cc_ctx *ctx, ccio_assemble_fn *fn, void **user);
+/* the group whose consensus buffers the hook's next call uses when libccio passes it no arrays (that
+ * call consumes it); -1 clears it */
+int cc_bam_assemble_group(cc_ctx *ctx, int32_t group_id);
 /* cc_table_unpack with the records read in place from a resident stream (cc_bgzf_inflate_keep): they
  * are its bytes [base, base + bytes), which must lie inside it (else CC_E_INVALID), and rec_off counts
  * from base, as ccio_bam_decode_ids gives it.  Checks, errors and the table are cc_table_unpack's;
