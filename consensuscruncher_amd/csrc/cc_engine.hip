@@ -5482,6 +5482,8 @@ struct cc_ctx {
     BgzfEnc* bgzf = nullptr;              // made by the first cc_bgzf_deflate / hook call
     std::mutex bgzf_mu;                   // guards its creation (the writers' threads call the hook)
     int32_t asm_group = -1;               // cc_bam_assemble_group: the assemble hook's next consensus source
+    uint8_t* names_buf = nullptr;         // cc_format_*_names' blob until cc_names_read fetches it
+    int64_t names_total = -1;             // its bytes (-1: no blob)
 };
 
 namespace {
@@ -6171,6 +6173,7 @@ int cc_destroy(cc_ctx* ctx) {
     if (ctx->tmp.p) (void)hipFree(ctx->tmp.p);
     if (ctx->sort_buf.p) (void)hipFree(ctx->sort_buf.p);
     if (ctx->scan_st) (void)hipFree(ctx->scan_st);
+    if (ctx->names_buf) (void)hipFree(ctx->names_buf);
     flush_prof(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     (void)hipFree(ctx->d_err);
@@ -6627,6 +6630,7 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
 
 #include "table_unpack.hip.inc"
 #include "bam_assemble.hip.inc"
+#include "name_format.hip.inc"
 
 namespace {
 // Per-pass table preparation (timed with the pass): the member records; on a coordinate-sorted table

@@ -1575,6 +1575,43 @@ int64_t ccio_format_dcs_names(ccio_bam* b, int64_t n, const int64_t* rec_tag, co
     return used;
 }
 
+// 1 when the names ccio_format_dcs_names would read for these pairs (l_read_name - 1 bytes each) hold no
+// NUL, so that they are the bytes the record table keeps (its qn_len is a strnlen); 0 otherwise, -1
+// for a record index outside the handle.
+int ccio_dcs_names_plain(ccio_bam* b, int64_t n, const int64_t* rec_tag, const int64_t* rec_ds) {
+    const int64_t nrec = (int64_t)b->rec.size();
+    std::atomic<int> res{1};
+    parallel_chunks(n, hw_threads(0), 16384, [&](int64_t b0, int64_t e0) {
+        for (int64_t i = b0; i < e0 && res.load(std::memory_order_relaxed) == 1; ++i)
+            for (const int64_t r : {rec_tag[i], rec_ds[i]}) {
+                if (r < 0 || r >= nrec) { res = -1; return; }
+                const uint8_t* c = b->rec[r] + 4;
+                if (c[8] && (c[32 + c[8] - 1] != 0 || memchr(c + 32, 0, (size_t)c[8] - 1))) {   // (or no terminator)
+                    int one = 1;
+                    res.compare_exchange_strong(one, 0);
+                }
+            }
+    });
+    if (res < 0) set_err("dcs_names_plain: record index out of range");
+    return res;
+}
+
+// An interner table's strings side by side: off[0 .. n] (n = ccio_interner_size) their offsets, string i
+// is blob[off[i], off[i + 1]).  Returns the bytes in all; blob NULL: the offsets only; -1 when cap is
+// short or the kind unknown.
+int64_t ccio_interner_blob(ccio_interner* it, int kind, char* blob, int64_t cap, int64_t* off) {
+    if (kind < 0 || kind > 2 || !off) { set_err("interner_blob: unknown kind or no offsets"); return -1; }
+    std::lock_guard<std::mutex> g(it->mu);
+    const std::vector<std::string>& s = it->t[kind].strs;
+    int64_t used = 0;
+    for (size_t i = 0; i < s.size(); ++i) { off[i] = used; used += (int64_t)s[i].size(); }
+    off[s.size()] = used;
+    if (!blob) return used;
+    if (used > cap) { set_err("interner blob too small"); return -1; }
+    for (size_t i = 0; i < s.size(); ++i) memcpy(blob + off[i], s[i].data(), s[i].size());
+    return used;
+}
+
 }  // extern "C"
 
 namespace {

@@ -45,6 +45,17 @@ class Interner(object):
     def intern(self, kind, s):
         return int(N.io().ccio_interner_intern(self.h, kind, s.encode()))
 
+    def blob(self, kind):
+        """A table's strings side by side (ccio_interner_blob): (uint8 blob, int64 offsets, size + 1 of them)."""
+        off = np.zeros(self.size(kind) + 1, np.int64)
+        need = int(N.io().ccio_interner_blob(self.h, kind, None, 0, N.ptr(off)))
+        if need < 0:
+            raise RuntimeError(N.io_error())
+        blob = np.zeros(max(need, 1), np.uint8)
+        if int(N.io().ccio_interner_blob(self.h, kind, N.ptr(blob), need, N.ptr(off))) != need:
+            raise RuntimeError(N.io_error())
+        return blob, off
+
     def swap_table(self):
         n = int(N.io().ccio_interner_swap_table(self.h, None, 0))
         out = np.zeros(max(n, 1), np.int32)
@@ -355,6 +366,7 @@ class Engine(object):
         self._keep_wired = False
         self.crc_device = False
         self.assemble_device = False
+        self.names_device = os.environ.get("CC_NAMES_DEVICE") == "1"
         if os.environ.get("CC_CRC_DEVICE") == "1":   # before the hooks below are wired: they take the crc variants
             self.device_crc(True)
         if os.environ.get("CC_RESIDENT_DEVICE") == "1":
@@ -554,6 +566,58 @@ class Engine(object):
         _ASSEMBLE_OWNER = None
         self.assemble_device = False
         return was
+
+    def device_names(self, on):
+        """Switches the stages' consensus read names between libccio's formatters (csn_names / dcs_names,
+        the default) and the device formatter (Engine.csn_names / Engine.dcs_names: k_name_sizes_* and
+        k_name_write_*).  The names, and every file written with them, are the same either way.  A
+        per-engine switch (no process-wide hook).  Returns the previous state."""
+        was = self.names_device
+        self.names_device = bool(on)
+        return was
+
+    def _names_blob(self, n, off, total):
+        blob = np.zeros(max(int(total), 1), np.uint8)
+        self._check(self.lib.cc_names_read(self.h, N.ptr(blob), int(total)))
+        return blob, off
+
+    def csn_names(self, interner, ckey9, suffix):
+        """csn_names on the device (cc_format_csn_names): the same (blob, off).  What the device refuses
+        (an id outside its table) or does not support goes to the host function, which raises what
+        it always raised."""
+        n = len(suffix)
+        ck = np.ascontiguousarray(ckey9, np.int32).reshape(-1)
+        sf = np.ascontiguousarray(suffix, np.int64)
+        if len(ck) != 9 * n:
+            raise ValueError("csn_names: nine fields per name")
+        bc, bc_off = interner.blob(0)
+        cg, cg_off = interner.blob(1)
+        off = np.zeros(n + 1, np.int64)
+        total = C.c_int64(0)
+        rc = self.lib.cc_format_csn_names(self.h, n, N.ptr(ck), N.ptr(sf), N.ptr(bc), N.ptr(bc_off), len(bc_off) - 1,
+                                          N.ptr(cg), N.ptr(cg_off), len(cg_off) - 1, N.ptr(off), C.byref(total))
+        if rc in (N.CC_E_INVALID, N.CC_E_UNSUPPORTED):
+            return csn_names(interner, ckey9, suffix)
+        self._check(rc)
+        return self._names_blob(n, off, total.value)
+
+    def dcs_names(self, bam, table, rec_tag, rec_ds):
+        """dcs_names on the device (cc_format_dcs_names) from `table`, the record table built from bam:
+        the same (blob, off).  Names with a NUL inside (ccio_dcs_names_plain: the table keeps them up to
+        it), whatever the device refuses (the reference's IndexError) and what it does not support go
+        to the host function, which raises what it always raised."""
+        n = len(rec_tag)
+        a = np.ascontiguousarray(rec_tag, np.int64)
+        b = np.ascontiguousarray(rec_ds, np.int64)
+        if N.io().ccio_dcs_names_plain(bam.h, n, N.ptr(a), N.ptr(b)) != 1:
+            return dcs_names(bam, rec_tag, rec_ds)
+        off = np.zeros(n + 1, np.int64)
+        total = C.c_int64(0)
+        rc = self.lib.cc_format_dcs_names(self.h, int(table), n, N.ptr(a), N.ptr(b), N.ptr(off), C.byref(total))
+        if rc in (N.CC_E_INVALID, N.CC_E_UNSUPPORTED):
+            return dcs_names(bam, rec_tag, rec_ds)
+        self._check(rc)
+        return self._names_blob(n, off, total.value)
 
     def assemble(self, header, sources, specs, names=None, name_off=None, cons_seq=None, cons_qual=None, group=None,
                  rg_values=(), sort=False):

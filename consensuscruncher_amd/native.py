@@ -21,6 +21,7 @@ CC_E = {
 CC_E_INVALID = -1
 CC_E_N_HIGHQ = -3
 CC_E_COLLISION = -10
+CC_E_UNSUPPORTED = -11
 CC_E_KEYERROR = -12
 CC_E_REPLAY = -13
 
@@ -141,6 +142,8 @@ IO_SIGS = {
     "ccio_dcs_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
     "ccio_duplex_tag": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
     "ccio_format_dcs_names": (C.c_int64, [P, C.c_int64, P, P, P, C.c_int64, P]),
+    "ccio_dcs_names_plain": (C.c_int, [P, C.c_int64, P, P]),
+    "ccio_interner_blob": (C.c_int64, [P, C.c_int, P, C.c_int64, P]),
     "ccio_write_bam": (C.c_int, [C.c_char_p, P, P, C.c_int64, P, P, C.c_int, P, P, P, P, C.c_int, C.c_int]),
     "ccio_sort_bam": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "ccio_merge_bams": (C.c_int, [C.c_char_p, P, C.c_int, C.c_int, C.c_int]),
@@ -216,6 +219,9 @@ AMD_SIGS = {
                                   C.c_uint64, P, C.POINTER(C.c_uint64)]),
     "cc_bam_assemble_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
     "cc_bam_assemble_group": (C.c_int, [P, C.c_int32]),
+    "cc_format_csn_names": (C.c_int, [P, C.c_int64, P, P, P, P, C.c_int64, P, P, C.c_int64, P, i64p]),
+    "cc_format_dcs_names": (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, i64p]),
+    "cc_names_read": (C.c_int, [P, P, C.c_int64]),
     "cc_table_free": (C.c_int, [P, C.c_int32]),
     "cc_table_derive": (C.c_int, [P, C.c_int32]),
     "cc_table_fetch": (C.c_int64, [P, C.c_int32, C.c_char_p, P, C.c_int64]),

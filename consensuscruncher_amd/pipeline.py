@@ -53,8 +53,9 @@ def cleanup(sd, identifier, scorrect):
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
                        bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host", crc="host",
-                       assemble="host"):
-    """assemble: "host" (libccio assembles the stage outputs' records, the default) or "device" (the
+                       assemble="host", names="host"):
+    """names: "host" (libccio formats the consensus read names, the default) or "device" (the engine's
+    name formatter, Engine.device_names: the same names, so the same files).  assemble: "host" (libccio assembles the stage outputs' records, the default) or "device" (the
     engine's record assembler builds each output stream from the votes' device buffers,
     Engine.device_assemble: the same files).  bgzf: "host" (libccio's codec, the default) or "device" (the engine's BGZF encoder deflates the
     output files: same records, other compressed bytes and .bai offsets).  bgzf_effort: the device
@@ -71,6 +72,17 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
     come from the device; same bytes read, same files written); it engages only with inflate="device"
     or bgzf="device" and is otherwise without effect.  Each option is wired for this call only; see
     _consensus_pipeline."""
+    if names not in ("host", "device"):
+        raise ValueError('names must be "host" or "device"')
+    if names == "device":
+        engine = engine or get_engine()
+        was_names = engine.device_names(True)
+        try:
+            return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                      cleanup_files, all_unique_sscs, bgzf, inflate, decode, bgzf_effort, resident, crc,
+                                      assemble)
+        finally:
+            engine.device_names(was_names)
     if assemble not in ("host", "device"):
         raise ValueError('assemble must be "host" or "device"')
     if assemble == "device":

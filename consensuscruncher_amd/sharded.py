@@ -622,8 +622,9 @@ def to_owners(comm, geo, parts):
 def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|", scorrect="True", level=6,
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
                      cuts=None, bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host",
-                     crc="host", assemble="host"):
-    """assemble: "host" (the default) or "device": this rank's stage outputs assembled by the engine's
+                     crc="host", assemble="host", names="host"):
+    """names: "host" (the default) or "device": this rank's consensus read names formatted by the
+    engine's name formatter (Engine.device_names).  assemble: "host" (the default) or "device": this rank's stage outputs assembled by the engine's
     record assembler where their sources hold their records in place (Engine.device_assemble; a
     rank's combined and routed views are assembled on the host as before).
     bgzf: "host" (the default) or "device": this rank's output files deflated by the engine's BGZF
@@ -635,6 +636,16 @@ def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|
     uploaded as before).  crc: "host" (the default) or "device": this rank's device inflater and encoder
     take their CRC32s from the device (Engine.device_crc; only with inflate="device" or bgzf="device").
     These are pipeline.consensus_pipeline's options; see _sharded_pipeline."""
+    if names not in ("host", "device"):
+        raise ValueError('names must be "host" or "device"')
+    if names == "device":
+        was_names = engine.device_names(True)
+        try:
+            return sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                    blocks, held, refs, keep, finalize, timings, cuts, bgzf, inflate, decode,
+                                    bgzf_effort, resident, crc, assemble)
+        finally:
+            engine.device_names(was_names)
     if assemble not in ("host", "device"):
         raise ValueError('assemble must be "host" or "device"')
     if assemble == "device":

@@ -120,7 +120,7 @@ class SSCSRun(object):
         ne = len(emit_n)
         self.times["emit_fetch"] = time.time() - t0
         t0 = time.time()
-        names, name_off = csn_names(it, emit_ckey, emit_n)
+        names, name_off = eng.csn_names(it, emit_ckey, emit_n) if eng.names_device else csn_names(it, emit_ckey, emit_n)
         self.times["emit_names"] = time.time() - t0
         t0 = time.time()
         voted = emit_vslot >= 0
@@ -342,7 +342,10 @@ class DCSRun(object):
         nm = int(made.sum())
         self.times["emit_fetch"] = time.time() - t0
         t0 = time.time()
-        names, name_off = dcs_names(bam, t_rec[made], p_rec[made])
+        if eng.names_device:
+            names, name_off = eng.dcs_names(bam, self.table, t_rec[made], p_rec[made])
+        else:
+            names, name_off = dcs_names(bam, t_rec[made], p_rec[made])
         self.times["emit_names"] = time.time() - t0
         t0 = time.time()
         sp = _new_specs(nm, t_rec[made], np.arange(nm), vslot[made], meta, qstride)
@@ -483,7 +486,8 @@ class SCRun(object):
         for code, name in ((0, "sscs.correction"), (1, "singleton.correction")):
             m = dec == code
             k = int(m.sum())
-            names, name_off = csn_names(it, q_ckey[m], np.ones(k, np.int64))
+            fmt = eng.csn_names if eng.names_device else csn_names
+            names, name_off = fmt(it, q_ckey[m], np.ones(k, np.int64))
             sp = _new_specs(k, t_rec[m], np.arange(k), vslot[m], meta, qstride)
             write_bam('{}.{}.bam'.format(base, name), sbam, it, sp, [sbam], names, name_off, cons_seq, cons_qual,
                       level, sink=sink, cons_group=cgroup)

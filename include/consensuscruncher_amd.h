@@ -174,6 +174,13 @@ int ccio_dcs_name(const char *tag, const char *ds, char *out, int cap);
 int ccio_duplex_tag(const char *tag, char *out, int cap);
 int64_t ccio_format_dcs_names(ccio_bam *b, int64_t n, const int64_t *rec_tag, const int64_t *rec_ds,
                               char *blob, int64_t cap, int64_t *off);
+/* 1 when every name ccio_format_dcs_names reads for these pairs (l_read_name - 1 bytes) holds no NUL and
+ * is terminated, so that it is the bytes a record table keeps (its qn_len is a strnlen); 0 when one
+ * is not; -1 for a record index outside b. */
+int ccio_dcs_names_plain(ccio_bam *b, int64_t n, const int64_t *rec_tag, const int64_t *rec_ds);
+/* An interner table's strings side by side: off[0 .. ccio_interner_size] their offsets, string i is
+ * blob[off[i], off[i + 1]).  Returns the bytes in all; blob NULL: the offsets only; -1 when cap is short. */
+int64_t ccio_interner_blob(ccio_interner *it, int kind, char *blob, int64_t cap, int64_t *off);
 int ccio_write_bam(const char *path, ccio_bam *tmpl, ccio_interner *it, int64_t n, const cc_out_spec *spec,
                    ccio_bam *const *srcs, int nsrc, const char *names, const int64_t *name_off,
                    const uint8_t *cons_seq, const uint8_t *cons_qual, int level, int nthreads);
@@ -621,6 +628,29 @@ int cc_bam_assemble_hook(cc_ctx *ctx, ccio_assemble_fn *fn, void **user);
 /* the group whose consensus buffers the hook's next call uses when libccio passes it no arrays (that
  * call consumes it); -1 clears it */
 int cc_bam_assemble_group(cc_ctx *ctx, int32_t group_id);
+/* The consensus read names formatted on the device (csrc/name_core.h, name_format.hip.inc), byte for
+ * byte what ccio_format_csn_names / ccio_format_dcs_names give.  Both take host arrays, write
+ * off[n + 1] (name i is bytes [off[i], off[i + 1]) of the blob) and *total (= off[n]), and leave the
+ * blob in a device buffer the context owns until cc_names_read fetches it; a new format call or
+ * cc_destroy releases a blob nobody read.
+ *   csn: f9 holds nine int32 fields per name, suffix one int64; the barcode strings (field 0) and the
+ *     cigar strings (fields 5, 6) come side by side with n_bc + 1 / n_cg + 1 offsets
+ *     (ccio_interner_blob).
+ *   dcs: rec_tag / rec_ds are record indices into `table`, whose qname slots hold the two names.
+ * A name the shared rules refuse (csn: field 0 outside the barcode table, field 5 or 6 outside the
+ * cigar table; dcs: no '_' or no ':' in the tag name, no ':' in the partner name, a record index
+ * outside the table) is CC_E_INVALID, and cc_last_error names the first such name and the reason; a
+ * blob of 2^32 bytes or more, or more than 2^31 - 1 names, is CC_E_UNSUPPORTED.  After any error no
+ * blob exists and nothing the call allocated stays allocated.  With profiling on, cc_kernel_times
+ * reports the kernels as "name_sizes" and "name_write", the offsets' scan as "name_scan". */
+int cc_format_csn_names(cc_ctx *ctx, int64_t n, const int32_t *f9, const int64_t *suffix, const char *bc_blob,
+                        const int64_t *bc_off, int64_t n_bc, const char *cg_blob, const int64_t *cg_off, int64_t n_cg,
+                        int64_t *off, int64_t *total);
+int cc_format_dcs_names(cc_ctx *ctx, int32_t table, int64_t n, const int64_t *rec_tag, const int64_t *rec_ds,
+                        int64_t *off, int64_t *total);
+/* The last formatted blob copied to blob[0, total) and its device buffer released.  cap < total is
+ * CC_E_INVALID and keeps the buffer, as does a call without a blob to read. */
+int cc_names_read(cc_ctx *ctx, char *blob, int64_t cap);
 /* cc_table_unpack with the records read in place from a resident stream (cc_bgzf_inflate_keep): they
  * are its bytes [base, base + bytes), which must lie inside it (else CC_E_INVALID), and rec_off counts
  * from base, as ccio_bam_decode_ids gives it.  Checks, errors and the table are cc_table_unpack's;
