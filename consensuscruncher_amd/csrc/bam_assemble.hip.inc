@@ -118,9 +118,11 @@ __global__ __launch_bounds__(ASM_T) void k_asm_copy(asmb::Tables T, const asmb::
 struct AsmGuard {
     cc_ctx* ctx;
     std::vector<void*> tmp;
+    uint8_t* kept = nullptr;   // cc_bam_assemble_keep's stream until the call has succeeded
     ~AsmGuard() {
         (void)hipStreamSynchronize(ctx->stream);   // nothing enqueued still uses them
         for (void* p : tmp) (void)hipFree(p);
+        if (kept) (void)hipFree(kept);
     }
 };
 
@@ -169,9 +171,11 @@ struct AsmArgs {
 
 // cc_bam_assemble's work.  The stream's buffer comes from alloc(actx, total) once the sizes are known
 // (null alloc: a size query, null result: CC_E_INVALID); the caller holds the encoder's mutex when a
-// source is resident.
+// source is resident.  With keep (cc_bam_assemble_keep; the caller holds the mutex) the stream is built
+// in a buffer of its own with a resident stream's padding, which *keep receives when the call
+// succeeds; it is downloaded only when alloc is given.
 int bam_assemble(cc_ctx* ctx, const AsmArgs& a, const std::vector<const uint8_t*>& resident, cc_asm_alloc_fn alloc,
-                 void* actx, uint64_t* at, uint64_t* total) {
+                 void* actx, uint64_t* at, uint64_t* total, Resident* keep = nullptr) {
     const int64_t n = a.n;
     if (n > (int64_t)INT32_MAX) { ctx->err = "cc_bam_assemble: more than 2^31 - 1 records"; return CC_E_UNSUPPORTED; }
     RC(enter(ctx));
@@ -256,12 +260,25 @@ int bam_assemble(cc_ctx* ctx, const AsmArgs& a, const std::vector<const uint8_t*
         sum += h_st->total;
     }
     if (total) *total = sum;
-    if (!alloc) return 0;   // a size query
-    uint8_t* out = alloc(actx, sum);
-    if (!out || !at) { ctx->err = "cc_bam_assemble: no buffer for the stream"; return CC_E_INVALID; }
+    if (!alloc && !keep) return 0;   // a size query
+    uint8_t* out = alloc ? alloc(actx, sum) : nullptr;
+    if ((alloc && !out) || !at) { ctx->err = "cc_bam_assemble: no buffer for the stream"; return CC_E_INVALID; }
     at[0] = a.header_bytes;
+    uint8_t* d_out = nullptr;
+    if (keep) {   // `sum` usable bytes, the bytes behind them zero (the resident streams' contract)
+        const size_t padded = (size_t)((sum + 15) & ~15ull) + 32;
+        HIPCHK(hipMalloc((void**)&guard.kept, padded));
+        d_out = guard.kept;
+        HIPCHK(hipMemsetAsync(d_out + sum, 0, padded - (size_t)sum, ctx->stream));
+    }
     if (n == 0) {
-        if (a.header_bytes) memcpy(out, a.header, (size_t)a.header_bytes);
+        if (a.header_bytes && out) memcpy(out, a.header, (size_t)a.header_bytes);
+        if (keep) {
+            if (a.header_bytes) HIPCHK(hipMemcpyAsync(d_out, a.header, (size_t)a.header_bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            *keep = Resident{guard.kept, sum};
+            guard.kept = nullptr;
+        }
         return 0;
     }
     if (a.flags & CCIO_W_SORT) {
@@ -281,8 +298,7 @@ int bam_assemble(cc_ctx* ctx, const AsmArgs& a, const std::vector<const uint8_t*
     const int64_t cap = std::min(per, n);
     RC(dev_alloc(ctx, guard.tmp, &ssz, cap, 64));
     RC(dev_alloc(ctx, guard.tmp, &off32, cap, 64));
-    uint8_t* d_out = nullptr;
-    RC(dev_alloc(ctx, guard.tmp, &d_out, (int64_t)sum, 64));
+    if (!keep) RC(dev_alloc(ctx, guard.tmp, &d_out, (int64_t)sum, 64));
     uint64_t* d_at = nullptr;
     RC(dev_alloc(ctx, guard.tmp, &d_at, n + 1));
     if (a.header_bytes) HIPCHK(hipMemcpyAsync(d_out, a.header, (size_t)a.header_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -300,17 +316,26 @@ int bam_assemble(cc_ctx* ctx, const AsmArgs& a, const std::vector<const uint8_t*
         base += h_st->tot;
     }
     if (base != sum) { ctx->err = "cc_bam_assemble: the offsets' scan totals do not match the sizes"; return CC_E_INVALID; }
-    {
+    if (out) {
         ProfScope ps(ctx, "asm_download");
         HIPCHK(hipMemcpyAsync(out, d_out, (size_t)sum, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(at, d_at, sizeof(uint64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    } else {   // a kept stream nobody wants on the host: the offsets alone
+        HIPCHK(hipMemcpyAsync(at, d_at, sizeof(uint64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (keep) {
+        *keep = Resident{guard.kept, sum};
+        guard.kept = nullptr;
+    }
     return 0;
 }
 
-// the arguments checked, the resident sources found (under the encoder's mutex, held until the kernels are done)
-int bam_assemble_locked(cc_ctx* ctx, const AsmArgs& a, cc_asm_alloc_fn alloc, void* actx, uint64_t* at, uint64_t* total) {
+// the arguments checked, the resident sources found (under the encoder's mutex, held until the kernels are done);
+// with rid the stream stays on the device, registered in the resident table under *rid (0 after any error)
+int bam_assemble_locked(cc_ctx* ctx, const AsmArgs& a, cc_asm_alloc_fn alloc, void* actx, uint64_t* at, uint64_t* total,
+                        int64_t* rid = nullptr) {
+    if (rid) *rid = 0;
     if (!ctx) return CC_E_INVALID;
     if (a.n < 0 || a.nsrc < 0 || a.n_names < 0 || a.n_rg < 0 || (a.header_bytes && !a.header) ||
         (a.n > 0 && (!a.spec || (a.nsrc > 0 && !a.srcs))) || (a.n_names > 0 && !a.name_off) || (a.names_bytes && !a.names) ||
@@ -330,7 +355,7 @@ int bam_assemble_locked(cc_ctx* ctx, const AsmArgs& a, cc_asm_alloc_fn alloc, vo
         }
         any = any || s.resident_id;
     }
-    if (!any) return bam_assemble(ctx, a, resident, alloc, actx, at, total);
+    if (!any && !rid) return bam_assemble(ctx, a, resident, alloc, actx, at, total);
     BgzfEnc* E = bgzf_get(ctx);
     std::lock_guard<std::mutex> lk(E->mu);
     for (int32_t f = 0; f < a.nsrc; ++f) {
@@ -349,7 +374,13 @@ int bam_assemble_locked(cc_ctx* ctx, const AsmArgs& a, cc_asm_alloc_fn alloc, vo
     HIPCHK(hipSetDevice(ctx->device));
     for (int b = 0; b < 2; ++b)   // the inflater's and the patches' writes are done before the first kernel
         if (E->st[b]) HIPCHK(hipStreamSynchronize(E->st[b]));
-    return bam_assemble(ctx, a, resident, alloc, actx, at, total);
+    if (!rid) return bam_assemble(ctx, a, resident, alloc, actx, at, total);
+    Resident R;
+    RC(bam_assemble(ctx, a, resident, alloc, actx, at, total, &R));
+    if (!E->dec) E->dec = new BgzfDec();   // the table's home (its coder buffers are made by the first inflate)
+    *rid = g_resident_next.fetch_add(1);
+    E->dec->res[*rid] = R;
+    return 0;
 }
 
 struct AsmFixed {
@@ -394,6 +425,23 @@ int cc_bam_assemble(cc_ctx* ctx, const uint8_t* header, uint64_t header_bytes, c
     AsmFixed f{out, cap};
     const int rc = bam_assemble_locked(ctx, a, out ? asm_fixed_alloc : nullptr, &f, at, total);
     if (rc == CC_E_INVALID && out && total && *total > cap && ctx) ctx->err = "cc_bam_assemble: the buffer is smaller than the stream";
+    return rc;
+}
+
+int cc_bam_assemble_keep(cc_ctx* ctx, const uint8_t* header, uint64_t header_bytes, const cc_asm_src* srcs, int32_t nsrc,
+                         const cc_out_spec* spec, int64_t n, const char* names, const int64_t* name_off, int64_t n_names,
+                         uint64_t names_bytes, const uint8_t* cons_seq, uint64_t cons_seq_bytes, const uint8_t* cons_qual,
+                         uint64_t cons_qual_bytes, int32_t cons_group, const char* rg_blob, const int64_t* rg_off, int32_t n_rg,
+                         int flags, uint8_t* out, uint64_t cap, uint64_t* at, uint64_t* total, int64_t* resident_id) {
+    if (!ctx || !resident_id) return CC_E_INVALID;
+    *resident_id = 0;
+    if (!at || !total) { ctx->err = "cc_bam_assemble_keep: at and total are required"; return CC_E_INVALID; }
+    *total = 0;
+    const AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
+                    cons_seq_bytes, cons_qual, cons_qual_bytes, cons_group, rg_blob, rg_off, n_rg, flags};
+    AsmFixed f{out, cap};
+    const int rc = bam_assemble_locked(ctx, a, out ? asm_fixed_alloc : nullptr, &f, at, total, resident_id);
+    if (rc == CC_E_INVALID && out && *total > cap) ctx->err = "cc_bam_assemble_keep: the buffer is smaller than the stream";
     return rc;
 }
 

@@ -490,6 +490,10 @@ struct BgzfEnc {
     CrcBufs cb;             // the encoder's CRC values (made by the first round with crc_on)
     double crc_ms = 0;      // k_crc32 of every caller on these streams (scope bgzf_crc32)
     int64_t crc_n = 0;
+    double idx_ms = 0;      // k_index_fields (scope index_fields)
+    int64_t idx_n = 0;
+    double put_ms = 0;      // cc_resident_put's uploads (scope resident_put)
+    int64_t put_n = 0;
     BgzfDec* dec = nullptr;
     std::string err;
     hipStream_t st[2] = {nullptr, nullptr};
@@ -503,8 +507,9 @@ struct BgzfEnc {
     uint32_t* d_len[2] = {nullptr, nullptr};
     hipEvent_t ev[2][6] = {};   // per stream: around the kernel, the upload, the download
     bool timed[2] = {false, false};
+    bool up_timed[2] = {false, false};   // the launch uploaded its input (not one fed from a resident stream)
     double prof_ms = 0, h2d_ms = 0, d2h_ms = 0;   // the kernel (scope bgzf_deflate), the two copies
-    int64_t prof_n = 0;
+    int64_t prof_n = 0, h2d_n = 0;
     uint32_t (*crc_ld)(uint32_t, const void*, size_t) = nullptr;       // libdeflate_crc32
     unsigned long (*crc_z)(unsigned long, const uint8_t*, unsigned) = nullptr;   // zlib's crc32
     uint32_t crc(const uint8_t* p, size_t n) const {
@@ -591,7 +596,8 @@ BgzfEnc* bgzf_get(cc_ctx* ctx) {
 
 // the encoder's kernel time so far (or its reset); the pointer is read under the mutex that guards
 // its creation by a writer thread
-void bgzf_prof(cc_ctx* ctx, bool reset, double* ms, int64_t* n, double* h2d = nullptr, double* d2h = nullptr) {
+void bgzf_prof(cc_ctx* ctx, bool reset, double* ms, int64_t* n, double* h2d = nullptr, double* d2h = nullptr,
+               int64_t* h2d_n = nullptr) {
     BgzfEnc* E;
     {
         std::lock_guard<std::mutex> lk(ctx->bgzf_mu);
@@ -599,8 +605,9 @@ void bgzf_prof(cc_ctx* ctx, bool reset, double* ms, int64_t* n, double* h2d = nu
     }
     if (!E) return;
     std::lock_guard<std::mutex> lk(E->mu);
-    if (reset) { E->prof_ms = E->h2d_ms = E->d2h_ms = 0; E->prof_n = 0; }
+    if (reset) { E->prof_ms = E->h2d_ms = E->d2h_ms = 0; E->prof_n = E->h2d_n = 0; }
     if (h2d) *h2d = E->h2d_ms;
+    if (h2d_n) *h2d_n = E->h2d_n;
     if (d2h) *d2h = E->d2h_ms;
     if (ms) *ms = E->prof_ms;
     if (n) *n = E->prof_n;
@@ -620,6 +627,22 @@ void bgzf_crc_prof(cc_ctx* ctx, bool reset, double* ms, int64_t* n) {
     if (n) *n = E->crc_n;
 }
 
+// k_index_fields' time so far (or its reset)
+void bgzf_idx_prof(cc_ctx* ctx, bool reset, double* ms, int64_t* n, double* put_ms = nullptr, int64_t* put_n = nullptr) {
+    BgzfEnc* E;
+    {
+        std::lock_guard<std::mutex> lk(ctx->bgzf_mu);
+        E = ctx->bgzf;
+    }
+    if (!E) return;
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (reset) { E->idx_ms = E->put_ms = 0; E->idx_n = E->put_n = 0; }
+    if (put_ms) *put_ms = E->put_ms;
+    if (put_n) *put_n = E->put_n;
+    if (ms) *ms = E->idx_ms;
+    if (n) *n = E->idx_n;
+}
+
 // a finished, timed k_crc32 launch of set B's stream b added to the scope
 int crc_prof_add(BgzfEnc* E, CrcBufs* B, int b) {
     if (!B->timed[b]) return 0;
@@ -635,11 +658,14 @@ int crc_prof_add(BgzfEnc* E, CrcBufs* B, int b) {
 // its own pinned and device buffers: while one launch encodes, the previous one's members are
 // downloaded and framed and the next one's input is staged; the CRCs are computed meanwhile, by the
 // calling thread or (crc_on) by k_crc32 over the launch's input buffer, behind its encoder kernels.
+// With dev (cc_bgzf_deflate_resident: n bytes of a resident stream at a 256-byte multiple of it, data
+// null) the kernels read their pieces where they lie: nothing is staged or uploaded, and the CRCs are
+// always k_crc32's.
 int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, uint8_t* stage, uint64_t slot,
-                    uint32_t* out_len, int64_t cap) {
+                    uint32_t* out_len, int64_t cap, const uint8_t* dev = nullptr) {
     const int64_t np = (int64_t)((n + BG_PIECE - 1) / BG_PIECE);
     if (np == 0) return 0;
-    if (!data || !stage || !out_len || slot < 0x10000 || np > cap) {
+    if ((!data && !dev) || !stage || !out_len || slot < 0x10000 || np > cap) {
         E->err = "cc_bgzf_deflate: null argument, slot under 65536 or more pieces than cap";
         return CC_E_INVALID;
     }
@@ -647,7 +673,7 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
     BGCHK(hipSetDevice(ctx->device));   // (not enter(): a writer's thread, the switches are the engine thread's)
     if (!E->ready) RC(bgzf_init(E));
     const bool prof = ctx->profiling;
-    const bool dev_crc = E->crc_on;   // the whole round one way
+    const bool dev_crc = E->crc_on || dev;   // the whole round one way
     if (dev_crc) BGCHK(crc_bufs_init(&E->cb, BG_CHUNK));
     const auto kernel = E->effort == 2 ? k_bgzf_deflate<2> : k_bgzf_deflate<1>;   // the whole round at one effort
     const int64_t nchunks = (np + BG_CHUNK - 1) / BG_CHUNK;
@@ -656,21 +682,24 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
     auto launch = [&](int64_t k) -> int {
         const int b = (int)(k & 1), pc = pieces_of(k);
         const uint64_t o = (uint64_t)k * BG_CHUNK * BG_PIECE, bytes = std::min<uint64_t>(n - o, (uint64_t)pc * BG_PIECE);
-        memcpy(E->h_in[b], data + o, bytes);
-        if (prof) BGCHK(hipEventRecord(E->ev[b][2], E->st[b]));
-        BGCHK(hipMemcpyAsync(E->d_in[b], E->h_in[b], bytes, hipMemcpyHostToDevice, E->st[b]));
-        if (prof) BGCHK(hipEventRecord(E->ev[b][3], E->st[b]));
+        const uint8_t* in = dev ? dev + o : E->d_in[b];
+        if (!dev) {
+            memcpy(E->h_in[b], data + o, bytes);
+            if (prof) BGCHK(hipEventRecord(E->ev[b][2], E->st[b]));
+            BGCHK(hipMemcpyAsync(E->d_in[b], E->h_in[b], bytes, hipMemcpyHostToDevice, E->st[b]));
+            if (prof) BGCHK(hipEventRecord(E->ev[b][3], E->st[b]));
+        }
         E->timed[b] = prof;
+        E->up_timed[b] = prof && !dev;
         if (prof) BGCHK(hipEventRecord(E->ev[b][0], E->st[b]));
-        klaunch(E->st[b], kernel, (unsigned)pc, BG_T, E->d_in[b], (uint64_t)bytes, E->d_tok[b], E->d_out[b],
-                E->d_len[b]);
+        klaunch(E->st[b], kernel, (unsigned)pc, BG_T, in, (uint64_t)bytes, E->d_tok[b], E->d_out[b], E->d_len[b]);
         if (prof) BGCHK(hipEventRecord(E->ev[b][1], E->st[b]));
         klaunch(E->st[b], k_bgzf_pack, (unsigned)pc, 256, E->d_out[b], E->d_len[b], E->d_pack[b]);
         BGCHK(hipGetLastError());
         BGCHK(hipMemcpyAsync(E->h_len[b], E->d_len[b], (size_t)pc * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[b]));
         if (dev_crc) {
             E->cb.timed[b] = prof;
-            BGCHK(crc_launch(E->st[b], prof ? E->cb.ev[b] : nullptr, E->d_in[b], nullptr, CR_PIECE, bytes, E->cb.d[b], pc));
+            BGCHK(crc_launch(E->st[b], prof ? E->cb.ev[b] : nullptr, in, nullptr, CR_PIECE, bytes, E->cb.d[b], pc));
             BGCHK(hipMemcpyAsync(E->cb.h[b], E->cb.d[b], (size_t)pc * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st[b]));
         }
         return 0;
@@ -683,8 +712,12 @@ int64_t bgzf_encode(cc_ctx* ctx, BgzfEnc* E, const uint8_t* data, uint64_t n, ui
             BGCHK(hipEventElapsedTime(&ms, E->ev[b][0], E->ev[b][1]));
             E->prof_ms += ms;
             E->prof_n += 1;
+        }
+        if (E->up_timed[b]) {
+            float ms = 0;
             BGCHK(hipEventElapsedTime(&ms, E->ev[b][2], E->ev[b][3]));
             E->h2d_ms += ms;
+            E->h2d_n += 1;
         }
         if (dev_crc) RC(crc_prof_add(E, &E->cb, b));
         uint64_t words = 0;

@@ -584,6 +584,76 @@ int crc_ranges(cc_ctx* ctx, BgzfEnc* E, const char* who, const uint8_t* base, ui
     return 0;
 }
 
+// cc_bgzf_deflate_resident's work: the range checked against the stream, then bgzf_encode over the
+// device bytes themselves (the caller holds the mutex)
+int64_t bgzf_encode_resident(cc_ctx* ctx, BgzfEnc* E, int64_t id, uint64_t off, uint64_t n, uint8_t* stage, uint64_t slot,
+                             uint32_t* out_len, int64_t cap) {
+    const Resident* R = resident_find(E, id);
+    if (!R) { E->err = "cc_bgzf_deflate_resident: unknown id"; return CC_E_INVALID; }
+    if (off % 256) { E->err = "cc_bgzf_deflate_resident: off is not a multiple of 256"; return CC_E_INVALID; }
+    if (off > R->total || n > R->total - off) {
+        E->err = "cc_bgzf_deflate_resident: the range does not lie inside the stream";
+        return CC_E_INVALID;
+    }
+    return bgzf_encode(ctx, E, nullptr, n, stage, slot, out_len, cap, R->p + off);
+}
+
+// cc_resident_put's work: host bytes as a resident stream (the caller holds the mutex)
+int resident_put(cc_ctx* ctx, BgzfEnc* E, const uint8_t* bytes, uint64_t n, int64_t* id) {
+    *id = 0;
+    if (n > 0 && !bytes) { E->err = "cc_resident_put: null bytes"; return CC_E_INVALID; }
+    if (E->broken) return CC_E_HIP;
+    BGCHK(hipSetDevice(ctx->device));
+    RC(bgzf_streams(E));
+    Resident R;
+    R.total = n;
+    const size_t padded = bi_align((size_t)n) + 32;
+    if (hipMalloc((void**)&R.p, padded) != hipSuccess) {
+        (void)hipGetLastError();   // (out of memory is no reason for the latch)
+        E->err = "cc_resident_put: no device memory for the stream";
+        return CC_E_HIP;
+    }
+    const bool prof = ctx->profiling;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && prof && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+    if (e == hipSuccess && prof) e = hipEventRecord(ev[0], E->st[0]);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(R.p, bytes, (size_t)n, hipMemcpyHostToDevice, E->st[0]);
+    if (e == hipSuccess) e = hipMemsetAsync(R.p + n, 0, padded - (size_t)n, E->st[0]);
+    if (e == hipSuccess && prof) e = hipEventRecord(ev[1], E->st[0]);
+    const hipError_t es = hipStreamSynchronize(E->st[0]);
+    if (e == hipSuccess) e = es;
+    float ms = 0;
+    if (e == hipSuccess && prof) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (e == hipSuccess && prof) { E->put_ms += ms; E->put_n += 1; }
+    for (int k = 0; k < 2; ++k)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    if (e != hipSuccess) {
+        (void)hipFree(R.p);
+        BGCHK(e);
+    }
+    if (!E->dec) E->dec = new BgzfDec();
+    *id = g_resident_next.fetch_add(1);
+    E->dec->res[*id] = R;
+    return 0;
+}
+
+// [off, off + n) of a resident stream copied to dst (the caller holds the mutex)
+int resident_fetch_range(cc_ctx* ctx, BgzfEnc* E, int64_t id, uint64_t off, uint64_t n, uint8_t* dst) {
+    const Resident* R = resident_find(E, id);
+    if (!R || off > R->total || n > R->total - off || (n > 0 && !dst)) {
+        E->err = R ? "cc_resident_fetch: the range does not lie inside the stream" : "cc_resident_fetch: unknown id";
+        return CC_E_INVALID;
+    }
+    if (n == 0) return 0;
+    if (E->broken) return CC_E_HIP;
+    BGCHK(hipSetDevice(ctx->device));
+    RC(bgzf_streams(E));
+    BGCHK(hipMemcpyAsync(dst, R->p + off, (size_t)n, hipMemcpyDeviceToHost, E->st[0]));
+    BGCHK(hipStreamSynchronize(E->st[0]));
+    return 0;
+}
+
 int bgzf_patch_hook_fn(void* user, int64_t token, uint64_t off, const uint8_t* bytes, uint64_t n) {
     cc_ctx* ctx = (cc_ctx*)user;
     if (!ctx) return 1;
@@ -674,6 +744,25 @@ int64_t cc_resident_fetch(cc_ctx* ctx, int64_t id, uint8_t* dst, uint64_t cap) {
         }
     }
     return (int64_t)R->total;
+}
+
+int64_t cc_bgzf_deflate_resident(cc_ctx* ctx, int64_t id, uint64_t off, uint64_t n, uint8_t* stage, uint64_t slot,
+                                 uint32_t* out_len, int64_t cap) {
+    if (!ctx) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const int64_t r = bgzf_encode_resident(ctx, E, id, off, n, stage, slot, out_len, cap);
+    if (r < 0) ctx->err = E->err;
+    return r;
+}
+
+int cc_resident_put(cc_ctx* ctx, const uint8_t* bytes, uint64_t n, int64_t* id) {
+    if (!ctx || !id) return CC_E_INVALID;
+    BgzfEnc* E = bgzf_get(ctx);
+    std::lock_guard<std::mutex> lk(E->mu);
+    const int rc = resident_put(ctx, E, bytes, n, id);
+    if (rc) ctx->err = E->err;
+    return rc;
 }
 
 int64_t cc_resident_count(cc_ctx* ctx) {

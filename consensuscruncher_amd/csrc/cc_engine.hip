@@ -6207,6 +6207,7 @@ int cc_set_profiling(cc_ctx* ctx, int on) {
     if (on) bgzf_prof(ctx, true, nullptr, nullptr);
     if (on) bgzf_dec_prof(ctx, true, nullptr, nullptr, nullptr, nullptr);
     if (on) bgzf_crc_prof(ctx, true, nullptr, nullptr);
+    if (on) bgzf_idx_prof(ctx, true, nullptr, nullptr);
     return 0;
 }
 
@@ -6228,11 +6229,11 @@ int cc_kernel_times(cc_ctx* ctx, char* names, int names_cap, double* ms, int64_t
     flush_prof(ctx);
     {   // the encoder times its kernel on its own streams
         double bms = 0, up = 0, down = 0;
-        int64_t bn = 0;
-        bgzf_prof(ctx, false, &bms, &bn, &up, &down);
+        int64_t bn = 0, un = 0;
+        bgzf_prof(ctx, false, &bms, &bn, &up, &down, &un);
         if (bn) {
             ctx->prof["bgzf_deflate"] = {bms, bn};
-            ctx->prof["bgzf_upload"] = {up, bn};       // the launches' host-to-device copies
+            ctx->prof["bgzf_upload"] = {up, un};       // the launches' host-to-device copies (none from a resident stream)
             ctx->prof["bgzf_download"] = {down, bn};   // and the packed members' way back
         }
     }
@@ -6251,6 +6252,13 @@ int cc_kernel_times(cc_ctx* ctx, char* names, int names_cap, double* ms, int64_t
         int64_t cn = 0;
         bgzf_crc_prof(ctx, false, &cms, &cn);
         if (cn) ctx->prof["bgzf_crc32"] = {cms, cn};
+    }
+    {   // and the index-fields kernel, on the same streams
+        double xms = 0, pms = 0;
+        int64_t xn = 0, pn = 0;
+        bgzf_idx_prof(ctx, false, &xms, &xn, &pms, &pn);
+        if (xn) ctx->prof["index_fields"] = {xms, xn};
+        if (pn) ctx->prof["resident_put"] = {pms, pn};   // cc_resident_put's uploads
     }
     int i = 0;
     std::string all;
@@ -6631,6 +6639,7 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
 #include "table_unpack.hip.inc"
 #include "bam_assemble.hip.inc"
 #include "name_format.hip.inc"
+#include "bam_index.hip.inc"
 
 namespace {
 // Per-pass table preparation (timed with the pass): the member records; on a coordinate-sorted table

@@ -39,6 +39,7 @@
 
 #include "../../include/consensuscruncher_amd.h"
 #include "unpack_core.h"
+#include "index_core.h"
 
 namespace {
 
@@ -400,8 +401,9 @@ bool bgzf_inflate_all(const CVec& comp, Vec& out, int nthreads, std::string& err
     return true;
 }
 
+struct ResSrc;
 bool bgzf_deflate_blocks(FILE* f, const uint8_t* data, size_t n, int level, int nthreads,
-                         std::vector<uint64_t>* csize = nullptr);
+                         std::vector<uint64_t>* csize = nullptr, const ResSrc* rs = nullptr);
 
 bool bgzf_deflate_write(FILE* f, const uint8_t* data, size_t n, int level, int nthreads,
                         std::vector<uint64_t>* csize = nullptr) {
@@ -417,6 +419,30 @@ void* g_hook_user = nullptr;
 // device assembler of libccamd, or any function with its contract.
 ccio_assemble_fn g_asm_fn = nullptr;
 void* g_asm_user = nullptr;
+// The resident output set (ccio_set_out_resident): the assembled stream stays where the assembler
+// built it, and the encoder and the index read it there.
+bool g_outres_on = false;
+ccio_out_resident g_outres_cb = {};
+void* g_outres_user = nullptr;
+
+// a stream the resident set holds, as the writers below see it
+struct ResSrc {
+    ccio_out_resident cb;
+    void* user;
+    int64_t token;
+};
+// what hook_assemble leaves of a write that went to the set
+struct ResOut {
+    ResSrc rs{};
+    bool need_host = false;    // the caller keeps the stream (a kept handle, CCIO_W_MEMORY)
+    bool have_host = false;    // `all` holds the stream
+    bool have_fields = false;  // fields[n] passed the checks
+    std::vector<cc_index_field> fields;
+    uint64_t total = 0;
+};
+
+bool round_members_ok(size_t nbytes, size_t step, const uint8_t* stage, size_t slot, size_t pieces,
+                      const std::vector<uint32_t>& got, std::vector<size_t>& len);
 
 // One round through the hook: true when every member it reports is a framed BGZF member of its
 // piece (sizes and the BSIZE / ISIZE fields checked here); anything else leaves the round to the
@@ -433,6 +459,21 @@ bool hook_round(const uint8_t* data, size_t nbytes, size_t step, uint8_t* stage,
     if (!fn) return false;
     std::vector<uint32_t> got(pieces, 0);
     if (fn(user, data, (uint64_t)nbytes, stage, (uint64_t)slot, got.data(), (int64_t)pieces) != 0) return false;
+    return round_members_ok(nbytes, step, stage, slot, pieces, got, len);
+}
+
+// the same round through the resident set's encoder: the stream's bytes [off, off + nbytes)
+bool resident_round(const ResSrc& rs, uint64_t off, size_t nbytes, size_t step, uint8_t* stage, size_t slot, size_t pieces,
+                    std::vector<size_t>& len) {
+    if (!rs.cb.deflate) return false;
+    std::vector<uint32_t> got(pieces, 0);
+    if (rs.cb.deflate(rs.user, rs.token, off, (uint64_t)nbytes, stage, (uint64_t)slot, got.data(), (int64_t)pieces) != 0)
+        return false;
+    return round_members_ok(nbytes, step, stage, slot, pieces, got, len);
+}
+
+bool round_members_ok(size_t nbytes, size_t step, const uint8_t* stage, size_t slot, size_t pieces,
+                      const std::vector<uint32_t>& got, std::vector<size_t>& len) {
     for (size_t j = 0; j < pieces; ++j) {
         const size_t ln = std::min(step, nbytes - j * step), b = got[j];
         const uint8_t* h = stage + j * slot;
@@ -445,9 +486,12 @@ bool hook_round(const uint8_t* data, size_t nbytes, size_t step, uint8_t* stage,
 }
 
 // the BGZF members of data (no EOF marker): 0xff00-byte pieces compressed in parallel into one
-// staging area (a bounded slot per piece), written in order; csize gets each member's size
+// staging area (a bounded slot per piece), written in order; csize gets each member's size.
+// With rs the n bytes are a resident stream's: a round goes to the set's encoder first, and one it
+// refuses is compressed by the host codec from data, or (data null: no host copy) from the round's
+// bytes fetched for it.
 bool bgzf_deflate_blocks(FILE* f, const uint8_t* data, size_t n, int level, int nthreads,
-                         std::vector<uint64_t>* csize) {
+                         std::vector<uint64_t>* csize, const ResSrc* rs) {
     const size_t step = 0xff00;
     const size_t nb = (n + step - 1) / step;
     const size_t slot = 0x10000 + 64;   // a BGZF member is at most 64 KiB
@@ -460,27 +504,41 @@ bool bgzf_deflate_blocks(FILE* f, const uint8_t* data, size_t n, int level, int 
     std::vector<size_t> len2[2] = {std::vector<size_t>(rcap), std::vector<size_t>(rcap)};
     std::thread writer;
     std::atomic<bool> wbad(false);
+    std::vector<uint8_t> fetched;   // a refused round of a stream without a host copy
     int cur = 0;
     for (size_t r0 = 0; r0 < nb; r0 += round, cur ^= 1) {
         const size_t r1 = std::min(nb, r0 + round);
         uint8_t* const stage = stage2[cur].get();
         std::vector<size_t>& len = len2[cur];
         std::atomic<bool> bad(false);
-        const bool hooked = level >= 1 && hook_round(data + r0 * step, std::min(n, r1 * step) - r0 * step, step, stage,
-                                                     slot, r1 - r0, len);
+        const size_t rbytes = std::min(n, r1 * step) - r0 * step;
+        const uint8_t* rdata = data ? data + r0 * step : nullptr;
+        bool hooked;
+        if (rs) {
+            hooked = level >= 1 && resident_round(*rs, (uint64_t)(r0 * step), rbytes, step, stage, slot, r1 - r0, len);
+            if (!hooked && !rdata) {
+                fetched.resize(rbytes);
+                if (!rs->cb.fetch || rs->cb.fetch(rs->user, rs->token, (uint64_t)(r0 * step), (uint64_t)rbytes, fetched.data()) != 0) {
+                    if (writer.joinable()) writer.join();
+                    return false;
+                }
+                rdata = fetched.data();
+            }
+        } else {
+            hooked = level >= 1 && hook_round(rdata, rbytes, step, stage, slot, r1 - r0, len);
+        }
         if (!hooked) parallel_chunks((int64_t)(r1 - r0), nthreads, 8, [&](int64_t b, int64_t e) {
             Codec c;
             for (int64_t j = b; j < e && !bad; ++j) {
-                const size_t i = r0 + (size_t)j;
-                const size_t o = i * step, ln = std::min(step, n - o);
+                const size_t o = (size_t)j * step, ln = std::min(step, rbytes - o);
                 uint8_t* h = stage + (size_t)j * slot;
-                const size_t clen = c.deflate_raw(level, data + o, ln, h + 18, slot - 26);
+                const size_t clen = c.deflate_raw(level, rdata + o, ln, h + 18, slot - 26);
                 if (clen == 0 || clen + 26 > 0x10000) { bad = true; break; }
                 const size_t bsize = clen + 26;
                 const uint8_t hd[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 66, 67, 2, 0,
                                         (uint8_t)((bsize - 1) & 0xff), (uint8_t)((bsize - 1) >> 8)};
                 memcpy(h, hd, 18);
-                const uint32_t crc = c.crc32_of(data + o, ln);
+                const uint32_t crc = c.crc32_of(rdata + o, ln);
                 uint8_t* t = h + 18 + clen;
                 for (int k = 0; k < 4; ++k) t[k] = (crc >> (8 * k)) & 0xff;
                 for (int k = 0; k < 4; ++k) t[4 + k] = ((uint32_t)ln >> (8 * k)) & 0xff;
@@ -791,6 +849,15 @@ void ccio_set_assemble_hook(ccio_assemble_fn fn, void* user) {
     std::lock_guard<std::mutex> lk(g_hook_mu);
     g_asm_fn = fn;
     g_asm_user = fn ? user : nullptr;
+}
+
+// cb's callbacks keep ccio_write_bam_ex's assembled stream in a place of their own from now on (NULL:
+// the plain assemble and deflate hooks, or the host alone, again)
+void ccio_set_out_resident(const ccio_out_resident* cb, void* user) {
+    std::lock_guard<std::mutex> lk(g_hook_mu);
+    g_outres_on = cb && cb->assemble_keep && cb->fetch && cb->release;
+    g_outres_cb = g_outres_on ? *cb : ccio_out_resident{};
+    g_outres_user = g_outres_on ? user : nullptr;
 }
 
 void ccio_set_inflate_hook(ccio_inflate_fn fn, void* user) {
@@ -1134,6 +1201,25 @@ int ccio_bam_resident(ccio_bam* b, int64_t* token, uint64_t* base) {
     *token = b->res_token;
     *base = b->res_base;
     return 1;
+}
+
+int ccio_bam_set_resident(ccio_bam* b, int64_t token, uint64_t base) {
+    if (!b || !b->data || b->packed) return -1;
+    if (token && !b->rec.empty() && b->rec[0] != b->data->data() + base) return -1;
+    b->res_token = token;
+    b->res_base = token ? base : 0;
+    return 0;
+}
+
+// the stream of a handle whose records lie in place: its bytes and where its first record starts
+int ccio_bam_stream(ccio_bam* b, const uint8_t** data, uint64_t* bytes, uint64_t* rec_base) {
+    if (!b || !b->data || b->packed || !data || !bytes || !rec_base) return -1;
+    const uint8_t* lo = b->data->data();
+    *data = lo;
+    *bytes = (uint64_t)b->data->size();
+    *rec_base = b->rec.empty() ? *bytes : (uint64_t)(b->rec[0] - lo);
+    if (!b->rec.empty() && (b->rec[0] < lo || b->rec[0] >= lo + b->data->size())) return -1;
+    return 0;
 }
 
 void ccio_bam_close(ccio_bam* b) { delete b; }
@@ -1618,6 +1704,8 @@ namespace {
 
 int index_stream(const uint8_t* dp, size_t dn, const std::vector<uint64_t>& bco, const std::vector<uint64_t>& buo,
                  const char* path);
+int index_fields(const std::vector<uint8_t>& hdr, const std::vector<uint64_t>& at, const std::vector<cc_index_field>& fields,
+                 const std::vector<uint64_t>& bco, const std::vector<uint64_t>& buo, const char* path);
 
 inline uint64_t coord_key(const uint8_t* r) {   // r: record core (after block_size)
     const uint64_t tid = (uint32_t)rd32(r), pos = (uint32_t)(rd32(r + 4) + 1);
@@ -1934,6 +2022,113 @@ int write_stream_file(const std::string& path, const uint8_t* dp, size_t dn, int
     return 0;
 }
 
+// write_stream_file for a stream the resident set holds (dp null: no host copy of it): the rounds go
+// to the set's encoder, the index comes from the fields (fields null: the stream is walked, fetched
+// first when there is no host copy)
+int write_resident_file(const std::string& path, const ResSrc& rs, const uint8_t* dp, size_t dn,
+                        const std::vector<uint8_t>& hdr, const std::vector<uint64_t>& at,
+                        const std::vector<cc_index_field>* fields, int level, int T, int flags) {
+    PhaseTimer pt;
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) { set_err("cannot write " + path); return -1; }
+    std::vector<uint64_t> cs;
+    const bool ok = bgzf_deflate_blocks(f, dp, dn, level, T, (flags & CCIO_W_INDEX) ? &cs : nullptr, &rs) &&
+                    fwrite(kBgzfEof, 1, 28, f) == 28;
+    if (fclose(f) != 0 || !ok) { set_err("BGZF write failed: " + path); return -1; }
+    pt.lap("finish: resident deflate + write");
+    if (flags & CCIO_W_INDEX) {
+        std::vector<uint64_t> bco, buo;
+        uint64_t off = 0;
+        for (size_t i = 0; i < cs.size(); ++i) {
+            bco.push_back(off);
+            buo.push_back((uint64_t)i * 0xff00);
+            off += cs[i];
+        }
+        bco.push_back(off);
+        buo.push_back(dn);
+        if (fields) {
+            if (index_fields(hdr, at, *fields, bco, buo, path.c_str()) != 0) return -1;
+        } else {
+            Bytes got;
+            if (!dp) {
+                got.resize(dn);
+                if (rs.cb.fetch(rs.user, rs.token, 0, (uint64_t)dn, got.data()) != 0) {
+                    set_err("index: the resident stream could not be fetched: " + path);
+                    return -1;
+                }
+                dp = got.data();
+            }
+            if (index_stream(dp, dn, bco, buo, path.c_str()) != 0) return -1;
+        }
+        pt.lap("finish: index");
+    }
+    return 0;
+}
+
+// finish_stream for a stream the resident set holds: `all` is its host copy when ro.have_host.  The
+// token is released when the file is written (CCIO_W_ASYNC: by the writer thread); a kept handle owns
+// only the host copy.
+int finish_resident(const char* path, const ccio_bam* hdr, Bytes&& all, std::vector<uint64_t>&& at, ResOut&& ro, int level,
+                    int T, int flags, ccio_bam** keep) {
+    const ResSrc rs = ro.rs;
+    auto release = [rs]() { rs.cb.release(rs.user, rs.token); };
+    if ((flags & CCIO_W_MEMORY) && !keep) { release(); set_err("CCIO_W_MEMORY needs a kept handle"); return -1; }
+    if (!(flags & CCIO_W_MEMORY)) wait_path(path);   // an earlier asynchronous write of the same file
+    std::unique_ptr<ccio_bam> nb;
+    if (keep) {   // (need_host was 1: the copy is there)
+        nb.reset(new ccio_bam());
+        nb->header_text = hdr->header_text;
+        nb->refs = hdr->refs;
+        nb->header_raw = hdr->header_raw;
+        nb->data = std::make_shared<Bytes>(std::move(all));
+        const uint8_t* base = nb->data->data();
+        nb->rec.resize(at.size() - 1);
+        parallel_chunks((int64_t)nb->rec.size(), T, 1 << 16, [&](int64_t a, int64_t e) {
+            for (int64_t i = a; i < e; ++i) nb->rec[i] = base + at[i];
+        });
+    }
+    if (flags & CCIO_W_MEMORY) {
+        release();
+        *keep = nb.release();
+        return 0;
+    }
+    const size_t dn = (size_t)ro.total;
+    const bool have_fields = ro.have_fields;
+    if (!(flags & CCIO_W_ASYNC)) {
+        const uint8_t* dp = nb ? nb->data->data() : (ro.have_host ? all.data() : nullptr);
+        const int rc = write_resident_file(path, rs, dp, dn, hdr->header_raw, at, have_fields ? &ro.fields : nullptr, level, T,
+                                           flags);
+        release();
+        if (rc != 0) return -1;
+        if (keep) *keep = nb.release();
+        return 0;
+    }
+    std::shared_ptr<Bytes> own;
+    if (!nb && ro.have_host) own = std::make_shared<Bytes>(std::move(all));
+    const uint8_t* dp = nb ? nb->data->data() : (own ? own->data() : nullptr);
+    auto err = std::make_shared<std::string>();
+    const std::string p = abs_path(path);
+    auto hraw = std::make_shared<std::vector<uint8_t>>(hdr->header_raw);
+    auto atp = std::make_shared<std::vector<uint64_t>>(std::move(at));
+    auto fl = std::make_shared<std::vector<cc_index_field>>(std::move(ro.fields));
+    std::shared_future<int> fut =
+        std::async(std::launch::async, [p, rs, dp, dn, hraw, atp, fl, have_fields, level, T, flags, err, own]() {
+            const int rc = write_resident_file(p, rs, dp, dn, *hraw, *atp, have_fields ? fl.get() : nullptr, level, T, flags);
+            rs.cb.release(rs.user, rs.token);
+            if (rc != 0) *err = g_err;
+            return rc;
+        }).share();
+    {
+        std::lock_guard<std::mutex> lk(g_pend_mu);
+        g_pend.push_back({p, fut, err});
+    }
+    if (keep) {
+        nb->pending = fut;
+        *keep = nb.release();
+    }
+    return 0;
+}
+
 int finish_stream(const char* path, const ccio_bam* hdr, Bytes&& all, const std::vector<uint64_t>& at, int level,
                   int T, int flags, ccio_bam** keep) {
     if ((flags & CCIO_W_MEMORY) && !keep) { set_err("CCIO_W_MEMORY needs a kept handle"); return -1; }
@@ -2010,17 +2205,25 @@ uint8_t* asm_alloc(void* actx, uint64_t total) {
 // ccio_write_bam_ex's records through the hook: true with the stream in `all` and its offsets in `at`
 // when a hook is set, every source's records lie in place and in order in its own stream, the hook
 // returned 0 and its result passed the checks; anything else leaves the write to the host.
+// With ro (the resident set, ccio_set_out_resident) the stream stays with the set under ro->rs.token
+// and `all` holds it only when ro->have_host; the record checks then come from the set's fields.  A
+// false return has released the token.
 bool hook_assemble(const ccio_bam* tmpl, ccio_interner* it, int64_t n, const cc_out_spec* spec, ccio_bam* const* srcs,
                    int nsrc, const char* names, const int64_t* name_off, const uint8_t* cons_seq, const uint8_t* cons_qual,
-                   int flags, int T, Bytes& all, std::vector<uint64_t>& at) {
+                   int flags, int T, Bytes& all, std::vector<uint64_t>& at, ResOut* ro = nullptr) {
     ccio_assemble_fn fn;
     void* user;
     {
         std::lock_guard<std::mutex> lk(g_hook_mu);
         fn = g_asm_fn;
         user = g_asm_user;
+        if (ro) {
+            if (!g_outres_on) return false;
+            ro->rs.cb = g_outres_cb;
+            ro->rs.user = g_outres_user;
+        }
     }
-    if (!fn) return false;
+    if (!fn && !ro) return false;
     std::vector<cc_asm_src> ss((size_t)nsrc);
     std::vector<std::vector<uint64_t>> offs((size_t)nsrc);
     for (int f = 0; f < nsrc; ++f) {
@@ -2084,6 +2287,73 @@ bool hook_assemble(const ccio_bam* tmpl, ccio_interner* it, int64_t n, const cc_
     }
     at.assign((size_t)n + 1, 0);
     uint64_t total = 0;
+    if (ro) {
+        const std::vector<uint8_t>& hdr = tmpl->header_raw;
+        ResSrc& rs = ro->rs;
+        auto fail = [&]() {
+            if (rs.token) rs.cb.release(rs.user, rs.token);
+            rs.token = 0;
+            return false;
+        };
+        const int rc = rs.cb.assemble_keep(rs.user, hdr.data(), (uint64_t)hdr.size(), ss.data(), nsrc, spec, n, names, name_off,
+                                           n_names, (uint64_t)name_end, cons_seq, own_cons ? 0 : (uint64_t)cs, cons_qual,
+                                           own_cons ? 0 : (uint64_t)cq, rg_blob.data(), rg_off.data(), (int32_t)rgs.size(),
+                                           flags & CCIO_W_SORT, asm_alloc, &all, ro->need_host ? 1 : 0, at.data(), &total,
+                                           &rs.token);
+        if (rc != 0 || rs.token == 0) return fail();
+        ro->total = total;
+        ro->have_host = ro->need_host;
+        if (at[0] != hdr.size() || at[(size_t)n] != total || total < hdr.size()) return fail();
+        {   // strictly increasing offsets
+            std::atomic<bool> bad(false);
+            parallel_chunks(n, T, 65536, [&](int64_t s0, int64_t e0) {
+                for (int64_t i = s0; i < e0; ++i)
+                    if (at[(size_t)i + 1] <= at[(size_t)i]) { bad = true; return; }
+            });
+            if (bad) return fail();
+        }
+        {   // the header where the stream lies
+            std::vector<uint8_t> got(hdr.size());
+            if (!hdr.empty() && (rs.cb.fetch(rs.user, rs.token, 0, (uint64_t)hdr.size(), got.data()) != 0 || got != hdr)) return fail();
+        }
+        if (n > 0 && rs.cb.index_fields) {
+            ro->fields.assign((size_t)n, cc_index_field{0, 0, 0, 0});
+            if (rs.cb.index_fields(rs.user, rs.token, at.data(), n, ro->fields.data()) == 0) {
+                std::atomic<bool> bad(false);
+                parallel_chunks(n, T, 65536, [&](int64_t s0, int64_t e0) {
+                    for (int64_t i = s0; i < e0; ++i)
+                        if ((uint64_t)ro->fields[(size_t)i].block_size + 4 != at[(size_t)i + 1] - at[(size_t)i]) { bad = true; return; }
+                });
+                if (bad) return fail();
+                ro->have_fields = true;
+            } else {
+                ro->fields.clear();
+            }
+        } else if (n == 0) {
+            ro->have_fields = true;
+        }
+        if (!ro->have_fields && !ro->have_host) {   // no fields to check the records by: the stream itself
+            try {
+                all.resize((size_t)total);
+            } catch (...) {
+                return fail();
+            }
+            if (rs.cb.fetch(rs.user, rs.token, 0, total, all.data()) != 0) return fail();
+            ro->have_host = true;
+        }
+        if (ro->have_host) {   // today's checks as well
+            if (total != all.size() || memcmp(all.data(), hdr.data(), hdr.size()) != 0) return fail();
+            std::atomic<bool> bad(false);
+            parallel_chunks(n, T, 65536, [&](int64_t s0, int64_t e0) {
+                for (int64_t i = s0; i < e0; ++i) {
+                    const uint64_t a = at[(size_t)i], e = at[(size_t)i + 1];
+                    if (e > total || e - a < 4 || (uint64_t)(uint32_t)rd32(all.data() + a) + 4 != e - a) { bad = true; return; }
+                }
+            });
+            if (bad) return fail();
+        }
+        return true;
+    }
     const int rc = fn(user, tmpl->header_raw.data(), (uint64_t)tmpl->header_raw.size(), ss.data(), nsrc, spec, n, names,
                       name_off, n_names, (uint64_t)name_end, cons_seq, own_cons ? 0 : (uint64_t)cs, cons_qual,
                       own_cons ? 0 : (uint64_t)cq, rg_blob.data(), rg_off.data(), (int32_t)rgs.size(), flags & CCIO_W_SORT,
@@ -2128,7 +2398,18 @@ int ccio_write_bam_ex(const char* path, ccio_bam* tmpl, ccio_interner* it, int64
     for (int64_t i = 0; i < n; ++i)
         if (spec[i].src_file < 0 || spec[i].src_file >= nsrc) { set_err("bad output spec"); return -1; }
     {
-        // the assemble hook first (ccio_set_assemble_hook); whatever it refuses is assembled below
+        // the resident set first (ccio_set_out_resident): the stream stays where it was built
+        Bytes rall;
+        std::vector<uint64_t> rat;
+        ResOut ro;
+        ro.need_host = keep != nullptr || (flags & CCIO_W_MEMORY) != 0;
+        if (hook_assemble(tmpl, it, n, spec, srcs, nsrc, names, name_off, cons_seq, cons_qual, flags, T, rall, rat, &ro)) {
+            pt.lap("write: resident assemble");
+            return finish_resident(path, tmpl, std::move(rall), std::move(rat), std::move(ro), level, T, flags, keep);
+        }
+    }
+    {
+        // the assemble hook next (ccio_set_assemble_hook); whatever it refuses is assembled below
         Bytes hall;
         std::vector<uint64_t> hat;
         if (hook_assemble(tmpl, it, n, spec, srcs, nsrc, names, name_off, cons_seq, cons_qual, flags, T, hall, hat)) {
@@ -2352,42 +2633,30 @@ namespace {
 // The BAI of one coordinate-sorted BAM stream held in memory (data: the whole uncompressed
 // stream from the magic on; bco / buo: per non-empty BGZF member its compressed offset and
 // uncompressed start, then the EOF member's offset and the stream's length), written to path.bai.
-int index_stream(const uint8_t* dp, size_t dn, const std::vector<uint64_t>& bco, const std::vector<uint64_t>& buo,
-                 const char* path) {
-    struct Span {
-        const uint8_t* p; size_t n;
-        size_t size() const { return n; }
-        const uint8_t* data() const { return p; }
-        const uint8_t& operator[](size_t i) const { return p[i]; }
-    } data{dp, dn};
-    // the records come in stream order: the member holding an offset is found by walking forward
-    // from the previous one (amortised O(1), not a search per record)
+// the member holding an uncompressed offset, found by walking forward from the previous one (the
+// records come in stream order: amortised O(1), not a search per record)
+struct VOff {
+    const std::vector<uint64_t>& bco;
+    const std::vector<uint64_t>& buo;
     size_t vcur = 0;
-    auto voff = [&](uint64_t u) {
+    uint64_t operator()(uint64_t u) {
         if (u < buo[vcur]) vcur = std::upper_bound(buo.begin(), buo.end(), u) - buo.begin() - 1;
         while (vcur + 1 < buo.size() && buo[vcur + 1] <= u) ++vcur;
         return (bco[vcur] << 16) | (u - buo[vcur]);
-    };
-    if (data.size() < 12 || memcmp(data.data(), "BAM\1", 4) != 0) { set_err("index: not a BAM file"); return -1; }
-    size_t off = 4;
-    const int32_t ltext = rd32(&data[off]);
-    if (ltext < 0 || off + 8 + (size_t)ltext > data.size()) { set_err("index: truncated header"); return -1; }
-    off += 4 + ltext;
-    const int32_t nref = rd32(&data[off]);
-    off += 4;
-    if (nref < 0) { set_err("index: bad reference count"); return -1; }
-    for (int32_t i = 0; i < nref; ++i) {
-        if (off + 4 > data.size()) { set_err("index: truncated header"); return -1; }
-        const int32_t ln = rd32(&data[off]);
-        if (ln < 0 || off + 8 + (size_t)ln > data.size()) { set_err("index: truncated header"); return -1; }
-        off += 4 + ln + 4;
     }
+};
+
+// The BAI's accumulator: one add() per record in stream order, whoever read the record (the walk over
+// the stream below, or the fields a device kernel read: index_fields).  It owns the sortedness check,
+// the bins and their chunks, the linear index, the pseudo-bin, the no-coordinate count and the writing.
+struct BaiBuilder {
     struct Ref {
         std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
         std::vector<uint64_t> lin;
         uint64_t beg = ~0ULL, end = 0, mapped = 0, unmapped = 0;
     };
-    std::vector<Ref> refs(nref);
+    int32_t nref;
+    std::vector<Ref> refs;
     uint64_t no_coor = 0;
     // the last bin touched (sorted records mostly land in the bin of the record before them)
     int32_t cache_tid = -1;
@@ -2395,33 +2664,21 @@ int index_stream(const uint8_t* dp, size_t dn, const std::vector<uint64_t>& bco,
     std::vector<std::pair<uint64_t, uint64_t>>* cache_ch = nullptr;
     int32_t last_tid = -2;
     int64_t last_pos = -1;
-    while (off + 4 <= data.size()) {
-        const int32_t bs = rd32(&data[off]);
-        if (bs < 32 || off + 4 + (size_t)bs > data.size()) { set_err("index: truncated BAM record"); return -1; }
-        const uint8_t* r = &data[off + 4];
-        const int32_t tid = rd32(r), pos = rd32(r + 4);
-        const uint16_t ncig = rdu16(r + 12), flag = rdu16(r + 14);
-        if (32 + (size_t)r[8] + 4 * (size_t)ncig > (size_t)bs) { set_err("index: record cigar past its end"); return -1; }
-        const uint64_t vb = voff(off), ve = voff(off + 4 + bs);
+    explicit BaiBuilder(int32_t n) : nref(n), refs((size_t)n) {}
+
+    // rl: the reference length (0 for an unmapped record); vbeg / vend: the record's virtual offsets
+    bool add(int32_t tid, int32_t pos, uint32_t rl, bool unmapped, uint64_t vb, uint64_t ve) {
         if ((tid >= 0 && tid < last_tid) || (tid == last_tid && pos < last_pos) || (tid >= 0 && last_tid == -1)) {
             set_err("index: BAM not coordinate-sorted");
-            return -1;
+            return false;
         }
         last_tid = tid;
         last_pos = pos;
-        off += 4 + bs;
-        if (tid < 0 || tid >= nref) { ++no_coor; continue; }
-        int64_t rl = 0;
-        if (!(flag & 4)) {
-            const uint8_t* cg = r + 32 + r[8];
-            for (int c = 0; c < ncig; ++c) {
-                const uint32_t v = rdu32(cg + 4 * c), op = v & 0xf;
-                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += v >> 4;
-            }
-        }
-        const int64_t beg = pos < 0 ? 0 : pos, end = beg + (rl ? rl : 1);
+        if (tid < 0 || tid >= nref) { ++no_coor; return true; }
+        int64_t beg, end;
+        idx::interval(pos, rl, &beg, &end);
         Ref& R = refs[tid];
-        const uint32_t bin = (uint32_t)reg2bin(beg, end);
+        const uint32_t bin = (uint32_t)idx::reg2bin(beg, end);
         if (!cache_ch || cache_tid != tid || cache_bin != bin) {
             cache_ch = &R.bins[bin];   // std::map: the pointer stays valid as bins are added
             cache_tid = tid;
@@ -2436,40 +2693,106 @@ int index_stream(const uint8_t* dp, size_t dn, const std::vector<uint64_t>& bco,
             if (!R.lin[w]) R.lin[w] = vb;
         R.beg = std::min(R.beg, vb);
         R.end = std::max(R.end, ve);
-        if (flag & 4) ++R.unmapped;
+        if (unmapped) ++R.unmapped;
         else ++R.mapped;
+        return true;
     }
-    std::string out("BAI\1", 4);
-    wr32(out, nref);
-    auto w64 = [&](uint64_t v) { out.append((const char*)&v, 8); };
-    for (Ref& R : refs) {
-        const bool any = R.mapped + R.unmapped > 0;
-        wr32(out, (int32_t)R.bins.size() + (any ? 1 : 0));
-        for (auto& b : R.bins) {
-            wr32(out, (int32_t)b.first);
-            wr32(out, (int32_t)b.second.size());
-            for (auto& c : b.second) { w64(c.first); w64(c.second); }
+
+    int write(const char* path) {
+        std::string out("BAI\1", 4);
+        wr32(out, nref);
+        auto w64 = [&](uint64_t v) { out.append((const char*)&v, 8); };
+        for (Ref& R : refs) {
+            const bool any = R.mapped + R.unmapped > 0;
+            wr32(out, (int32_t)R.bins.size() + (any ? 1 : 0));
+            for (auto& b : R.bins) {
+                wr32(out, (int32_t)b.first);
+                wr32(out, (int32_t)b.second.size());
+                for (auto& c : b.second) { w64(c.first); w64(c.second); }
+            }
+            if (any) {   // htslib's metadata pseudo-bin
+                wr32(out, 37450);
+                wr32(out, 2);
+                w64(R.beg); w64(R.end); w64(R.mapped); w64(R.unmapped);
+            }
+            for (size_t w = 1; w < R.lin.size(); ++w)
+                if (!R.lin[w]) R.lin[w] = R.lin[w - 1];
+            wr32(out, (int32_t)R.lin.size());
+            for (uint64_t v : R.lin) w64(v);
         }
-        if (any) {   // htslib's metadata pseudo-bin
-            wr32(out, 37450);
-            wr32(out, 2);
-            w64(R.beg); w64(R.end); w64(R.mapped); w64(R.unmapped);
+        w64(no_coor);
+        const std::string ipath = std::string(path) + ".bai";
+        FILE* g = fopen(ipath.c_str(), "wb");
+        if (!g || fwrite(out.data(), 1, out.size(), g) != out.size()) {
+            if (g) fclose(g);
+            set_err("cannot write " + ipath);
+            return -1;
         }
-        for (size_t w = 1; w < R.lin.size(); ++w)
-            if (!R.lin[w]) R.lin[w] = R.lin[w - 1];
-        wr32(out, (int32_t)R.lin.size());
-        for (uint64_t v : R.lin) w64(v);
+        fclose(g);
+        return 0;
     }
-    w64(no_coor);
-    const std::string ipath = std::string(path) + ".bai";
-    FILE* g = fopen(ipath.c_str(), "wb");
-    if (!g || fwrite(out.data(), 1, out.size(), g) != out.size()) {
-        if (g) fclose(g);
-        set_err("cannot write " + ipath);
-        return -1;
+};
+
+// the encoded header at the head of a stream: its reference count and where the records start
+int bam_header_extent(const uint8_t* dp, size_t dn, int32_t* nref_out, size_t* rec0) {
+    if (dn < 12 || memcmp(dp, "BAM\1", 4) != 0) { set_err("index: not a BAM file"); return -1; }
+    size_t off = 4;
+    const int32_t ltext = rd32(dp + off);
+    if (ltext < 0 || off + 8 + (size_t)ltext > dn) { set_err("index: truncated header"); return -1; }
+    off += 4 + ltext;
+    const int32_t nref = rd32(dp + off);
+    off += 4;
+    if (nref < 0) { set_err("index: bad reference count"); return -1; }
+    for (int32_t i = 0; i < nref; ++i) {
+        if (off + 4 > dn) { set_err("index: truncated header"); return -1; }
+        const int32_t ln = rd32(dp + off);
+        if (ln < 0 || off + 8 + (size_t)ln > dn) { set_err("index: truncated header"); return -1; }
+        off += 4 + ln + 4;
     }
-    fclose(g);
+    *nref_out = nref;
+    *rec0 = off;
     return 0;
+}
+
+// The record walker: every record of the stream read by index_core.h's field() and fed to the builder.
+int index_stream(const uint8_t* dp, size_t dn, const std::vector<uint64_t>& bco, const std::vector<uint64_t>& buo,
+                 const char* path) {
+    VOff voff{bco, buo};
+    int32_t nref = 0;
+    size_t off = 0;
+    if (bam_header_extent(dp, dn, &nref, &off) != 0) return -1;
+    BaiBuilder B(nref);
+    const idx::HostSrc src{dp};
+    while (off + 4 <= dn) {
+        const int32_t bs = rd32(dp + off);
+        if (bs < 32 || off + 4 + (size_t)bs > dn) { set_err("index: truncated BAM record"); return -1; }
+        idx::Field f;
+        if (idx::field(src, (uint64_t)off, (uint64_t)off + 4 + (uint64_t)bs, (uint64_t)dn, f) != 0) {
+            set_err("index: record cigar past its end");
+            return -1;
+        }
+        const uint64_t vb = voff(off), ve = voff(off + 4 + bs);
+        if (!B.add(f.tid, f.pos, f.rl & idx::RL_MAX, (f.rl & idx::UNMAPPED) != 0, vb, ve)) return -1;
+        off += 4 + bs;
+    }
+    return B.write(path);
+}
+
+// The fields-driven loop: the same index from what a kernel read of each record (hdr: the stream's
+// encoded header, at[n + 1]: the records' offsets in the stream).
+int index_fields(const std::vector<uint8_t>& hdr, const std::vector<uint64_t>& at, const std::vector<cc_index_field>& fields,
+                 const std::vector<uint64_t>& bco, const std::vector<uint64_t>& buo, const char* path) {
+    VOff voff{bco, buo};
+    int32_t nref = 0;
+    size_t off = 0;
+    if (bam_header_extent(hdr.data(), hdr.size(), &nref, &off) != 0) return -1;
+    BaiBuilder B(nref);
+    for (size_t i = 0; i + 1 < at.size(); ++i) {
+        const cc_index_field& f = fields[i];
+        const uint64_t vb = voff(at[i]), ve = voff(at[i + 1]);
+        if (!B.add(f.tid, f.pos, f.rl & idx::RL_MAX, (f.rl & idx::UNMAPPED) != 0, vb, ve)) return -1;
+    }
+    return B.write(path);
 }
 
 }  // namespace

@@ -345,6 +345,7 @@ _BGZF_OWNER = None   # the engine whose encoder libccio's (process-wide) deflate
 _INFLATE_OWNER = None   # likewise for the inflate hook
 _KEEP_OWNER = None   # and for the inflate hook that keeps resident streams
 _ASSEMBLE_OWNER = None   # and for the assemble hook
+_OUT_RESIDENT_OWNER = None   # and for the resident output set
 
 
 class Engine(object):
@@ -366,6 +367,8 @@ class Engine(object):
         self._keep_wired = False
         self.crc_device = False
         self.assemble_device = False
+        self.out_resident_device = False   # the resident output set is wired (device_out_resident)
+        self._out_resident_want = os.environ.get("CC_OUT_RESIDENT_DEVICE") == "1"
         self.names_device = os.environ.get("CC_NAMES_DEVICE") == "1"
         if os.environ.get("CC_CRC_DEVICE") == "1":   # before the hooks below are wired: they take the crc variants
             self.device_crc(True)
@@ -381,6 +384,7 @@ class Engine(object):
             self.device_decode(True)
         if os.environ.get("CC_ASSEMBLE_DEVICE") == "1":
             self.device_assemble(True)
+        self._sync_out_resident()
 
     def device_decode(self, on):
         """Switches table() between the host decoder (Bam.decode + upload, the default) and the device
@@ -523,16 +527,19 @@ class Engine(object):
             if prev is not None and prev is not self:
                 rc = io.ccio_flush()   # no writer thread is inside the previous owner's encoder
                 prev.bgzf_device = False
+                prev._sync_out_resident()
                 if rc != 0:
                     raise IOError(N.io_error())
             io.ccio_set_deflate_hook(fn, user)
             _BGZF_OWNER = self
             self.bgzf_device = True
+            self._sync_out_resident()
             return was
         rc = io.ccio_flush()   # no writer thread is inside the hook after this
         io.ccio_set_deflate_hook(None, None)
         _BGZF_OWNER = None
         self.bgzf_device = False
+        self._sync_out_resident()
         if rc != 0:
             raise IOError(N.io_error())
         return was
@@ -558,14 +565,116 @@ class Engine(object):
             prev = _ASSEMBLE_OWNER
             if prev is not None and prev is not self:
                 prev.assemble_device = False
+                prev._sync_out_resident()
             io.ccio_set_assemble_hook(fn, user)
             _ASSEMBLE_OWNER = self
             self.assemble_device = True
+            self._sync_out_resident()
             return was
         io.ccio_set_assemble_hook(None, None)
         _ASSEMBLE_OWNER = None
         self.assemble_device = False
+        self._sync_out_resident()
         return was
+
+    def device_out_resident(self, on):
+        """Asks for (or gives up) the resident output path (cc_out_resident_hooks -> ccio_set_out_resident):
+        write_bam's assembled stream stays on the device, the encoder reads its pieces there
+        (cc_bgzf_deflate_resident) and the .bai comes from k_index_fields, so a file nobody keeps in
+        memory never crosses PCIe uncompressed.  The files are byte for byte those of assemble_device
+        with bgzf_device.  Effective only while assemble_device and bgzf_device are both on: otherwise
+        nothing is wired and nothing raises, and the set is wired once both are (out_resident_device
+        says whether it is).  One set per process, with device_bgzf's ownership rules.  Wiring and
+        unwiring wait for the background writes first.  Returns the previous request."""
+        was = self._out_resident_want
+        self._out_resident_want = bool(on)
+        self._sync_out_resident()
+        return was
+
+    def _sync_out_resident(self):
+        global _OUT_RESIDENT_OWNER
+        want = bool(self._out_resident_want and self.assemble_device and self.bgzf_device and self.h)
+        if want == self.out_resident_device:
+            return
+        io = N.io()
+        rc = io.ccio_flush()   # no writer thread is inside the set (or the previous owner's) after this
+        if want:
+            cb, user = N.ccio_out_resident(), N.P()
+            self._check(self.lib.cc_out_resident_hooks(self.h, C.byref(cb), C.byref(user)))
+            prev = _OUT_RESIDENT_OWNER
+            if prev is not None and prev is not self:
+                prev.out_resident_device = False
+            io.ccio_set_out_resident(C.byref(cb), user)
+            _OUT_RESIDENT_OWNER = self
+            self.out_resident_device = True
+        else:
+            if _OUT_RESIDENT_OWNER is self:
+                io.ccio_set_out_resident(None, None)
+                _OUT_RESIDENT_OWNER = None
+            self.out_resident_device = False
+        if rc != 0:
+            raise IOError(N.io_error())
+
+    def resident_put(self, data):
+        """cc_resident_put: data (bytes-like or a uint8 array) uploaded as a resident stream; its id."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        rid = C.c_int64(0)
+        self._check(self.lib.cc_resident_put(self.h, N.ptr(buf) if buf.size else None, buf.size, C.byref(rid)))
+        return int(rid.value)
+
+    def resident_free(self, rid):
+        self._check(self.lib.cc_resident_free(self.h, int(rid)))
+
+    def resident_count(self):
+        return int(self.lib.cc_resident_count(self.h))
+
+    def resident_fetch(self, rid):
+        """A resident stream's bytes (cc_resident_fetch)."""
+        total = int(self.lib.cc_resident_fetch(self.h, int(rid), None, 0))
+        if total < 0:
+            self._check(total)
+        out = np.zeros(max(total, 1), np.uint8)
+        got = int(self.lib.cc_resident_fetch(self.h, int(rid), N.ptr(out), total))
+        if got < 0:
+            self._check(got)
+        return out[:total].tobytes()
+
+    def bgzf_deflate_resident(self, token, off, n, effort=None):
+        """cc_bgzf_deflate_resident: the framed BGZF members of bytes [off, off + n) of resident stream
+        `token`, as bgzf_deflate returns them."""
+        if effort is not None:
+            was = self._set_bgzf_effort(effort)
+            try:
+                return self.bgzf_deflate_resident(token, off, n)
+            finally:
+                self._set_bgzf_effort(was)
+        pieces = (int(n) + 0xff00 - 1) // 0xff00
+        slot = 0x10000
+        stage = np.zeros(max(pieces, 1) * slot, np.uint8)
+        lens = np.zeros(max(pieces, 1), np.uint32)
+        got = int(self.lib.cc_bgzf_deflate_resident(self.h, int(token), int(off), int(n), N.ptr(stage), slot,
+                                                    N.ptr(lens), pieces))
+        if got < 0:
+            raise N.CCError(got, self.lib.cc_last_error(self.h).decode(errors="replace"))
+        return [stage[j * slot:j * slot + int(lens[j])].tobytes() for j in range(got)]
+
+    def index_fields(self, token, at):
+        """cc_index_fields: one N.INDEX_FIELD_DTYPE row per record of resident stream `token`, record i
+        at byte at[i] (len(at) - 1 records)."""
+        at = np.ascontiguousarray(at, np.uint64)
+        n = len(at) - 1
+        out = np.zeros(max(n, 1), N.INDEX_FIELD_DTYPE)
+        self._check(self.lib.cc_index_fields(self.h, int(token), N.ptr(at), n, N.ptr(out)))
+        return out[:n]
+
+    def pin_source(self, bam):
+        """A context manager: bam's stream (a handle whose records lie in place) uploaded once as a
+        resident stream and named to the assemble hooks (ccio_bam_set_resident), so that every write
+        from it inside the block reads that copy instead of uploading the stream again.  On exit the
+        background writes are waited for, the name is cleared and the stream freed.  A handle that
+        already names a resident copy, or whose records do not lie in place, is left as it is."""
+        return _PinnedSource(self, bam)
 
     def device_names(self, on):
         """Switches the stages' consensus read names between libccio's formatters (csn_names / dcs_names,
@@ -620,12 +729,14 @@ class Engine(object):
         return self._names_blob(n, off, total.value)
 
     def assemble(self, header, sources, specs, names=None, name_off=None, cons_seq=None, cons_qual=None, group=None,
-                 rg_values=(), sort=False):
+                 rg_values=(), sort=False, keep=False):
         """cc_bam_assemble: the output stream (header bytes, then the records of `specs`) and its
         n + 1 record offsets, as (bytes, uint64 array).  sources: per source (stream, rec_off) with the
         records' bytes and offsets in host memory, or (None, rec_off, resident id, base, nbytes) for a
         resident stream.  The consensus arrays are cons_seq / cons_qual, or group's device buffers.
-        rg_values: the RG table's values (bytes), by rg_id.  sort: samtools-sort order."""
+        rg_values: the RG table's values (bytes), by rg_id.  sort: samtools-sort order.  keep=True is
+        cc_bam_assemble_keep without a download: (at, token), the stream left on the device as resident
+        stream `token` (resident_fetch, bgzf_deflate_resident, index_fields; resident_free when done)."""
         header = np.frombuffer(bytes(header), np.uint8)
         specs = np.ascontiguousarray(specs, N.OUT_SPEC_DTYPE)
         n = len(specs)
@@ -658,6 +769,16 @@ class Engine(object):
                 -1 if group is None else int(group), N.ptr(rg_blob), N.ptr(rg_off), len(rg), N.W_SORT if sort else 0,
                 out, cap, at, total)
         total = C.c_uint64()
+        if keep:
+            at = np.zeros(n + 1, np.uint64)
+            rid = C.c_int64(0)
+            self._check(self.lib.cc_bam_assemble_keep(
+                self.h, N.ptr(header) if len(header) else None, len(header), arr, len(sources), N.ptr(specs), n,
+                N.ptr(names) if len(names) else None, N.ptr(name_off), len(name_off) - 1, len(names),
+                N.ptr(cs) if len(cs) else None, len(cs), N.ptr(cq) if len(cq) else None, len(cq),
+                -1 if group is None else int(group), N.ptr(rg_blob), N.ptr(rg_off), len(rg), N.W_SORT if sort else 0,
+                None, 0, N.ptr(at), C.byref(total), C.byref(rid)))
+            return at, int(rid.value)
         self._check(call(None, 0, None, C.byref(total)))
         out = np.zeros(max(int(total.value), 1), np.uint8)
         at = np.zeros(n + 1, np.uint64)
@@ -798,7 +919,7 @@ class Engine(object):
                 self.device_resident(False)   # the hooks must not outlive the context; the resident streams
                 self.device_inflate(False)    # that are left go with it (cc_destroy)
                 self.device_bgzf(False)
-                self.device_assemble(False)
+                self.device_assemble(False)   # (the resident output set goes with either of the two)
             finally:
                 self.lib.cc_destroy(self.h)
                 self.h = None
@@ -1204,6 +1325,39 @@ def write_bam(path, template, interner, specs, srcs, names=None, name_off=None, 
         cons_seq = eng.fetch(g, "cons_seq", np.uint8)
         cons_qual = eng.fetch(g, "cons_qual", np.uint8)
     return _write_bam(path, template, interner, specs, srcs, names, name_off, cons_seq, cons_qual, level, nthreads, sink)
+
+
+class _PinnedSource(object):
+    """Engine.pin_source's context manager."""
+
+    def __init__(self, eng, bam):
+        self.eng, self.bam, self.rid = eng, bam, 0
+
+    def __enter__(self):
+        io = N.io()
+        tok, base = C.c_int64(0), C.c_uint64(0)
+        if io.ccio_bam_resident(self.bam.h, C.byref(tok), C.byref(base)):
+            return self   # it names a copy already (the inflater's)
+        data, nbytes, rec0 = N.P(), C.c_uint64(0), C.c_uint64(0)
+        if io.ccio_bam_stream(self.bam.h, C.byref(data), C.byref(nbytes), C.byref(rec0)) != 0:
+            return self   # a view: its writes never reach the hooks
+        rid = C.c_int64(0)
+        self.eng._check(self.eng.lib.cc_resident_put(self.eng.h, data, nbytes.value, C.byref(rid)))
+        if io.ccio_bam_set_resident(self.bam.h, rid.value, rec0.value) != 0:
+            self.eng.resident_free(rid.value)
+            return self
+        self.rid = int(rid.value)
+        return self
+
+    def __exit__(self, *exc):
+        if self.rid:
+            rc = N.io().ccio_flush()   # no background write still reads the copy
+            N.io().ccio_bam_set_resident(self.bam.h, 0, 0)
+            self.eng.resident_free(self.rid)
+            self.rid = 0
+            if rc != 0 and exc[0] is None:
+                raise IOError(N.io_error())
+        return False
 
 
 class _NeedCons(Exception):

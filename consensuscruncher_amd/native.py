@@ -108,6 +108,35 @@ ASSEMBLE_FN = C.CFUNCTYPE(C.c_int, P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_
                           C.c_uint64, P, C.c_uint64, P, C.c_uint64, P, P, C.c_int32, C.c_int, ASM_ALLOC_FN, P,
                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 
+
+
+class cc_index_field(C.Structure):
+    _fields_ = [("tid", C.c_int32), ("pos", C.c_int32), ("block_size", C.c_uint32), ("rl", C.c_uint32)]
+
+
+INDEX_FIELD_DTYPE = np.dtype([("tid", "<i4"), ("pos", "<i4"), ("block_size", "<u4"), ("rl", "<u4")])
+assert INDEX_FIELD_DTYPE.itemsize == C.sizeof(cc_index_field) == 16
+
+# the resident output set (ccio_set_out_resident).  ccio_assemble_keep_fn: ccio_assemble_fn's arguments up to
+# actx, then need_host, at, total, token
+ASSEMBLE_KEEP_FN = C.CFUNCTYPE(C.c_int, P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, P, C.c_int64, P, P,
+                               C.c_int64, C.c_uint64, P, C.c_uint64, P, C.c_uint64, P, P, C.c_int32, C.c_int,
+                               ASM_ALLOC_FN, P, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                               C.POINTER(C.c_int64))
+# ccio_deflate_resident_fn: user, token, off, n, stage, slot, out_len, pieces
+DEFLATE_RESIDENT_FN = C.CFUNCTYPE(C.c_int, P, C.c_int64, C.c_uint64, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint32),
+                                  C.c_int64)
+# ccio_index_fields_fn: user, token, at, n, fields
+INDEX_FIELDS_FN = C.CFUNCTYPE(C.c_int, P, C.c_int64, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(cc_index_field))
+# ccio_resident_fetch_fn: user, token, off, n, dst; ccio_resident_release_fn: user, token
+RESIDENT_FETCH_FN = C.CFUNCTYPE(C.c_int, P, C.c_int64, C.c_uint64, C.c_uint64, P)
+RESIDENT_RELEASE_FN = C.CFUNCTYPE(None, P, C.c_int64)
+
+
+class ccio_out_resident(C.Structure):
+    _fields_ = [("assemble_keep", P), ("deflate", P), ("index_fields", P), ("fetch", P), ("release", P)]
+
+
 _io = None
 _amd = None
 
@@ -121,6 +150,9 @@ IO_SIGS = {
     "ccio_set_inflate_crc_hook": (None, [P, P]),
     "ccio_set_inflate_keep_crc_hook": (None, [P, P, P]),
     "ccio_bam_resident": (C.c_int, [P, i64p, C.POINTER(C.c_uint64)]),
+    "ccio_set_out_resident": (None, [C.POINTER(ccio_out_resident), P]),
+    "ccio_bam_set_resident": (C.c_int, [P, C.c_int64, C.c_uint64]),
+    "ccio_bam_stream": (C.c_int, [P, C.POINTER(P), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ccio_value_census": (C.c_int, [P, C.c_int64, C.c_int32, P, P]),
     "ccio_interner_new": (P, []),
     "ccio_interner_free": (None, [P]),
@@ -218,6 +250,13 @@ AMD_SIGS = {
                                   C.c_uint64, P, C.c_uint64, P, C.c_uint64, C.c_int32, P, P, C.c_int32, C.c_int, P,
                                   C.c_uint64, P, C.POINTER(C.c_uint64)]),
     "cc_bam_assemble_hook": (C.c_int, [P, C.POINTER(P), C.POINTER(P)]),
+    "cc_bam_assemble_keep": (C.c_int, [P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, P, C.c_int64, P, P,
+                                       C.c_int64, C.c_uint64, P, C.c_uint64, P, C.c_uint64, C.c_int32, P, P, C.c_int32,
+                                       C.c_int, P, C.c_uint64, P, C.POINTER(C.c_uint64), i64p]),
+    "cc_out_resident_hooks": (C.c_int, [P, C.POINTER(ccio_out_resident), C.POINTER(P)]),
+    "cc_bgzf_deflate_resident": (C.c_int64, [P, C.c_int64, C.c_uint64, C.c_uint64, P, C.c_uint64, P, C.c_int64]),
+    "cc_index_fields": (C.c_int, [P, C.c_int64, P, C.c_int64, P]),
+    "cc_resident_put": (C.c_int, [P, P, C.c_uint64, i64p]),
     "cc_bam_assemble_group": (C.c_int, [P, C.c_int32]),
     "cc_format_csn_names": (C.c_int, [P, C.c_int64, P, P, P, P, C.c_int64, P, P, C.c_int64, P, i64p]),
     "cc_format_dcs_names": (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, i64p]),

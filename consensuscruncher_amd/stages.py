@@ -6,6 +6,7 @@ stats text, with the per-read work done by libccamd on the GPU and the
 BAM I/O by libccio.
 """
 import collections
+import contextlib
 import math
 import os
 import re
@@ -51,6 +52,11 @@ def _stream(bam, rec, bedfile):
 
 
 # ---------------------------------------------------------------- SSCS
+def _pinned(eng, bam):
+    """Engine.pin_source(bam) while the resident output path is wired, else nothing."""
+    return eng.pin_source(bam) if eng.out_resident_device else contextlib.nullcontext()
+
+
 class SSCSRun(object):
     """Device side of SSCS_maker.main (SSCS_maker.py:183-425): input decoded and
     resident in HBM, read_bam + consensus_maker run on the GPU.  step() re-runs
@@ -125,18 +131,19 @@ class SSCSRun(object):
         t0 = time.time()
         voted = emit_vslot >= 0
         # SSCS records (create_aligned_segment) and renamed singletons, in emission order
-        sp = _new_specs(voted, emit_rec[voted], np.nonzero(voted)[0], emit_vslot[voted], meta, qstride)
-        write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
-                  cons_group=cgroup)
-        ss = make_specs(int((~voted).sum()))
-        ss["kind"] = N.OUT_RENAME
-        ss["src_rec"] = emit_rec[~voted]
-        ss["name_id"] = np.nonzero(~voted)[0]
-        write_bam('{}.singleton.bam'.format(prefix), bam, it, ss, [bam], names, name_off, level=level, sink=sink)
-        bs = make_specs(len(bad_rec))
-        bs["kind"] = N.OUT_RAW
-        bs["src_rec"] = bad_rec
-        write_bam('{}.badReads.bam'.format(prefix), bam, it, bs, [bam], level=level, sink=sink)
+        with _pinned(eng, bam):   # (the source uploaded once for these writes)
+            sp = _new_specs(voted, emit_rec[voted], np.nonzero(voted)[0], emit_vslot[voted], meta, qstride)
+            write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
+                      cons_group=cgroup)
+            ss = make_specs(int((~voted).sum()))
+            ss["kind"] = N.OUT_RENAME
+            ss["src_rec"] = emit_rec[~voted]
+            ss["name_id"] = np.nonzero(~voted)[0]
+            write_bam('{}.singleton.bam'.format(prefix), bam, it, ss, [bam], names, name_off, level=level, sink=sink)
+            bs = make_specs(len(bad_rec))
+            bs["kind"] = N.OUT_RAW
+            bs["src_rec"] = bad_rec
+            write_bam('{}.badReads.bam'.format(prefix), bam, it, bs, [bam], level=level, sink=sink)
         self.times["emit_write"] = time.time() - t0
         t0 = time.time()
         items = size_census(fam_sizes)
@@ -348,14 +355,15 @@ class DCSRun(object):
             names, name_off = dcs_names(bam, t_rec[made], p_rec[made])
         self.times["emit_names"] = time.time() - t0
         t0 = time.time()
-        sp = _new_specs(nm, t_rec[made], np.arange(nm), vslot[made], meta, qstride)
-        write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
-                  cons_group=cgroup)
-        single = dec == 1
-        ss = make_specs(int(single.sum()))
-        ss["kind"] = N.OUT_RAW
-        ss["src_rec"] = t_rec[single]
-        write_bam(singleton_path, bam, it, ss, [bam], level=level, sink=sink)
+        with _pinned(eng, bam):   # (the source uploaded once for these writes)
+            sp = _new_specs(nm, t_rec[made], np.arange(nm), vslot[made], meta, qstride)
+            write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
+                      cons_group=cgroup)
+            single = dec == 1
+            ss = make_specs(int(single.sum()))
+            ss["kind"] = N.OUT_RAW
+            ss["src_rec"] = t_rec[single]
+            write_bam(singleton_path, bam, it, ss, [bam], level=level, sink=sink)
         self.times["emit_write"] = time.time() - t0
         t0 = time.time()
         part = dict(counters=c, dcs=nm, sscs_singletons=int(single.sum()))
@@ -483,20 +491,21 @@ class SCRun(object):
         cons_qual = None if cgroup else eng.fetch(gs, "cons_qual", np.uint8)
         qstride = (max(self.srec.max_len, self.xrec.max_len) + 15) & ~15
         outs = {}
-        for code, name in ((0, "sscs.correction"), (1, "singleton.correction")):
-            m = dec == code
-            k = int(m.sum())
-            fmt = eng.csn_names if eng.names_device else csn_names
-            names, name_off = fmt(it, q_ckey[m], np.ones(k, np.int64))
-            sp = _new_specs(k, t_rec[m], np.arange(k), vslot[m], meta, qstride)
-            write_bam('{}.{}.bam'.format(base, name), sbam, it, sp, [sbam], names, name_off, cons_seq, cons_qual,
-                      level, sink=sink, cons_group=cgroup)
-            outs[name] = k
-        m = dec == 2
-        us = make_specs(int(m.sum()))
-        us["kind"] = N.OUT_RAW
-        us["src_rec"] = t_rec[m]
-        write_bam('{}.uncorrected.bam'.format(base), sbam, it, us, [sbam], level=level, sink=sink)
+        with _pinned(eng, sbam):   # (the source uploaded once for these writes)
+            for code, name in ((0, "sscs.correction"), (1, "singleton.correction")):
+                m = dec == code
+                k = int(m.sum())
+                fmt = eng.csn_names if eng.names_device else csn_names
+                names, name_off = fmt(it, q_ckey[m], np.ones(k, np.int64))
+                sp = _new_specs(k, t_rec[m], np.arange(k), vslot[m], meta, qstride)
+                write_bam('{}.{}.bam'.format(base, name), sbam, it, sp, [sbam], names, name_off, cons_seq, cons_qual,
+                          level, sink=sink, cons_group=cgroup)
+                outs[name] = k
+            m = dec == 2
+            us = make_specs(int(m.sum()))
+            us["kind"] = N.OUT_RAW
+            us["src_rec"] = t_rec[m]
+            write_bam('{}.uncorrected.bam'.format(base), sbam, it, us, [sbam], level=level, sink=sink)
         part = dict(counters=c, processed=int((dec < 3).sum()), sscs_correction=outs["sscs.correction"],
                     singleton_correction=outs["singleton.correction"], uncorrected=int(m.sum()))
         if side:

@@ -304,6 +304,66 @@ typedef int (*ccio_assemble_fn)(void *user, const uint8_t *header, uint64_t head
                                 const char *rg_blob, const int64_t *rg_off, int32_t n_rg, int flags,
                                 cc_asm_alloc_fn alloc, void *actx, uint64_t *at, uint64_t *total);
 void ccio_set_assemble_hook(ccio_assemble_fn fn, void *user);
+/* What the BAI needs of one record (csrc/index_core.h): rl holds the reference length (the M / D / N /
+ * = / X op lengths summed, 0 for an unmapped record, saturating at 2^31 - 1) in bits 0..30 and the
+ * record's flag & 4 in bit 31. */
+typedef struct cc_index_field {
+    int32_t tid, pos;
+    uint32_t block_size;
+    uint32_t rl;
+} cc_index_field;
+/* The output stream kept where the assembler built it (the device: cc_out_resident_hooks below).
+ * With the set installed, ccio_write_bam_ex goes to it in place of the plain assemble hook, under
+ * the same condition on the sources:
+ *   assemble_keep   ccio_assemble_fn's contract, plus need_host and *token.  It leaves the stream in
+ *                   a place of its own named by *token (> 0) and always fills at[n + 1] and *total;
+ *                   it calls alloc and writes the stream to the host only when need_host is 1, which
+ *                   it is exactly when the caller asked for a kept handle or for CCIO_W_MEMORY.
+ *   deflate         ccio_deflate_fn with (token, off) in place of data: the members of the stream's
+ *                   bytes [off, off + n).  off is a multiple of 0xff00 * 1024 (the writers' round).
+ *   index_fields    fields[i] for the record at at[i], i < n; nonzero when any record is refused.
+ *   fetch           the stream's bytes [off, off + n) copied to dst.
+ *   release         the token is dead: called exactly once per token assemble_keep returned, by the
+ *                   thread that finished (or gave up) the file; for CCIO_W_ASYNC the writer thread.
+ * Without a host copy libccio fetches and compares the header's bytes, checks at[0], that at is
+ * strictly increasing and at[n] == total, and (from index_fields) every record's block_size + 4
+ * against at[i + 1] - at[i]; with a host copy the plain hook's checks run as well.  When
+ * assemble_keep returns nonzero or a check fails, the token (if any) is released and the write goes
+ * on to the plain assemble hook or the host assembler, exactly as without the set.  Every encoder
+ * round at level >= 1 goes to deflate first, with the plain deflate hook's checks on what it
+ * returns; a round it refuses is fetched and compressed by the host codec.  With CCIO_W_INDEX the
+ * .bai is built from the fields, byte for byte what the walk over the stream writes; when
+ * index_fields refuses, the stream is fetched and walked.  A file is never lost or left partial.
+ * A kept handle owns only its host copy.  The callbacks are called from the CCIO_W_ASYNC writer
+ * threads, several at once.  NULL cb unsets the set; unset it (after ccio_flush) before freeing
+ * what user points to. */
+typedef int (*ccio_assemble_keep_fn)(void *user, const uint8_t *header, uint64_t header_bytes, const cc_asm_src *srcs,
+                                     int32_t nsrc, const cc_out_spec *spec, int64_t n, const char *names,
+                                     const int64_t *name_off, int64_t n_names, uint64_t names_bytes,
+                                     const uint8_t *cons_seq, uint64_t cons_seq_bytes, const uint8_t *cons_qual,
+                                     uint64_t cons_qual_bytes, const char *rg_blob, const int64_t *rg_off, int32_t n_rg,
+                                     int flags, cc_asm_alloc_fn alloc, void *actx, int need_host, uint64_t *at,
+                                     uint64_t *total, int64_t *token);
+typedef int (*ccio_deflate_resident_fn)(void *user, int64_t token, uint64_t off, uint64_t n, uint8_t *stage,
+                                        uint64_t slot, uint32_t *out_len, int64_t pieces);
+typedef int (*ccio_index_fields_fn)(void *user, int64_t token, const uint64_t *at, int64_t n, cc_index_field *fields);
+typedef int (*ccio_resident_fetch_fn)(void *user, int64_t token, uint64_t off, uint64_t n, uint8_t *dst);
+typedef void (*ccio_resident_release_fn)(void *user, int64_t token);
+typedef struct ccio_out_resident {
+    ccio_assemble_keep_fn assemble_keep;
+    ccio_deflate_resident_fn deflate;
+    ccio_index_fields_fn index_fields;
+    ccio_resident_fetch_fn fetch;
+    ccio_resident_release_fn release;
+} ccio_out_resident;
+void ccio_set_out_resident(const ccio_out_resident *cb, void *user);
+/* b's records (which must lie in place in its own stream, ccio_bam_resident's condition) named as
+ * bytes [base, ...) of the resident copy `token`: ccio_bam_resident then answers with them and the
+ * assemble hooks read that copy (cc_resident_put uploads one).  Token 0 clears it.  -1 for a view. */
+int ccio_bam_set_resident(ccio_bam *b, int64_t token, uint64_t base);
+/* the stream of a handle whose records lie in place (what cc_resident_put uploads for it): its bytes
+ * and the offset of its first record in them (its size without records); -1 for a view */
+int ccio_bam_stream(ccio_bam *b, const uint8_t **data, uint64_t *bytes, uint64_t *rec_base);
 /* per value 0..maxv of v[0..n): count and first index (n when absent), one pass (read_families.txt) */
 int ccio_value_census(const int32_t *v, int64_t n, int32_t maxv, int64_t *first, int64_t *count);
 /* (cons_seq and cons_qual both NULL with CC_OUT_NEW specs: only an assemble hook that brings its own
@@ -494,6 +554,29 @@ int cc_resident_free(cc_ctx *ctx, int64_t id);
  * number of resident streams the context holds */
 int64_t cc_resident_fetch(cc_ctx *ctx, int64_t id, uint8_t *dst, uint64_t cap);
 int64_t cc_resident_count(cc_ctx *ctx);
+/* Host bytes uploaded as a new resident stream (*id > 0), with the streams' padding: a stage's source
+ * uploaded once for all of its writes (ccio_bam_set_resident names it to the assemble hooks).
+ * Without device memory for it CC_E_HIP and *id = 0; the coders stay usable. */
+int cc_resident_put(cc_ctx *ctx, const uint8_t *bytes, uint64_t n, int64_t *id);
+/* cc_bgzf_deflate over bytes [off, off + n) of resident stream id: k_bgzf_deflate reads its pieces
+ * where they lie (no pinned staging copy, no upload; with profiling on nothing is added to
+ * "bgzf_upload").  off must be a multiple of 256, the kernel's alignment assumption: anything else,
+ * a range outside the stream or an unknown id is CC_E_INVALID.  The members' CRC32 fields always come
+ * from k_crc32 over the device bytes, whatever cc_bgzf_set_crc says (there is no host copy to
+ * hash).  The same bytes give, byte for byte, cc_bgzf_deflate's members, at either effort.  Runs
+ * under the encoder's mutex on its two streams, from any thread. */
+int64_t cc_bgzf_deflate_resident(cc_ctx *ctx, int64_t id, uint64_t off, uint64_t n, uint8_t *stage, uint64_t slot,
+                                 uint32_t *out_len, int64_t cap);
+/* One cc_index_field per record of resident stream id (k_index_fields, csrc/bam_index.hip.inc: a
+ * record per lane, index_core.h's arithmetic): record i's block_size word is the stream's byte at[i],
+ * at[n + 1] offsets in all.  The records may sit at any byte offset; nothing outside
+ * [at[i], at[i + 1]) is looked at.  CC_E_INVALID, cc_last_error naming the first such record, when
+ * block_size < 32, at[i] + 4 + block_size != at[i + 1] (offsets out of order or past the stream
+ * included) or 32 + l_read_name + 4 * n_cigar_op > block_size; also when at[n] lies past the stream
+ * or the id is unknown.  fields then holds nothing of use.  Runs on the coders' first stream under
+ * the encoder's mutex, from any thread; with profiling on, cc_kernel_times reports the kernel as
+ * "index_fields". */
+int cc_index_fields(cc_ctx *ctx, int64_t id, const uint64_t *at, int64_t n, cc_index_field *fields);
 /* CRC-32 (zlib's) on the device (k_crc32: one workgroup of 256 threads per segment of at most 65,536
  * bytes at any byte address; slice-by-4 tables and a "through 4,080 zero bytes" operator built in LDS
  * from the polynomial; csrc/crc_core.h holds the arithmetic and the per-lane rule).  crc[i] = the
@@ -625,6 +708,21 @@ int cc_bam_assemble(cc_ctx *ctx, const uint8_t *header, uint64_t header_bytes, c
                     int32_t n_rg, int flags, uint8_t *out, uint64_t cap, uint64_t *at, uint64_t *total);
 /* the pair to hand to ccio_set_assemble_hook; unset the hook before cc_destroy */
 int cc_bam_assemble_hook(cc_ctx *ctx, ccio_assemble_fn *fn, void **user);
+/* cc_bam_assemble that leaves the stream on the device: the same kernels, but the stream is built in
+ * a buffer registered in the resident table (cc_resident_fetch, _free, _count, _crc32 and the calls
+ * above serve it; same padding) and named by *resident_id (> 0).  at[n + 1] and *total are always
+ * returned (both required); the stream is downloaded only when out is non-NULL (out[cap], as for
+ * cc_bam_assemble).  After any error *resident_id = 0, no resident stream remains and nothing the
+ * call allocated stays allocated. */
+int cc_bam_assemble_keep(cc_ctx *ctx, const uint8_t *header, uint64_t header_bytes, const cc_asm_src *srcs,
+                         int32_t nsrc, const cc_out_spec *spec, int64_t n, const char *names, const int64_t *name_off,
+                         int64_t n_names, uint64_t names_bytes, const uint8_t *cons_seq, uint64_t cons_seq_bytes,
+                         const uint8_t *cons_qual, uint64_t cons_qual_bytes, int32_t cons_group, const char *rg_blob,
+                         const int64_t *rg_off, int32_t n_rg, int flags, uint8_t *out, uint64_t cap, uint64_t *at,
+                         uint64_t *total, int64_t *resident_id);
+/* the set to hand to ccio_set_out_resident (assemble-keep, resident deflate, index fields, fetch and
+ * release over this context); unset it before cc_destroy */
+int cc_out_resident_hooks(cc_ctx *ctx, ccio_out_resident *cb, void **user);
 /* the group whose consensus buffers the hook's next call uses when libccio passes it no arrays (that
  * call consumes it); -1 clears it */
 int cc_bam_assemble_group(cc_ctx *ctx, int32_t group_id);
