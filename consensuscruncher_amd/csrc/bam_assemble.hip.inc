@@ -167,7 +167,15 @@ struct AsmArgs {
     const int64_t* rg_off;
     int32_t n_rg;
     int flags;
+    int64_t names_set = 0;   // a name set read in place of `names` (asm_names_of; 0: the host names)
 };
+
+// The name set a call reads: the one cc_bam_assemble_names selected, when the call brings no names of
+// its own (names null, names_bytes > 0).  The selection is not consumed: a stage writes several files
+// from one set.
+int64_t asm_names_of(cc_ctx* ctx, const char* names, uint64_t names_bytes) {
+    return ctx && !names && names_bytes > 0 ? ctx->asm_names : 0;
+}
 
 // cc_bam_assemble's work.  The stream's buffer comes from alloc(actx, total) once the sizes are known
 // (null alloc: a size query, null result: CC_E_INVALID); the caller holds the encoder's mutex when a
@@ -215,10 +223,25 @@ int bam_assemble(cc_ctx* ctx, const AsmArgs& a, const std::vector<const uint8_t*
         T.nsrc = a.nsrc;
         T.n_names = a.n_names;
         T.names_bytes = a.names_bytes;
-        RC(asm_upload_padded(ctx, guard.tmp, &T.names, a.names, a.names_bytes));
-        int64_t* no = nullptr;
-        RC(upload(ctx, guard.tmp, &no, a.name_off, a.n_names > 0 ? a.n_names + 1 : 0));
-        T.name_off = no;
+        if (a.names_set) {   // the set's blob and offsets where they lie (bam_assemble_locked checked its extents)
+            const NameSet& s = ctx->name_sets[a.names_set];
+            T.names = s.blob;
+            T.name_off = s.off;
+        } else {
+            auto names_up = [&]() -> int {
+                RC(asm_upload_padded(ctx, guard.tmp, &T.names, a.names, a.names_bytes));
+                int64_t* no = nullptr;
+                RC(upload(ctx, guard.tmp, &no, a.name_off, a.n_names > 0 ? a.n_names + 1 : 0));
+                T.name_off = no;
+                return 0;
+            };
+            if (a.names_bytes) {
+                ProfScope ps(ctx, "asm_names_upload");
+                RC(names_up());
+            } else {
+                RC(names_up());
+            }
+        }
         if (a.cons_group >= 0) {
             Group& g = *ctx->groups[a.cons_group];
             // (the buffers are hipMalloc's own allocations: 16-B aligned, and the aligned words around
@@ -338,13 +361,21 @@ int bam_assemble_locked(cc_ctx* ctx, const AsmArgs& a, cc_asm_alloc_fn alloc, vo
     if (rid) *rid = 0;
     if (!ctx) return CC_E_INVALID;
     if (a.n < 0 || a.nsrc < 0 || a.n_names < 0 || a.n_rg < 0 || (a.header_bytes && !a.header) ||
-        (a.n > 0 && (!a.spec || (a.nsrc > 0 && !a.srcs))) || (a.n_names > 0 && !a.name_off) || (a.names_bytes && !a.names) ||
+        (a.n > 0 && (!a.spec || (a.nsrc > 0 && !a.srcs))) || (a.n_names > 0 && !a.name_off && !a.names_set) || (a.names_bytes && !a.names && !a.names_set) ||
         (a.n_rg > 0 && (!a.rg_off || !a.rg_blob)) ||
         (a.cons_group < 0 && ((a.cons_seq_bytes && !a.cons_seq) || (a.cons_qual_bytes && !a.cons_qual)))) {
         ctx->err = "cc_bam_assemble: null or negative argument";
         return CC_E_INVALID;
     }
     if (a.cons_group >= 0 && !ctx->groups.count(a.cons_group)) { ctx->err = "cc_bam_assemble: unknown group"; return CC_E_INVALID; }
+    if (a.names_set) {
+        const auto it = ctx->name_sets.find(a.names_set);
+        if (it == ctx->name_sets.end()) { ctx->err = "cc_bam_assemble: unknown name set"; return CC_E_INVALID; }
+        if (a.n_names > it->second.n || a.names_bytes > (uint64_t)it->second.total) {
+            ctx->err = "cc_bam_assemble: n_names or names_bytes larger than the name set's";
+            return CC_E_INVALID;
+        }
+    }
     std::vector<const uint8_t*> resident((size_t)a.nsrc, nullptr);
     bool any = false;
     for (int32_t f = 0; f < a.nsrc; ++f) {
@@ -405,8 +436,9 @@ int asm_hook_fn(void* user, const uint8_t* header, uint64_t header_bytes, const 
         group = ctx->asm_group;
         ctx->asm_group = -1;
     }
-    const AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
-                    cons_seq_bytes, cons_qual, cons_qual_bytes, group, rg_blob, rg_off, n_rg, flags};
+    AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
+              cons_seq_bytes, cons_qual, cons_qual_bytes, group, rg_blob, rg_off, n_rg, flags};
+    a.names_set = asm_names_of(ctx, names, names_bytes);
     if (!alloc) return CC_E_INVALID;
     return bam_assemble_locked(ctx, a, alloc, actx, at, total);
 }
@@ -420,8 +452,9 @@ int cc_bam_assemble(cc_ctx* ctx, const uint8_t* header, uint64_t header_bytes, c
                     uint64_t names_bytes, const uint8_t* cons_seq, uint64_t cons_seq_bytes, const uint8_t* cons_qual,
                     uint64_t cons_qual_bytes, int32_t cons_group, const char* rg_blob, const int64_t* rg_off, int32_t n_rg,
                     int flags, uint8_t* out, uint64_t cap, uint64_t* at, uint64_t* total) {
-    const AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
-                    cons_seq_bytes, cons_qual, cons_qual_bytes, cons_group, rg_blob, rg_off, n_rg, flags};
+    AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
+              cons_seq_bytes, cons_qual, cons_qual_bytes, cons_group, rg_blob, rg_off, n_rg, flags};
+    a.names_set = asm_names_of(ctx, names, names_bytes);
     AsmFixed f{out, cap};
     const int rc = bam_assemble_locked(ctx, a, out ? asm_fixed_alloc : nullptr, &f, at, total);
     if (rc == CC_E_INVALID && out && total && *total > cap && ctx) ctx->err = "cc_bam_assemble: the buffer is smaller than the stream";
@@ -437,8 +470,9 @@ int cc_bam_assemble_keep(cc_ctx* ctx, const uint8_t* header, uint64_t header_byt
     *resident_id = 0;
     if (!at || !total) { ctx->err = "cc_bam_assemble_keep: at and total are required"; return CC_E_INVALID; }
     *total = 0;
-    const AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
-                    cons_seq_bytes, cons_qual, cons_qual_bytes, cons_group, rg_blob, rg_off, n_rg, flags};
+    AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
+              cons_seq_bytes, cons_qual, cons_qual_bytes, cons_group, rg_blob, rg_off, n_rg, flags};
+    a.names_set = asm_names_of(ctx, names, names_bytes);
     AsmFixed f{out, cap};
     const int rc = bam_assemble_locked(ctx, a, out ? asm_fixed_alloc : nullptr, &f, at, total, resident_id);
     if (rc == CC_E_INVALID && out && *total > cap) ctx->err = "cc_bam_assemble_keep: the buffer is smaller than the stream";
@@ -448,6 +482,13 @@ int cc_bam_assemble_keep(cc_ctx* ctx, const uint8_t* header, uint64_t header_byt
 int cc_bam_assemble_group(cc_ctx* ctx, int32_t group_id) {
     if (!ctx || (group_id >= 0 && !ctx->groups.count(group_id))) return CC_E_INVALID;
     ctx->asm_group = group_id;
+    return 0;
+}
+
+int cc_bam_assemble_names(cc_ctx* ctx, int64_t names_id) {
+    if (!ctx) return CC_E_INVALID;
+    if (names_id != 0 && !ctx->name_sets.count(names_id)) { ctx->err = "cc_bam_assemble_names: unknown name set"; return CC_E_INVALID; }
+    ctx->asm_names = names_id;
     return 0;
 }
 

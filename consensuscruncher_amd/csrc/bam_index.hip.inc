@@ -104,8 +104,9 @@ int outres_assemble_fn(void* user, const uint8_t* header, uint64_t header_bytes,
         group = ctx->asm_group;
         ctx->asm_group = -1;
     }
-    const AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
-                    cons_seq_bytes, cons_qual, cons_qual_bytes, group, rg_blob, rg_off, n_rg, flags};
+    AsmArgs a{header, header_bytes, srcs, nsrc, spec, n, names, name_off, n_names, names_bytes, cons_seq,
+              cons_seq_bytes, cons_qual, cons_qual_bytes, group, rg_blob, rg_off, n_rg, flags};
+    a.names_set = asm_names_of(ctx, names, names_bytes);   // (not consumed: the plain hook finds it too)
     if (need_host && !alloc) return CC_E_INVALID;
     const int rc = bam_assemble_locked(ctx, a, need_host ? alloc : nullptr, actx, at, total, token);
     if (rc) ctx->asm_group = group;   // the plain hook, which libccio tries next, still finds it

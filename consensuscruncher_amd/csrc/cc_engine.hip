@@ -5445,6 +5445,15 @@ EngineSwitches read_switches() {
 
 struct BgzfEnc;   // the device BGZF encoder's streams and buffers (bgzf_deflate.hip.inc)
 
+// A name set (cc_names_keep): a formatted blob that stays on the device with its 64-bit offsets.  The
+// blob obeys DevSrc's read contract (16-B aligned, align16(total) + 32 bytes, the tail zero); both
+// pointers are null in a set of no names.
+struct NameSet {
+    uint8_t* blob = nullptr;
+    int64_t* off = nullptr;   // off[n + 1]
+    int64_t n = 0, total = 0;
+};
+
 struct cc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -5484,6 +5493,10 @@ struct cc_ctx {
     int32_t asm_group = -1;               // cc_bam_assemble_group: the assemble hook's next consensus source
     uint8_t* names_buf = nullptr;         // cc_format_*_names' blob until cc_names_read fetches it
     int64_t names_total = -1;             // its bytes (-1: no blob)
+    int64_t* names_off = nullptr;         // its device offsets off64[names_n + 1], kept beside it for cc_names_keep
+    int64_t names_n = 0;
+    std::map<int64_t, NameSet> name_sets; // cc_names_keep's sets by id
+    int64_t asm_names = 0;                // cc_bam_assemble_names: the set the assembler reads (0: none; not consumed)
 };
 
 namespace {
@@ -6174,6 +6187,11 @@ int cc_destroy(cc_ctx* ctx) {
     if (ctx->sort_buf.p) (void)hipFree(ctx->sort_buf.p);
     if (ctx->scan_st) (void)hipFree(ctx->scan_st);
     if (ctx->names_buf) (void)hipFree(ctx->names_buf);
+    if (ctx->names_off) (void)hipFree(ctx->names_off);
+    for (auto& s : ctx->name_sets) {
+        if (s.second.blob) (void)hipFree(s.second.blob);
+        if (s.second.off) (void)hipFree(s.second.off);
+    }
     flush_prof(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     (void)hipFree(ctx->d_err);

@@ -2420,10 +2420,13 @@ int ccio_write_bam_ex(const char* path, ccio_bam* tmpl, ccio_interner* it, int64
     if (!cons_seq || !cons_qual)
         for (int64_t i = 0; i < n; ++i)
             if (spec[i].kind == CC_OUT_NEW) { set_err("write_bam: consensus records without consensus arrays"); return -2; }
+    if (!names)   // the names were with a hook (cc_bam_assemble_names), and no hook took the write
+        for (int64_t i = 0; i < n; ++i)
+            if (spec[i].kind != CC_OUT_RAW && spec[i].name_id >= 0) { set_err("write_bam: names not in host memory"); return -3; }
     const std::vector<std::string>& rgs = it->t[2].strs;
     auto name_of = [&](const cc_out_spec& sp, const char** nm) -> size_t {
         *nm = "";
-        if (sp.name_id < 0) return 0;
+        if (sp.name_id < 0 || !names) return 0;   // (without names only specs that need none get here)
         *nm = names + name_off[sp.name_id];
         return (size_t)(name_off[sp.name_id + 1] - name_off[sp.name_id]);
     };

@@ -11,6 +11,12 @@
 //                   no lane writes a byte that is not its name's
 // Nothing is read through a name's fields before the sizes kernel has accepted every name: the write
 // kernel is only launched when no name was refused.
+// The csn kernels are templates over where a name's nine fields and suffix come from: the call's
+// uploaded arrays (CsnUploaded, cc_format_csn_names) or a group's emit_ckey / emit_n where the SSCS
+// stage left them (CsnGroup, cc_format_csn_names_group).
+// The blob and its 64-bit offsets stay with the context until cc_names_read fetches the blob or
+// cc_names_keep turns the pair into a name set, which the assembler reads in place
+// (cc_bam_assemble_names).
 #include "name_core.h"
 
 namespace {
@@ -58,15 +64,33 @@ __device__ __forceinline__ void name_status(unsigned long long bad, uint32_t len
     }
 }
 
-__global__ __launch_bounds__(NM_T) void k_name_sizes_csn(const int32_t* __restrict__ f9, const int64_t* __restrict__ suffix,
-                                                         int64_t n, nmc::Strs bc, nmc::Strs cg, uint32_t* __restrict__ len,
-                                                         NameStatus* st) {
+// a csn name's fields from the call's uploaded arrays: a row of nine and a suffix per name
+struct CsnUploaded {
+    const int32_t* __restrict__ f9;
+    const int64_t* __restrict__ suffix;
+    __device__ __forceinline__ const int32_t* fields(int64_t i) const { return f9 + 9 * i; }
+    __device__ __forceinline__ int64_t suf(int64_t i) const { return suffix[i]; }
+};
+
+// ... from a group's buffers: emit_ckey holds a row per emitted entry, shared by the entry's two names
+// (SSCSRun.emit's np.repeat(..., 2)), emit_n the suffix of each name.  The host has checked that
+// emit_ckey holds n / 2 rows and emit_n n values before any launch.
+struct CsnGroup {
+    const int32_t* __restrict__ ckey;
+    const int32_t* __restrict__ emit_n;
+    __device__ __forceinline__ const int32_t* fields(int64_t i) const { return ckey + 9 * (i >> 1); }
+    __device__ __forceinline__ int64_t suf(int64_t i) const { return (int64_t)emit_n[i]; }
+};
+
+template <class Src>
+__global__ __launch_bounds__(NM_T) void k_name_sizes_csn(Src src, int64_t n, nmc::Strs bc, nmc::Strs cg,
+                                                         uint32_t* __restrict__ len, NameStatus* st) {
     const int64_t i = (int64_t)blockIdx.x * NM_T + threadIdx.x;
     unsigned long long bad = ~0ULL;
     uint32_t l = 0;
     if (i < n) {
         nmc::CsnLay y;
-        const uint32_t e = nmc::csn_layout(f9 + 9 * i, suffix[i], bc, cg, y);
+        const uint32_t e = nmc::csn_layout(src.fields(i), src.suf(i), bc, cg, y);
         if (e) bad = ((unsigned long long)i << 8) | e;
         else l = y.len;
         len[i] = l;
@@ -134,20 +158,20 @@ __device__ __forceinline__ void name_store(uint8_t* __restrict__ out, uint64_t o
 
 // Name i goes to out[off32[i] ...).  Every name was accepted by the sizes kernel and off32 is the scan of
 // the lengths it wrote, so each name lies inside out[0, total).
-__global__ __launch_bounds__(NM_T) void k_name_write_csn(const int32_t* __restrict__ f9, const int64_t* __restrict__ suffix,
-                                                         int64_t n, nmc::Strs bc, nmc::Strs cg,
+template <class Src>
+__global__ __launch_bounds__(NM_T) void k_name_write_csn(Src src, int64_t n, nmc::Strs bc, nmc::Strs cg,
                                                          const uint32_t* __restrict__ off32, uint64_t total,
                                                          uint8_t* __restrict__ out, int64_t* __restrict__ off64,
                                                          NameStatus* st) {
     const int64_t i = (int64_t)blockIdx.x * (NM_T / NM_LANES) + (threadIdx.x / NM_LANES);
     const uint32_t j = threadIdx.x % NM_LANES;
     if (i >= n) return;
-    const int32_t* f = f9 + 9 * i;
+    const int32_t* f = src.fields(i);
     (void)CC_IDX(f[0], bc.n, DS_REC);
     (void)CC_IDX(f[5], cg.n, DS_REC);
     (void)CC_IDX(f[6], cg.n, DS_REC);
     nmc::CsnLay y;
-    const uint32_t e = nmc::csn_layout(f, suffix[i], bc, cg, y);
+    const uint32_t e = nmc::csn_layout(f, src.suf(i), bc, cg, y);
     const uint64_t off = off32[i];
     if (e || off > total || y.len > total - off) {   // (containment: never expected)
         if (j == 0) atomicOr(&st->guard, 1u);
@@ -199,24 +223,36 @@ const char* name_refusal(uint32_t bits) {
     return "a record index outside the table";
 }
 
+std::atomic<int64_t> g_names_next{1};   // name set ids: positive, unique across contexts
+
 void names_release(cc_ctx* ctx) {
-    if (ctx->names_buf) {
+    if (ctx->names_buf || ctx->names_off) {
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->names_buf);
+        if (ctx->names_buf) (void)hipFree(ctx->names_buf);
+        if (ctx->names_off) (void)hipFree(ctx->names_off);
     }
     ctx->names_buf = nullptr;
+    ctx->names_off = nullptr;
+    ctx->names_n = 0;
     ctx->names_total = -1;
 }
 
-// the call's allocations: the temporaries always freed, the blob unless the call succeeded
+const NameSet* names_find(cc_ctx* ctx, int64_t id) {
+    const auto it = id > 0 ? ctx->name_sets.find(id) : ctx->name_sets.end();
+    return it != ctx->name_sets.end() ? &it->second : nullptr;
+}
+
+// the call's allocations: the temporaries always freed, the blob and its offsets unless the call succeeded
 struct NameGuard {
     cc_ctx* ctx;
     std::vector<void*> tmp;
     uint8_t* blob = nullptr;
+    int64_t* off = nullptr;
     ~NameGuard() {
         (void)hipStreamSynchronize(ctx->stream);   // nothing enqueued still uses them
         for (void* p : tmp) (void)hipFree(p);
         if (blob) (void)hipFree(blob);
+        if (off) (void)hipFree(off);
     }
 };
 
@@ -239,7 +275,8 @@ struct NameRun {
         h_st->first_bad = ~0ULL;
         RC(dev_alloc(ctx, guard.tmp, &len, n, 64));
         RC(dev_alloc(ctx, guard.tmp, &off32, n, 64));
-        RC(dev_alloc(ctx, guard.tmp, &d_off, n + 1));
+        HIPCHK(hipMalloc((void**)&guard.off, sizeof(int64_t) * (size_t)(n + 1)));
+        d_off = guard.off;
         RC(dev_alloc(ctx, guard.tmp, &d_st, 1));
         HIPCHK(hipMemcpyAsync(d_st, h_st, sizeof(NameStatus), hipMemcpyHostToDevice, ctx->stream));
         return 0;
@@ -270,7 +307,10 @@ struct NameRun {
             ctx->err = std::string(what) + ": the offsets' scan total does not match the lengths";
             return CC_E_INVALID;
         }
-        HIPCHK(hipMalloc((void**)&guard.blob, (size_t)h_st->total + 16));
+        // (the assembler's read contract, as asm_upload_padded gives it: a name set is read in place)
+        const size_t padded = (size_t)((h_st->total + 15) & ~15ull) + 32;
+        HIPCHK(hipMalloc((void**)&guard.blob, padded));
+        HIPCHK(hipMemsetAsync(guard.blob + h_st->total, 0, padded - (size_t)h_st->total, ctx->stream));
         return 0;
     }
     // after the write kernel: the offsets fetched, the blob handed to the context
@@ -288,8 +328,11 @@ struct NameRun {
         }
         *total = (int64_t)h_st->total;
         ctx->names_buf = guard.blob;
+        ctx->names_off = guard.off;
+        ctx->names_n = n;
         ctx->names_total = *total;
         guard.blob = nullptr;
+        guard.off = nullptr;
         return 0;
     }
 };
@@ -312,6 +355,25 @@ int names_strs(cc_ctx* ctx, std::vector<void*>& tmp, nmc::Strs* s, const char* b
     return 0;
 }
 
+// cc_format_csn_names' and cc_format_csn_names_group's work once the fields' source is on the device
+template <class Src>
+int names_csn(NameRun& run, const Src& src, const nmc::Strs& bc, const nmc::Strs& cg, int64_t* off, int64_t* total) {
+    cc_ctx* ctx = run.ctx;
+    const int64_t n = run.n;
+    RC(run.begin());
+    klaunch(ctx, "name_sizes", k_name_sizes_csn<Src>, nblk(n, NM_T), NM_T, src, n, bc, cg, run.len, run.d_st);
+    RC(run.offsets());
+    klaunch(ctx, "name_write", k_name_write_csn<Src>, nblk(n, NM_T / NM_LANES), NM_T, src, n, bc, cg, run.off32,
+            (uint64_t)run.h_st->total, run.guard.blob, run.d_off, run.d_st);
+    return run.finish(off, total);
+}
+
+bool names_tables_bad(const char* bc_blob, const int64_t* bc_off, int64_t n_bc, const char* cg_blob, const int64_t* cg_off,
+                      int64_t n_cg) {
+    return n_bc < 0 || n_cg < 0 || (n_bc > 0 && !bc_off) || (n_cg > 0 && !cg_off) || (n_bc > 0 && bc_off[n_bc] > 0 && !bc_blob) ||
+           (n_cg > 0 && cg_off[n_cg] > 0 && !cg_blob);
+}
+
 }  // namespace
 
 extern "C" {
@@ -320,8 +382,7 @@ int cc_format_csn_names(cc_ctx* ctx, int64_t n, const int32_t* f9, const int64_t
                         const int64_t* bc_off, int64_t n_bc, const char* cg_blob, const int64_t* cg_off, int64_t n_cg,
                         int64_t* off, int64_t* total) {
     if (!ctx) return CC_E_INVALID;
-    if (n < 0 || n_bc < 0 || n_cg < 0 || !off || !total || (n > 0 && (!f9 || !suffix)) || (n_bc > 0 && !bc_off) ||
-        (n_cg > 0 && !cg_off) || (n_bc > 0 && bc_off[n_bc] > 0 && !bc_blob) || (n_cg > 0 && cg_off[n_cg] > 0 && !cg_blob)) {
+    if (n < 0 || !off || !total || (n > 0 && (!f9 || !suffix)) || names_tables_bad(bc_blob, bc_off, n_bc, cg_blob, cg_off, n_cg)) {
         ctx->err = "cc_format_csn_names: null or negative argument";
         return CC_E_INVALID;
     }
@@ -335,14 +396,45 @@ int cc_format_csn_names(cc_ctx* ctx, int64_t n, const int32_t* f9, const int64_t
     RC(names_strs(ctx, run.guard.tmp, &cg, cg_blob, cg_off, n_cg));
     int32_t* d_f9 = nullptr;
     int64_t* d_suf = nullptr;
-    RC(upload(ctx, run.guard.tmp, &d_f9, f9, 9 * n));
-    RC(upload(ctx, run.guard.tmp, &d_suf, suffix, n));
-    RC(run.begin());
-    klaunch(ctx, "name_sizes", k_name_sizes_csn, nblk(n, NM_T), NM_T, d_f9, d_suf, n, bc, cg, run.len, run.d_st);
-    RC(run.offsets());
-    klaunch(ctx, "name_write", k_name_write_csn, nblk(n, NM_T / NM_LANES), NM_T, d_f9, d_suf, n, bc, cg, run.off32,
-            (uint64_t)run.h_st->total, run.guard.blob, run.d_off, run.d_st);
-    return run.finish(off, total);
+    {
+        ProfScope ps(ctx, "name_fields_upload");   // (what cc_format_csn_names_group does without)
+        RC(upload(ctx, run.guard.tmp, &d_f9, f9, 9 * n));
+        RC(upload(ctx, run.guard.tmp, &d_suf, suffix, n));
+    }
+    return names_csn(run, CsnUploaded{d_f9, d_suf}, bc, cg, off, total);
+}
+
+int cc_format_csn_names_group(cc_ctx* ctx, int32_t group_id, const char* bc_blob, const int64_t* bc_off, int64_t n_bc,
+                              const char* cg_blob, const int64_t* cg_off, int64_t n_cg, int64_t* off, int64_t* total) {
+    if (!ctx) return CC_E_INVALID;
+    if (!off || !total || names_tables_bad(bc_blob, bc_off, n_bc, cg_blob, cg_off, n_cg)) {
+        ctx->err = "cc_format_csn_names_group: null or negative argument";
+        return CC_E_INVALID;
+    }
+    if (!ctx->groups.count(group_id)) { ctx->err = "cc_format_csn_names_group: unknown group"; return CC_E_INVALID; }
+    const Group& g = *ctx->groups[group_id];
+    const int32_t* ckey = g.ptr<B::emit_ckey>();
+    const int32_t* emit_n = g.ptr<B::emit_n>();
+    if (!g.planned[ST_SSCS] || !ckey || !emit_n) {
+        ctx->err = "cc_format_csn_names_group: the group holds no cc_consensus_maker output";
+        return CC_E_INVALID;
+    }
+    // the extents the kernels index by, from the buffers' used sizes: a row of emit_ckey per two names
+    const size_t ck_used = g.buf[(int)B::emit_ckey].used, en_used = g.buf[(int)B::emit_n].used;
+    const int64_t rows = (int64_t)(ck_used / (9 * sizeof(int32_t))), n = (int64_t)(en_used / sizeof(int32_t));
+    if (ck_used % (9 * sizeof(int32_t)) || en_used % sizeof(int32_t) || rows * 2 != n) {
+        ctx->err = "cc_format_csn_names_group: emit_ckey does not hold a row per two values of emit_n";
+        return CC_E_INVALID;
+    }
+    if (n > (int64_t)INT32_MAX) { ctx->err = "cc_format_csn_names: more than 2^31 - 1 names"; return CC_E_UNSUPPORTED; }
+    RC(enter(ctx));
+    names_release(ctx);
+    if (n == 0) return names_empty(ctx, off, total);
+    NameRun run(ctx, "cc_format_csn_names", n);
+    nmc::Strs bc{}, cg{};
+    RC(names_strs(ctx, run.guard.tmp, &bc, bc_blob, bc_off, n_bc));
+    RC(names_strs(ctx, run.guard.tmp, &cg, cg_blob, cg_off, n_cg));
+    return names_csn(run, CsnGroup{ckey, emit_n}, bc, cg, off, total);
 }
 
 int cc_format_dcs_names(cc_ctx* ctx, int32_t table, int64_t n, const int64_t* rec_tag, const int64_t* rec_ds, int64_t* off,
@@ -389,5 +481,50 @@ int cc_names_read(cc_ctx* ctx, char* blob, int64_t cap) {
     names_release(ctx);
     return 0;
 }
+
+int cc_names_keep(cc_ctx* ctx, int64_t* names_id) {
+    if (!ctx || !names_id) return CC_E_INVALID;
+    *names_id = 0;
+    if (ctx->names_total < 0) { ctx->err = "cc_names_keep: no formatted names to keep"; return CC_E_INVALID; }
+    RC(enter(ctx));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (the format call waited already)
+    const int64_t id = g_names_next.fetch_add(1);
+    ctx->name_sets[id] = NameSet{ctx->names_buf, ctx->names_off, ctx->names_n, ctx->names_total};
+    ctx->names_buf = nullptr;   // the set's from here on
+    ctx->names_off = nullptr;
+    names_release(ctx);
+    *names_id = id;
+    return 0;
+}
+
+int64_t cc_names_fetch(cc_ctx* ctx, int64_t names_id, char* blob, int64_t cap) {
+    if (!ctx) return CC_E_INVALID;
+    const NameSet* s = names_find(ctx, names_id);
+    if (!s) { ctx->err = "cc_names_fetch: unknown name set"; return CC_E_INVALID; }
+    if (!blob) return s->total;
+    if (cap < s->total) { ctx->err = "cc_names_fetch: the buffer is smaller than the blob"; return CC_E_INVALID; }
+    RC(enter(ctx));
+    if (s->total > 0) {
+        ProfScope ps(ctx, "name_download");
+        HIPCHK(hipMemcpyAsync(blob, s->blob, (size_t)s->total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return s->total;
+}
+
+int cc_names_free(cc_ctx* ctx, int64_t names_id) {
+    if (!ctx) return CC_E_INVALID;
+    const NameSet* s = names_find(ctx, names_id);
+    if (!s) { ctx->err = "cc_names_free: unknown name set"; return CC_E_INVALID; }
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);   // no assemble still reads it
+    if (s->blob) (void)hipFree(s->blob);
+    if (s->off) (void)hipFree(s->off);
+    ctx->name_sets.erase(names_id);
+    if (ctx->asm_names == names_id) ctx->asm_names = 0;
+    return 0;
+}
+
+int64_t cc_names_count(cc_ctx* ctx) { return ctx ? (int64_t)ctx->name_sets.size() : CC_E_INVALID; }
 
 }  // extern "C"

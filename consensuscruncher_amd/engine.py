@@ -370,6 +370,7 @@ class Engine(object):
         self.out_resident_device = False   # the resident output set is wired (device_out_resident)
         self._out_resident_want = os.environ.get("CC_OUT_RESIDENT_DEVICE") == "1"
         self.names_device = os.environ.get("CC_NAMES_DEVICE") == "1"
+        self._names_resident_want = os.environ.get("CC_NAMES_RESIDENT_DEVICE") == "1"
         if os.environ.get("CC_CRC_DEVICE") == "1":   # before the hooks below are wired: they take the crc variants
             self.device_crc(True)
         if os.environ.get("CC_RESIDENT_DEVICE") == "1":
@@ -685,15 +686,82 @@ class Engine(object):
         self.names_device = bool(on)
         return was
 
-    def _names_blob(self, n, off, total):
+    def device_names_resident(self, on):
+        """Asks for (or gives up) resident names (off is the default): the stages keep the blob the device
+        formatter wrote on the device as a name set (cc_names_keep) that the device assembler reads in
+        place (write_bam: names_dev), and the SSCS stage formats its names from the group's own
+        emit_ckey / emit_n (csn_names_group), so neither the blob nor those fields cross the bus.  The
+        files are the same either way.  Effective only while names_device and assemble_device are both
+        on (names_resident_device says whether it is); otherwise it has no effect and raises nothing.
+        A per-engine switch.  Returns the previous request."""
+        was = self._names_resident_want
+        self._names_resident_want = bool(on)
+        return was
+
+    @property
+    def names_resident_device(self):
+        return bool(self._names_resident_want and self.names_device and self.assemble_device and self.h)
+
+    def _names_blob(self, n, off, total, keep=False):
+        if keep:
+            nid = C.c_int64(0)
+            self._check(self.lib.cc_names_keep(self.h, C.byref(nid)))
+            return KeptNames(nid.value), off
         blob = np.zeros(max(int(total), 1), np.uint8)
         self._check(self.lib.cc_names_read(self.h, N.ptr(blob), int(total)))
         return blob, off
 
-    def csn_names(self, interner, ckey9, suffix):
+    def names_fetch(self, names_id):
+        """A name set's blob (cc_names_fetch) as a uint8 array; the set stays as it is."""
+        total = int(self.lib.cc_names_fetch(self.h, int(names_id), None, 0))
+        if total < 0:
+            self._check(total)
+        blob = np.zeros(max(total, 1), np.uint8)
+        got = int(self.lib.cc_names_fetch(self.h, int(names_id), N.ptr(blob), total))
+        if got < 0:
+            self._check(got)
+        return blob
+
+    def names_free(self, names_id):
+        self._check(self.lib.cc_names_free(self.h, int(names_id)))
+
+    def names_count(self):
+        return int(self.lib.cc_names_count(self.h))
+
+    def csn_names_group(self, group, interner, keep=False):
+        """The SSCS stage's names from the group's own buffers (cc_format_csn_names_group): what
+        csn_names(interner, repeat(fetch(emit_ckey), 2), fetch(emit_n)) gives, without fetching or
+        uploading either array.  The result is csn_names': (blob, off), or with keep=True
+        (KeptNames, off); what the device refuses or does not support goes to the host function over
+        the fetched arrays and comes back as (blob, off)."""
+        bc, bc_off = interner.blob(0)
+        cg, cg_off = interner.blob(1)
+        n = self._used(group, "emit_n") // 4
+        off = np.zeros(n + 1, np.int64)
+        total = C.c_int64(0)
+        rc = self.lib.cc_format_csn_names_group(self.h, int(group), N.ptr(bc), N.ptr(bc_off), len(bc_off) - 1, N.ptr(cg),
+                                                N.ptr(cg_off), len(cg_off) - 1, N.ptr(off), C.byref(total))
+        if rc in (N.CC_E_INVALID, N.CC_E_UNSUPPORTED):
+            ckey = np.repeat(self.fetch(group, "emit_ckey", np.int32).reshape(-1, 9), 2, axis=0).reshape(-1)
+            return csn_names(interner, ckey, self.fetch(group, "emit_n", np.int32))
+        self._check(rc)
+        return self._names_blob(n, off, total.value, keep)
+
+    def _used(self, group, name):
+        """A group buffer's bytes in use (cc_fetch's size query)."""
+        nb = int(self.lib.cc_fetch(self.h, group, name.encode(), None, 0))
+        if nb < 0:
+            raise N.CCError(nb, self.lib.cc_last_error(self.h).decode())
+        return nb
+
+    def csn_names(self, interner, ckey9, suffix, keep=False):
         """csn_names on the device (cc_format_csn_names): the same (blob, off).  What the device refuses
         (an id outside its table) or does not support goes to the host function, which raises what
-        it always raised."""
+        it always raised.  keep=True leaves the blob on the device as a name set (cc_names_keep) and
+        returns (KeptNames, off): KeptNames is the set's id (an int subclass) for names_fetch,
+        names_free, assemble(names_id=) and write_bam(names_dev=).  When the host function ran instead
+        the result is the ordinary (blob, off) whatever keep says, so a caller that keeps tells the
+        two by isinstance(result[0], KeptNames)."""
         n = len(suffix)
         ck = np.ascontiguousarray(ckey9, np.int32).reshape(-1)
         sf = np.ascontiguousarray(suffix, np.int64)
@@ -708,13 +776,13 @@ class Engine(object):
         if rc in (N.CC_E_INVALID, N.CC_E_UNSUPPORTED):
             return csn_names(interner, ckey9, suffix)
         self._check(rc)
-        return self._names_blob(n, off, total.value)
+        return self._names_blob(n, off, total.value, keep)
 
-    def dcs_names(self, bam, table, rec_tag, rec_ds):
+    def dcs_names(self, bam, table, rec_tag, rec_ds, keep=False):
         """dcs_names on the device (cc_format_dcs_names) from `table`, the record table built from bam:
         the same (blob, off).  Names with a NUL inside (ccio_dcs_names_plain: the table keeps them up to
         it), whatever the device refuses (the reference's IndexError) and what it does not support go
-        to the host function, which raises what it always raised."""
+        to the host function, which raises what it always raised.  keep: as for csn_names."""
         n = len(rec_tag)
         a = np.ascontiguousarray(rec_tag, np.int64)
         b = np.ascontiguousarray(rec_ds, np.int64)
@@ -726,17 +794,34 @@ class Engine(object):
         if rc in (N.CC_E_INVALID, N.CC_E_UNSUPPORTED):
             return dcs_names(bam, rec_tag, rec_ds)
         self._check(rc)
-        return self._names_blob(n, off, total.value)
+        return self._names_blob(n, off, total.value, keep)
 
     def assemble(self, header, sources, specs, names=None, name_off=None, cons_seq=None, cons_qual=None, group=None,
-                 rg_values=(), sort=False, keep=False):
+                 rg_values=(), sort=False, keep=False, names_id=None):
         """cc_bam_assemble: the output stream (header bytes, then the records of `specs`) and its
         n + 1 record offsets, as (bytes, uint64 array).  sources: per source (stream, rec_off) with the
         records' bytes and offsets in host memory, or (None, rec_off, resident id, base, nbytes) for a
         resident stream.  The consensus arrays are cons_seq / cons_qual, or group's device buffers.
         rg_values: the RG table's values (bytes), by rg_id.  sort: samtools-sort order.  keep=True is
         cc_bam_assemble_keep without a download: (at, token), the stream left on the device as resident
-        stream `token` (resident_fetch, bgzf_deflate_resident, index_fields; resident_free when done)."""
+        stream `token` (resident_fetch, bgzf_deflate_resident, index_fields; resident_free when done).
+        names_id, in place of names: a name set (csn_names / dcs_names with keep=True) read where it
+        lies (cc_bam_assemble_names, selected for this call only); name_off (the set's off, or a prefix
+        of it) then says how many names and bytes of the set the specs may use."""
+        if names_id is not None:
+            if names is not None:
+                raise ValueError("assemble: names or names_id, not both")
+            self._check(self.lib.cc_bam_assemble_names(self.h, int(names_id)))
+            try:
+                return self._assemble(header, sources, specs, None, name_off, cons_seq, cons_qual, group, rg_values, sort,
+                                      keep, True)
+            finally:
+                self.lib.cc_bam_assemble_names(self.h, 0)
+        return self._assemble(header, sources, specs, names, name_off, cons_seq, cons_qual, group, rg_values, sort, keep,
+                              False)
+
+    def _assemble(self, header, sources, specs, names, name_off, cons_seq, cons_qual, group, rg_values, sort, keep,
+                  in_set):
         header = np.frombuffer(bytes(header), np.uint8)
         specs = np.ascontiguousarray(specs, N.OUT_SPEC_DTYPE)
         n = len(specs)
@@ -754,6 +839,7 @@ class Engine(object):
                 arr[f] = N.cc_asm_src(st.ctypes.data if len(st) else None, len(st), 0, 0, off.ctypes.data, len(off))
         names = np.zeros(0, np.uint8) if names is None else np.ascontiguousarray(names).view(np.uint8)
         name_off = np.zeros(1, np.int64) if name_off is None else np.ascontiguousarray(name_off, np.int64)
+        names_bytes = int(name_off[-1]) if in_set else len(names)   # (a set: the bytes its first n_names names take)
         cs = np.zeros(0, np.uint8) if cons_seq is None else np.ascontiguousarray(cons_seq, np.uint8)
         cq = np.zeros(0, np.uint8) if cons_qual is None else np.ascontiguousarray(cons_qual, np.uint8)
         rg = [bytes(v) for v in rg_values]
@@ -764,7 +850,7 @@ class Engine(object):
         def call(out, cap, at, total):
             return self.lib.cc_bam_assemble(
                 self.h, N.ptr(header) if len(header) else None, len(header), arr, len(sources), N.ptr(specs), n,
-                N.ptr(names) if len(names) else None, N.ptr(name_off), len(name_off) - 1, len(names),
+                N.ptr(names) if len(names) else None, N.ptr(name_off), len(name_off) - 1, names_bytes,
                 N.ptr(cs) if len(cs) else None, len(cs), N.ptr(cq) if len(cq) else None, len(cq),
                 -1 if group is None else int(group), N.ptr(rg_blob), N.ptr(rg_off), len(rg), N.W_SORT if sort else 0,
                 out, cap, at, total)
@@ -774,7 +860,7 @@ class Engine(object):
             rid = C.c_int64(0)
             self._check(self.lib.cc_bam_assemble_keep(
                 self.h, N.ptr(header) if len(header) else None, len(header), arr, len(sources), N.ptr(specs), n,
-                N.ptr(names) if len(names) else None, N.ptr(name_off), len(name_off) - 1, len(names),
+                N.ptr(names) if len(names) else None, N.ptr(name_off), len(name_off) - 1, names_bytes,
                 N.ptr(cs) if len(cs) else None, len(cs), N.ptr(cq) if len(cq) else None, len(cq),
                 -1 if group is None else int(group), N.ptr(rg_blob), N.ptr(rg_off), len(rg), N.W_SORT if sort else 0,
                 None, 0, N.ptr(at), C.byref(total), C.byref(rid)))
@@ -1303,14 +1389,34 @@ def dcs_names(bam, rec_tag, rec_ds):
     return blob, off
 
 
+class KeptNames(int):
+    """A name set's id (Engine.csn_names / dcs_names / csn_names_group with keep=True): the first item
+    of their result in place of the blob.  An int, so it goes wherever a names_id goes."""
+
+
 def write_bam(path, template, interner, specs, srcs, names=None, name_off=None, cons_seq=None, cons_qual=None,
-              level=6, nthreads=0, sink=None, cons_group=None):
+              level=6, nthreads=0, sink=None, cons_group=None, names_dev=None):
     """Assembles and writes one output BAM (ccio_write_bam).  sink (the orchestrator's fused
     sort_index, Sink) may redirect it: written sorted and indexed under its sorted name, and kept in
     memory for the next stage.  cons_group, in place of cons_seq / cons_qual: (engine, group) whose
     device consensus buffers the engine's assembler reads (Engine.device_assemble); when the
     assembler does not take the write, the arrays are fetched and the host assembles as always.
+    names_dev, in place of names: (engine, names_id), a name set the engine's assembler reads where it
+    lies (cc_bam_assemble_names; name_off is still the host's); when no hook takes the write
+    (ccio_write_bam_ex's -3) the blob is fetched once and the write goes the ordinary way.
     Returns the path written."""
+    if names_dev is not None and names is None:
+        eng, nid = names_dev
+        if eng.assemble_device:
+            eng._check(eng.lib.cc_bam_assemble_names(eng.h, int(nid)))
+            try:
+                return write_bam(path, template, interner, specs, srcs, _NAMES_WITH_HOOK, name_off, cons_seq, cons_qual,
+                                 level, nthreads, sink, cons_group)
+            except _NeedNames:
+                pass
+            finally:
+                eng.lib.cc_bam_assemble_names(eng.h, 0)
+        names = eng.names_fetch(nid)
     if cons_group is not None and cons_seq is None:
         eng, g = cons_group
         if eng.assemble_device:
@@ -1364,6 +1470,13 @@ class _NeedCons(Exception):
     """ccio_write_bam_ex's -2: consensus records, no host arrays, and no hook took the write."""
 
 
+class _NeedNames(Exception):
+    """ccio_write_bam_ex's -3: specs with names, no host names, and no hook took the write."""
+
+
+_NAMES_WITH_HOOK = object()   # _write_bam's names: ccio_write_bam_ex gets NULL (the names are with the hook)
+
+
 def _write_bam(path, template, interner, specs, srcs, names, name_off, cons_seq, cons_qual, level, nthreads, sink,
                own_cons=False):
     specs = np.ascontiguousarray(specs, N.OUT_SPEC_DTYPE)
@@ -1374,14 +1487,17 @@ def _write_bam(path, template, interner, specs, srcs, names, name_off, cons_seq,
     if sink is not None:
         out, flags, k = sink.route(path)
         keep = N.P() if k else None
+    with_hook = names is _NAMES_WITH_HOOK
     rc = N.io().ccio_write_bam_ex(out.encode(), template.h, interner.h, len(specs), N.ptr(specs), arr, len(srcs),
-                                  N.ptr(names if names is not None else dummy),
+                                  None if with_hook else N.ptr(names if names is not None else dummy),
                                   N.ptr(name_off if name_off is not None else dummy_off),
                                   None if own_cons else N.ptr(cons_seq if cons_seq is not None and len(cons_seq) else dummy),
                                   None if own_cons else N.ptr(cons_qual if cons_qual is not None and len(cons_qual) else dummy),
                                   level, nthreads, flags, C.byref(keep) if keep is not None else None)
     if rc == -2 and own_cons:
         raise _NeedCons()
+    if rc == -3 and with_hook:
+        raise _NeedNames()
     if rc != 0:
         raise IOError(N.io_error())
     if keep is not None:

@@ -261,6 +261,12 @@ AMD_SIGS = {
     "cc_format_csn_names": (C.c_int, [P, C.c_int64, P, P, P, P, C.c_int64, P, P, C.c_int64, P, i64p]),
     "cc_format_dcs_names": (C.c_int, [P, C.c_int32, C.c_int64, P, P, P, i64p]),
     "cc_names_read": (C.c_int, [P, P, C.c_int64]),
+    "cc_format_csn_names_group": (C.c_int, [P, C.c_int32, P, P, C.c_int64, P, P, C.c_int64, P, i64p]),
+    "cc_names_keep": (C.c_int, [P, i64p]),
+    "cc_names_fetch": (C.c_int64, [P, C.c_int64, P, C.c_int64]),
+    "cc_names_free": (C.c_int, [P, C.c_int64]),
+    "cc_names_count": (C.c_int64, [P]),
+    "cc_bam_assemble_names": (C.c_int, [P, C.c_int64]),
     "cc_table_free": (C.c_int, [P, C.c_int32]),
     "cc_table_derive": (C.c_int, [P, C.c_int32]),
     "cc_table_fetch": (C.c_int64, [P, C.c_int32, C.c_char_p, P, C.c_int64]),

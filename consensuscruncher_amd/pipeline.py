@@ -53,8 +53,11 @@ def cleanup(sd, identifier, scorrect):
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
                        bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host", crc="host",
-                       assemble="host", names="host", out_resident="host"):
-    """out_resident: "host" (the default) or "device" (Engine.device_out_resident: each stage output's
+                       assemble="host", names="host", out_resident="host", names_resident="host"):
+    """names_resident: "host" (the default) or "device" (Engine.device_names_resident: a stage's formatted
+    names stay on the device as a name set the assembler reads in place, and the SSCS names are formatted
+    from the group's own buffers: the same files); it engages only with names="device" and
+    assemble="device" and is otherwise without effect.  out_resident: "host" (the default) or "device" (Engine.device_out_resident: each stage output's
     assembled stream stays on the device for the encoder and the index, and a stage's source is uploaded
     once for its writes, Engine.pin_source: the same files); it engages only with assemble="device" and
     bgzf="device" and is otherwise without effect.  names: "host" (libccio formats the consensus read names, the default) or "device" (the engine's
@@ -75,6 +78,17 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
     come from the device; same bytes read, same files written); it engages only with inflate="device"
     or bgzf="device" and is otherwise without effect.  Each option is wired for this call only; see
     _consensus_pipeline."""
+    if names_resident not in ("host", "device"):
+        raise ValueError('names_resident must be "host" or "device"')
+    if names_resident == "device":
+        engine = engine or get_engine()
+        was_nres = engine.device_names_resident(True)
+        try:
+            return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                      cleanup_files, all_unique_sscs, bgzf, inflate, decode, bgzf_effort, resident, crc,
+                                      assemble, names, out_resident)
+        finally:
+            engine.device_names_resident(was_nres)
     if out_resident not in ("host", "device"):
         raise ValueError('out_resident must be "host" or "device"')
     if out_resident == "device":

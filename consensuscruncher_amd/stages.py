@@ -16,7 +16,7 @@ import time
 import numpy as np
 
 from . import native as N
-from .engine import (MODE_DUPLEX, MODE_SSCS, Bam, Engine, Interner, bed_stream, csn_names, dcs_names,
+from .engine import (MODE_DUPLEX, MODE_SSCS, Bam, Engine, Interner, KeptNames, bed_stream, csn_names, dcs_names,
                      make_specs, whole_file_stream, write_bam)
 
 __all__ = ["SSCSRun", "DCSRun", "SCRun", "run_sscs", "run_dcs", "run_sc", "get_engine", "sscs_side", "dcs_side",
@@ -55,6 +55,20 @@ def _stream(bam, rec, bedfile):
 def _pinned(eng, bam):
     """Engine.pin_source(bam) while the resident output path is wired, else nothing."""
     return eng.pin_source(bam) if eng.out_resident_device else contextlib.nullcontext()
+
+
+@contextlib.contextmanager
+def _kept(eng, names):
+    """A formatter's first result as write_bam takes it: (names, names_dev).  A blob goes as names; a
+    name set (KeptNames: the formatter ran with keep=True and did not fall back to the host) goes as
+    names_dev and is freed on exit, whichever way the block ends."""
+    if isinstance(names, KeptNames):
+        try:
+            yield None, (eng, names)
+        finally:
+            eng.names_free(names)
+    else:
+        yield names, None
 
 
 class SSCSRun(object):
@@ -113,8 +127,10 @@ class SSCSRun(object):
         emit_n = eng.fetch(g, "emit_n", np.int32)
         emit_rec = eng.fetch(g, "emit_rec", np.int32)
         emit_vslot = eng.fetch(g, "emit_vslot", np.int32)
-        # one sscs_qname per entry, shared by the entry's two emitted records
-        emit_ckey = np.repeat(eng.fetch(g, "emit_ckey", np.int32).reshape(-1, 9), 2, axis=0).reshape(-1)
+        # one sscs_qname per entry, shared by the entry's two emitted records (with resident names the
+        # formatter reads emit_ckey where the vote left it: csn_names_group)
+        keep = eng.names_resident_device
+        emit_ckey = None if keep else np.repeat(eng.fetch(g, "emit_ckey", np.int32).reshape(-1, 9), 2, axis=0).reshape(-1)
         meta = eng.fetch(g, "vote_meta", np.int32).reshape(-1, 5)
         # with the device assembler on, the consensus arrays stay on the device (write_bam: cons_group)
         cgroup = (eng, g) if eng.assemble_device else None
@@ -126,24 +142,29 @@ class SSCSRun(object):
         ne = len(emit_n)
         self.times["emit_fetch"] = time.time() - t0
         t0 = time.time()
-        names, name_off = eng.csn_names(it, emit_ckey, emit_n) if eng.names_device else csn_names(it, emit_ckey, emit_n)
-        self.times["emit_names"] = time.time() - t0
-        t0 = time.time()
-        voted = emit_vslot >= 0
-        # SSCS records (create_aligned_segment) and renamed singletons, in emission order
-        with _pinned(eng, bam):   # (the source uploaded once for these writes)
-            sp = _new_specs(voted, emit_rec[voted], np.nonzero(voted)[0], emit_vslot[voted], meta, qstride)
-            write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
-                      cons_group=cgroup)
-            ss = make_specs(int((~voted).sum()))
-            ss["kind"] = N.OUT_RENAME
-            ss["src_rec"] = emit_rec[~voted]
-            ss["name_id"] = np.nonzero(~voted)[0]
-            write_bam('{}.singleton.bam'.format(prefix), bam, it, ss, [bam], names, name_off, level=level, sink=sink)
-            bs = make_specs(len(bad_rec))
-            bs["kind"] = N.OUT_RAW
-            bs["src_rec"] = bad_rec
-            write_bam('{}.badReads.bam'.format(prefix), bam, it, bs, [bam], level=level, sink=sink)
+        if keep:
+            names, name_off = eng.csn_names_group(g, it, keep=True)
+        else:
+            names, name_off = eng.csn_names(it, emit_ckey, emit_n) if eng.names_device else csn_names(it, emit_ckey, emit_n)
+        with _kept(eng, names) as (names, ndev):   # (a kept set is freed behind the pinned block)
+            self.times["emit_names"] = time.time() - t0
+            t0 = time.time()
+            voted = emit_vslot >= 0
+            with _pinned(eng, bam):   # (the source uploaded once for these writes)
+                # SSCS records (create_aligned_segment) and renamed singletons, in emission order
+                sp = _new_specs(voted, emit_rec[voted], np.nonzero(voted)[0], emit_vslot[voted], meta, qstride)
+                write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
+                          cons_group=cgroup, names_dev=ndev)
+                ss = make_specs(int((~voted).sum()))
+                ss["kind"] = N.OUT_RENAME
+                ss["src_rec"] = emit_rec[~voted]
+                ss["name_id"] = np.nonzero(~voted)[0]
+                write_bam('{}.singleton.bam'.format(prefix), bam, it, ss, [bam], names, name_off, level=level, sink=sink,
+                          names_dev=ndev)
+                bs = make_specs(len(bad_rec))
+                bs["kind"] = N.OUT_RAW
+                bs["src_rec"] = bad_rec
+                write_bam('{}.badReads.bam'.format(prefix), bam, it, bs, [bam], level=level, sink=sink)
         self.times["emit_write"] = time.time() - t0
         t0 = time.time()
         items = size_census(fam_sizes)
@@ -350,20 +371,21 @@ class DCSRun(object):
         self.times["emit_fetch"] = time.time() - t0
         t0 = time.time()
         if eng.names_device:
-            names, name_off = eng.dcs_names(bam, self.table, t_rec[made], p_rec[made])
+            names, name_off = eng.dcs_names(bam, self.table, t_rec[made], p_rec[made], keep=eng.names_resident_device)
         else:
             names, name_off = dcs_names(bam, t_rec[made], p_rec[made])
-        self.times["emit_names"] = time.time() - t0
-        t0 = time.time()
-        with _pinned(eng, bam):   # (the source uploaded once for these writes)
-            sp = _new_specs(nm, t_rec[made], np.arange(nm), vslot[made], meta, qstride)
-            write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
-                      cons_group=cgroup)
-            single = dec == 1
-            ss = make_specs(int(single.sum()))
-            ss["kind"] = N.OUT_RAW
-            ss["src_rec"] = t_rec[single]
-            write_bam(singleton_path, bam, it, ss, [bam], level=level, sink=sink)
+        with _kept(eng, names) as (names, ndev):   # (a kept set is freed behind the pinned block)
+            self.times["emit_names"] = time.time() - t0
+            t0 = time.time()
+            with _pinned(eng, bam):   # (the source uploaded once for these writes)
+                sp = _new_specs(nm, t_rec[made], np.arange(nm), vslot[made], meta, qstride)
+                write_bam(outfile, bam, it, sp, [bam], names, name_off, cons_seq, cons_qual, level, sink=sink,
+                          cons_group=cgroup, names_dev=ndev)
+                single = dec == 1
+                ss = make_specs(int(single.sum()))
+                ss["kind"] = N.OUT_RAW
+                ss["src_rec"] = t_rec[single]
+                write_bam(singleton_path, bam, it, ss, [bam], level=level, sink=sink)
         self.times["emit_write"] = time.time() - t0
         t0 = time.time()
         part = dict(counters=c, dcs=nm, sscs_singletons=int(single.sum()))
@@ -495,11 +517,14 @@ class SCRun(object):
             for code, name in ((0, "sscs.correction"), (1, "singleton.correction")):
                 m = dec == code
                 k = int(m.sum())
-                fmt = eng.csn_names if eng.names_device else csn_names
-                names, name_off = fmt(it, q_ckey[m], np.ones(k, np.int64))
+                if eng.names_device:
+                    names, name_off = eng.csn_names(it, q_ckey[m], np.ones(k, np.int64), keep=eng.names_resident_device)
+                else:
+                    names, name_off = csn_names(it, q_ckey[m], np.ones(k, np.int64))
                 sp = _new_specs(k, t_rec[m], np.arange(k), vslot[m], meta, qstride)
-                write_bam('{}.{}.bam'.format(base, name), sbam, it, sp, [sbam], names, name_off, cons_seq, cons_qual,
-                          level, sink=sink, cons_group=cgroup)
+                with _kept(eng, names) as (names, ndev):
+                    write_bam('{}.{}.bam'.format(base, name), sbam, it, sp, [sbam], names, name_off, cons_seq, cons_qual,
+                              level, sink=sink, cons_group=cgroup, names_dev=ndev)
                 outs[name] = k
             m = dec == 2
             us = make_specs(int(m.sum()))

@@ -367,7 +367,12 @@ int ccio_bam_stream(ccio_bam *b, const uint8_t **data, uint64_t *bytes, uint64_t
 /* per value 0..maxv of v[0..n): count and first index (n when absent), one pass (read_families.txt) */
 int ccio_value_census(const int32_t *v, int64_t n, int32_t maxv, int64_t *first, int64_t *count);
 /* (cons_seq and cons_qual both NULL with CC_OUT_NEW specs: only an assemble hook that brings its own
- * consensus arrays can write the file; when it does not, nothing is written and the result is -2) */
+ * consensus arrays can write the file; when it does not, nothing is written and the result is -2.
+ * names NULL means "the names are with the hook" (cc_bam_assemble_names): name_off stays a host array,
+ * from which the hooks' n_names and names_bytes are derived, and the hooks receive names as NULL.  When
+ * no hook takes such a write and a spec of kind RENAME or NEW has name_id >= 0, nothing is written and
+ * the result is -3, "write_bam: names not in host memory"; specs that need no name are written by the
+ * host as always) */
 int ccio_write_bam_ex(const char *path, ccio_bam *tmpl, ccio_interner *it, int64_t n, const cc_out_spec *spec,
                       ccio_bam *const *srcs, int nsrc, const char *names, const int64_t *name_off,
                       const uint8_t *cons_seq, const uint8_t *cons_qual, int level, int nthreads, int flags,
@@ -726,11 +731,21 @@ int cc_out_resident_hooks(cc_ctx *ctx, ccio_out_resident *cb, void **user);
 /* the group whose consensus buffers the hook's next call uses when libccio passes it no arrays (that
  * call consumes it); -1 clears it */
 int cc_bam_assemble_group(cc_ctx *ctx, int32_t group_id);
+/* The name set (cc_names_keep, below) that cc_bam_assemble, cc_bam_assemble_keep and both hooks read in
+ * place of host names from now on; 0 clears it, an unknown id is CC_E_INVALID.  A call uses the set when
+ * its names argument is NULL and names_bytes > 0: the set's blob and device offsets are the names
+ * table, nothing of either is uploaded and the call's name_off is not read.  n_names and names_bytes
+ * must not exceed the set's (else CC_E_INVALID before any launch); without a selected set such a call
+ * is CC_E_INVALID as before.  Unlike cc_bam_assemble_group's, the selection is not consumed: a stage
+ * writes several files from one set, and the caller clears it (cc_names_free of the selected set
+ * clears it too).  With profiling on, cc_kernel_times reports the upload of host names (names_bytes > 0)
+ * as "asm_names_upload"; a call that reads a set never adds to it. */
+int cc_bam_assemble_names(cc_ctx *ctx, int64_t names_id);
 /* The consensus read names formatted on the device (csrc/name_core.h, name_format.hip.inc), byte for
  * byte what ccio_format_csn_names / ccio_format_dcs_names give.  Both take host arrays, write
  * off[n + 1] (name i is bytes [off[i], off[i + 1]) of the blob) and *total (= off[n]), and leave the
- * blob in a device buffer the context owns until cc_names_read fetches it; a new format call or
- * cc_destroy releases a blob nobody read.
+ * blob in a device buffer the context owns until cc_names_read fetches it or cc_names_keep keeps it;
+ * a new format call or cc_destroy releases a blob nobody read.
  *   csn: f9 holds nine int32 fields per name, suffix one int64; the barcode strings (field 0) and the
  *     cigar strings (fields 5, 6) come side by side with n_bc + 1 / n_cg + 1 offsets
  *     (ccio_interner_blob).
@@ -740,7 +755,8 @@ int cc_bam_assemble_group(cc_ctx *ctx, int32_t group_id);
  * outside the table) is CC_E_INVALID, and cc_last_error names the first such name and the reason; a
  * blob of 2^32 bytes or more, or more than 2^31 - 1 names, is CC_E_UNSUPPORTED.  After any error no
  * blob exists and nothing the call allocated stays allocated.  With profiling on, cc_kernel_times
- * reports the kernels as "name_sizes" and "name_write", the offsets' scan as "name_scan". */
+ * reports the kernels as "name_sizes" and "name_write", the offsets' scan as "name_scan", the blob's
+ * download as "name_download" and cc_format_csn_names' upload of f9 and suffix as "name_fields_upload". */
 int cc_format_csn_names(cc_ctx *ctx, int64_t n, const int32_t *f9, const int64_t *suffix, const char *bc_blob,
                         const int64_t *bc_off, int64_t n_bc, const char *cg_blob, const int64_t *cg_off, int64_t n_cg,
                         int64_t *off, int64_t *total);
@@ -749,6 +765,31 @@ int cc_format_dcs_names(cc_ctx *ctx, int32_t table, int64_t n, const int64_t *re
 /* The last formatted blob copied to blob[0, total) and its device buffer released.  cap < total is
  * CC_E_INVALID and keeps the buffer, as does a call without a blob to read. */
 int cc_names_read(cc_ctx *ctx, char *blob, int64_t cap);
+/* cc_format_csn_names with the fields read where the SSCS stage left them: n is the count of group_id's
+ * emit_n, name i takes its nine fields from emit_ckey[9 * (i >> 1)] (an emitted entry's row serves its
+ * two names) and its suffix from emit_n[i].  Only the two string tables are uploaded.  A group that is
+ * unknown, has not run cc_consensus_maker, lacks either buffer, or whose emit_ckey does not hold exactly
+ * one row per two values of emit_n (checked on the host from the buffers' used sizes, before any
+ * launch) is CC_E_INVALID.  Everything else (refusals, limits, cc_last_error texts, profile scopes, the
+ * pending blob) is cc_format_csn_names'. */
+int cc_format_csn_names_group(cc_ctx *ctx, int32_t group_id, const char *bc_blob, const int64_t *bc_off, int64_t n_bc,
+                              const char *cg_blob, const int64_t *cg_off, int64_t n_cg, int64_t *off, int64_t *total);
+/* Name sets: the last formatted blob kept on the device with its 64-bit offsets, for the assembler to
+ * read in place (cc_bam_assemble_names).  The blob is 16-byte aligned and allocated as
+ * align16(total) + 32 bytes with the tail zero, the assembler's read contract.  A context owns its sets
+ * under positive ids that are unique across contexts; an unknown, freed or foreign id is CC_E_INVALID
+ * in every call, and cc_destroy frees what is left.
+ *   cc_names_keep    the pending blob becomes a set (*names_id) without a download and is no longer
+ *                    pending, as after cc_names_read; 0 names or 0 bytes give a valid empty set; without
+ *                    a pending blob CC_E_INVALID and *names_id = 0
+ *   cc_names_fetch   the set's bytes copied to blob[0, total), the set left as it is; returns total
+ *                    (blob NULL: a size query); cap < total is CC_E_INVALID and copies nothing
+ *   cc_names_free    frees a set
+ *   cc_names_count   the live sets (leak checks) */
+int cc_names_keep(cc_ctx *ctx, int64_t *names_id);
+int64_t cc_names_fetch(cc_ctx *ctx, int64_t names_id, char *blob, int64_t cap);
+int cc_names_free(cc_ctx *ctx, int64_t names_id);
+int64_t cc_names_count(cc_ctx *ctx);
 /* cc_table_unpack with the records read in place from a resident stream (cc_bgzf_inflate_keep): they
  * are its bytes [base, base + bytes), which must lie inside it (else CC_E_INVALID), and rec_off counts
  * from base, as ccio_bam_decode_ids gives it.  Checks, errors and the table are cc_table_unpack's;
