@@ -458,13 +458,16 @@ class AlignmentFile(object):
             raise ValueError("invalid contig `%s`" % contig)
         start = 0 if start is None else start
         stop = (1 << 31) - 1 if stop is None else stop
-        for raw in self._raw:
-            (rtid, rpos) = struct.unpack_from("<ii", raw, 4)
-            if rtid != tid or rpos >= stop:
-                continue
-            r = self._decode(raw)
-            if r._endpos() > start:
-                yield r
+        if self._records_cache is None:
+            # (tid, pos, end) per record, once per file: a bed file of many regions fetches many times,
+            # and only the records a region overlaps are decoded (anew each time: callers rename them)
+            self._records_cache = []
+            for raw in self._raw:
+                (rtid, rpos) = struct.unpack_from("<ii", raw, 4)
+                self._records_cache.append((rtid, rpos, self._decode(raw)._endpos()))
+        for raw, (rtid, rpos, rend) in zip(self._raw, self._records_cache):
+            if rtid == tid and rpos < stop and rend > start:
+                yield self._decode(raw)
 
     def __iter__(self):
         return self.fetch(until_eof=True)
