@@ -73,11 +73,12 @@ __global__ __launch_bounds__(ASM_T) void k_asm_sizes(asmb::Tables T, const asmb:
 
 // ssz[i] = the size of output record o0 + i (perm null: spec order)
 __global__ __launch_bounds__(ASM_T) void k_asm_gather(const uint32_t* __restrict__ sz, const uint32_t* __restrict__ perm,
-                                                      int64_t n, int64_t o0, int64_t cnt, uint32_t* __restrict__ ssz) {
+                                                      int64_t n, int64_t o0, int64_t cnt, uint32_t* __restrict__ ssz,
+                                                      AsmStatus* st) {
     const int64_t i = (int64_t)blockIdx.x * ASM_T + threadIdx.x;
     if (i >= cnt) return;
     const int64_t s = perm ? (int64_t)perm[o0 + i] : o0 + i;
-    ssz[i] = sz[CC_IDX(s, n, DS_REC)];
+    ssz[i] = sz[CC_IDXG(s, n, DS_REC, &st->guard)];
 }
 
 // Output records [o0, o0 + cnt): record o0 + i goes to out[base + off32[i] ...).  Every spec was accepted
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(ASM_T) void k_asm_copy(asmb::Tables T, const asmb::
     const int64_t s = perm ? (int64_t)perm[o] : o;
     asmb::Lay y;
     uint64_t k;
-    const uint32_t e = asmb::layout(spec[CC_IDX(s, n, DS_REC)], T, y, &k);
+    const uint32_t e = asmb::layout(spec[CC_IDXG(s, n, DS_REC, &st->guard)], T, y, &k);
     const uint64_t off = base + off32[i];
     if (e || off > total || y.size > total - off || (uint64_t)s >= (uint64_t)n) {   // (containment: never expected)
         if (j == 0) atomicOr(&st->guard, 1u);
@@ -328,7 +329,7 @@ int bam_assemble(cc_ctx* ctx, const AsmArgs& a, const std::vector<const uint8_t*
     uint64_t base = a.header_bytes;
     for (int64_t o0 = 0; o0 < n; o0 += per) {
         const int64_t cnt = std::min(per, n - o0);
-        klaunch(ctx, "k_asm_gather", k_asm_gather, nblk(cnt, ASM_T), ASM_T, sz, perm, n, o0, cnt, ssz);
+        klaunch(ctx, "k_asm_gather", k_asm_gather, nblk(cnt, ASM_T), ASM_T, sz, perm, n, o0, cnt, ssz, d_st);
         RC(scan_launch(ctx, ssz, cnt, &d_st->tot, "asm_scan", ScanStore{off32}));
         klaunch(ctx, "k_asm_copy", k_asm_copy, nblk(cnt, ASM_T / ASM_LANES), ASM_T, T, d_spec, perm, n, o0, cnt, off32, base, sum,
                 d_out, d_at, d_st);

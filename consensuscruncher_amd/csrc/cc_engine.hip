@@ -81,20 +81,26 @@ enum : uint32_t {
     EB_PLAN = 1u << 11,       // a planned capacity was exceeded (the pass re-runs exactly)
     EB_DEEPSORT = 1u << 15,   // a deep family out of end order is too long for k_deep_sortfam: re-run sorted
     EB_SCANWAIT = 1u << 16,   // a single-pass scan's look-back waited past its bound (k_scan_one)
-    EB_GUARD = 1u << 17,      // a guarded index was outside its array (release-build CC_IDX; g_guard)
+    EB_GUARD = 1u << 17,      // a guarded index was outside its array (release-build CC_IDX; the group's guard word)
 };
+
+// A group's error block: [0] the error word, [13] and [14] scratch totals (the vote's items, the sort's
+// scan), [15] the guards' flag (guard_fail).
+constexpr int ERR_WORDS = 16, ERR_GUARD = 15;
 
 // ---- device bounds checks (debug build: -DCC_DEBUG_BOUNDS, libccamd_debug.so) -----------------
 // A checked index outside [0, n) records its site and value in g_dbg_fault (the first one wins) and is
 // replaced by 0, so the kernel goes on reading valid memory; cc_debug_check reports it.
 // The release build guards the same sites (containment): an index outside [0, n) -- a record, slot,
 // member, qname or payload index read from a pooled buffer that a scan or a plan sized, e.g. a slot no
-// kernel of this pass wrote -- sets g_guard and reads index 0 instead of faulting; the pass's end folds
-// g_guard into its error word as EB_GUARD, and a planned pass then re-runs exactly (an exact pass
-// reports CC_E_INVALID).  -DCC_NO_GUARD compiles the guards away (the cost A/B).
-__device__ unsigned int g_guard;
-__device__ __noinline__ int64_t guard_fail() {
-    atomicOr(&g_guard, 1u);
+// kernel of this pass wrote -- sets the guard word of the pass's group and reads index 0 instead of
+// faulting; the pass's end folds the word into its error word as EB_GUARD, and a planned pass then
+// re-runs exactly (an exact pass reports CC_E_INVALID).  The word is reached through the kernel's
+// arguments: CC_IDX through the DevTable `T` in scope (T.guard, set when the call binds its group),
+// CC_IDXG through the pointer given.  Passes that overlap on two lanes never share one.
+// -DCC_NO_GUARD compiles the guards away (the cost A/B).
+__device__ __noinline__ int64_t guard_fail(unsigned int* guard) {
+    if (guard) atomicOr(guard, 1u);
     return 0;
 }
 #ifdef CC_DEBUG_BOUNDS
@@ -106,15 +112,16 @@ __device__ __noinline__ int64_t dbg_fail(int site, int64_t i) {
 __device__ __forceinline__ int64_t dbg_idx(int64_t i, int64_t n, int site) {
     return (i < 0 || i >= n) ? dbg_fail(site, i) : i;
 }
-#define CC_IDX(i, n, site) ((std::remove_cv_t<std::remove_reference_t<decltype(i)>>)dbg_idx((int64_t)(i), (int64_t)(n), (site)))
+#define CC_IDXG(i, n, site, guard) ((std::remove_cv_t<std::remove_reference_t<decltype(i)>>)dbg_idx((int64_t)(i), (int64_t)(n), (site)))
 #elif defined(CC_NO_GUARD)
-#define CC_IDX(i, n, site) (i)
+#define CC_IDXG(i, n, site, guard) (i)
 #else
-__device__ __forceinline__ int64_t guard_idx(int64_t i, int64_t n) {
-    return (uint64_t)i < (uint64_t)n ? i : guard_fail();
+__device__ __forceinline__ int64_t guard_idx(int64_t i, int64_t n, unsigned int* guard) {
+    return (uint64_t)i < (uint64_t)n ? i : guard_fail(guard);
 }
-#define CC_IDX(i, n, site) ((std::remove_cv_t<std::remove_reference_t<decltype(i)>>)guard_idx((int64_t)(i), (int64_t)(n)))
+#define CC_IDXG(i, n, site, guard) ((std::remove_cv_t<std::remove_reference_t<decltype(i)>>)guard_idx((int64_t)(i), (int64_t)(n), (guard)))
 #endif
+#define CC_IDX(i, n, site) CC_IDXG(i, n, site, T.guard)
 enum : int {   // bounds-check sites (cc_debug_check's message)
     DS_REC = 1, DS_QNAME = 2, DS_PAYLOAD = 3, DS_SLOT = 4, DS_PAIR = 5, DS_MEMBER = 6, DS_VOTE_REC = 7,
 };
@@ -159,6 +166,7 @@ struct DevTable {
     uint4* meta;         // per record the vote's 16-B member record without the valid bit (pack_meta)
     uint64_t* rkey;      // per record its position key (pos_key; position groups, mate search)
     uint32_t* ebits;     // error bits of the table's columns (EB_TOO_LONG), ORed into every pass's word
+    uint32_t* guard;     // the guard word of the group whose call is running (set when the call binds it)
     uint8_t* rdeep;      // per record 1 when its position group holds more than GRP_SMALL records (k_derive)
     int32_t* dlist;      // sorted tables: the first records of the deep position groups (k_derive, any order)
     uint32_t* ndeep;     // their count (device) ...
@@ -2750,7 +2758,7 @@ __global__ __launch_bounds__(256) void k_fam_build(int64_t F, int64_t R, int64_t
         fam_o[f] = 0x7f7f7f7f;   // orphan tags are never processed (k_entries_build sets the others)
         int32_t b = CC_IDX(fam_beg[f], R, DS_SLOT);
         int32_t e = (f + 1 < F) ? fam_beg[f + 1] : (int32_t)R;
-        if (e < b || e > R) e = b + (int32_t)guard_fail() + 1;   // (a stale start: guarded)
+        if (e < b || e > R) e = b + (int32_t)guard_fail(T.guard) + 1;   // (a stale start: guarded)
         fam_end[f] = e;
         fam_n[f] = e - b - fam_drop[f];   // len(read_dict[tag]): members not dropped
         uint32_t fe = rs_val[b];
@@ -3524,14 +3532,14 @@ __global__ __launch_bounds__(256) void k_vote_plan(
         int2 sp = emit_span[o];
         // a vote slot past the planned capacity (a flag no kernel of this pass wrote): guarded
         const bool over = need && (int64_t)vxo >= nvcap;
-        if (over) guard_fail();
+        if (over) guard_fail(T.guard);
         if (!need || over) {
             emit_vslot[o] = -1;
         } else {
             const int32_t v = (int32_t)vxo;
             vote_fam[v] = f;
             emit_vslot[o] = v;
-            if (sp.x < 0 || sp.y < 0 || (int64_t)sp.x + sp.y > nmem) sp = make_int2((int32_t)guard_fail(), 0);
+            if (sp.x < 0 || sp.y < 0 || (int64_t)sp.x + sp.y > nmem) sp = make_int2((int32_t)guard_fail(T.guard), 0);
             const int32_t beg = sp.x, cnt = sp.y;
             const uint4* fm = mem_meta + beg;
             const uint4 m0 = cnt > 0 ? fm[0] : make_uint4(0u, 0u, 0u, 0u);
@@ -3623,7 +3631,7 @@ __global__ __launch_bounds__(256) void k_vote_plan(
     if (key >= 0) {
         const int64_t at = s_vb + atomicAdd(&s_cur[key], 1u);
         if (at < nvcap) vote_order[at] = rec;
-        else guard_fail();
+        else guard_fail(T.guard);
     }
 }
 
@@ -3751,7 +3759,7 @@ __global__ __launch_bounds__(256, CC_SV_WAVES) void k_sscs_vote_swar(
         const int4 vi = vote_order[t];                  // {first member, members, L, vote slot}
         beg = vi.x; cnt = vi.y; L = vi.z; v = vi.w;
         if (beg < 0 || cnt < 0 || (int64_t)beg + cnt > nmem || v < 0 || v >= nv) {   // (a stale slot: guarded)
-            beg = (int32_t)guard_fail();
+            beg = (int32_t)guard_fail(T.guard);
             cnt = 0;
         }
     }
@@ -4523,12 +4531,12 @@ __global__ __launch_bounds__(256) void k_duplex_vote_swar(
     uint32_t eb = 0;
     if (g < fpw && w < nv) {
         const int4 vp = vpair[w];   // {read1 record, read2 record, decision, entry} (EmitVotePairs)
-        const int32_t a = CC_IDX(vp.x, TA.n, DS_VOTE_REC), b = vp.y;
+        const int32_t a = CC_IDXG(vp.x, TA.n, DS_VOTE_REC, TA.guard), b = vp.y;
         // SC: a complement found among the singletons (dec 1) lives in the singleton table
         const bool b_in_a = sc && vp.z == 1;
         const DevTable& TBx = b_in_a ? TA : TB;
         const uint8_t* bpay = TBx.payload;
-        const uint4 ma = TA.meta[a], mb = TBx.meta[CC_IDX(b, TBx.n, DS_VOTE_REC)];   // pay16, tlen, lseq | qlen << 16, flag | mapq | rflags | rg7
+        const uint4 ma = TA.meta[a], mb = TBx.meta[CC_IDXG(b, TBx.n, DS_VOTE_REC, TA.guard)];   // pay16, tlen, lseq | qlen << 16, flag | mapq | rflags | rg7
         const int32_t la = (int32_t)(ma.z & 0xffffu), lb = (int32_t)(mb.z & 0xffffu);
         int32_t L = la;                                                      // read1.query_length
         if (lb < L) { eb |= EB_SHORT; L = 0; }
@@ -5134,9 +5142,9 @@ __device__ __forceinline__ uint32_t stripe_sum(const uint32_t* __restrict__ stri
 
 // the guards' flag into the pass's error word (and cleared for the next pass)
 __global__ __launch_bounds__(64) void k_guard_fold(uint32_t* __restrict__ err) {
-    if (threadIdx.x == 0 && g_guard) {
+    if (threadIdx.x == 0 && err[ERR_GUARD]) {
         atomicOr(err, EB_GUARD);
-        g_guard = 0u;
+        err[ERR_GUARD] = 0u;
     }
 }
 __global__ __launch_bounds__(256) void k_defer_pack(const uint32_t* __restrict__ err,
@@ -5145,8 +5153,9 @@ __global__ __launch_bounds__(256) void k_defer_pack(const uint32_t* __restrict__
                                                     const uint32_t* __restrict__ stripes, uint8_t* __restrict__ h) {
     const int t = threadIdx.x;
     if (t == 0) {
-        *reinterpret_cast<uint32_t*>(h) = *err | (g_guard ? EB_GUARD : 0u);
-        if (g_guard) g_guard = 0u;
+        uint32_t* guard = const_cast<uint32_t*>(err) + ERR_GUARD;
+        *reinterpret_cast<uint32_t*>(h) = *err | (*guard ? EB_GUARD : 0u);
+        if (*guard) *guard = 0u;
     }
     if (cnt && t < CC_NUM_COUNTERS) {
         unsigned long long v = 0;
@@ -5328,11 +5337,26 @@ constexpr const char* PLAN_NAME[] = {
 constexpr int PLAN_SLOTS = 64;
 static_assert((int)PT::COUNT <= PLAN_SLOTS, "a planned total's slot is its id");
 
+// The last call that touched a group or a table (read or wrote it), as an event on that call's lane:
+// a call on another lane waits for it before its own work (pass_enter); -1: none outstanding.
+struct Touch {
+    hipEvent_t ev = nullptr;
+    int lane = -1;
+};
+constexpr int CC_MAX_LANES = 4;
+
 enum Stage { ST_READ_BAM, ST_SSCS, ST_DCS, ST_SC, ST_COUNT };   // the stages run_planned runs
 constexpr const char* STAGE_NAME[ST_COUNT] = {"read_bam", "sscs", "dcs", "sc"};
 
 struct Group {
     int32_t table = -1;
+    int lane = 0;                   // its lane (round-robin at creation; taken modulo the lanes in use)
+    Touch touch;
+    uint32_t* d_err = nullptr;      // its error block (ERR_WORDS words), zeroed and judged per pass
+    unsigned long long* d_cnt = nullptr;   // its striped counters
+    int64_t reruns = 0;             // its planned passes re-run exactly (a plan that did not hold; cc_group_reruns)
+    int64_t guard_reruns = 0;       // ... of them after a guarded index (EB_GUARD)
+    int64_t lane_waits = 0;         // events of other lanes its calls made their lane wait for
     int64_t S = 0, P = 0, R = 0, F = 0, E = 0, Q = 0, NV = 0;
     uint64_t seed = 0;
     int scoped = 0, delim_filter = 0, badread = 0;
@@ -5419,6 +5443,7 @@ struct EngineSwitches {
     bool gr_by_pair = false;       // CC_GR_BY_PAIR: the group ranking compares tags through the pairs
     bool deep_sort = false;        // CC_DEEP_SORT: deep position groups ranked by the sort, not in place
     bool trace_upload = false;     // CC_TRACE_UPLOAD: one stderr line per uploaded table
+    int lanes = CC_MAX_LANES;      // CC_LANES=1..4: streams the groups' passes are spread over (1: one stream)
 };
 
 EngineSwitches read_switches() {
@@ -5438,6 +5463,7 @@ EngineSwitches read_switches() {
     sw.gr_by_pair = getenv("CC_GR_BY_PAIR") != nullptr;
     sw.deep_sort = getenv("CC_DEEP_SORT") != nullptr;
     sw.trace_upload = getenv("CC_TRACE_UPLOAD") != nullptr;
+    if (const char* v = getenv("CC_LANES")) sw.lanes = std::min(std::max(atoi(v), 1), CC_MAX_LANES);
     return sw;
 }
 
@@ -5454,29 +5480,47 @@ struct NameSet {
     int64_t n = 0, total = 0;
 };
 
-struct cc_ctx {
-    int device = 0;
+// A lane: one stream and what the work enqueued on it shares between launches (the scans' partials and
+// look-back states, the sort's buffer, the pinned words of scalar readbacks).  A group's passes all run
+// on its lane, so these are never shared by passes that overlap.
+struct Lane {
     hipStream_t stream = nullptr;
-    std::string err;
-    EngineSwitches sw;              // as the entry point now running read them (enter), not kept across calls
-    std::map<int32_t, DevTable> tables;
-    std::map<int32_t, std::vector<void*>> table_allocs;
-    std::map<int32_t, std::unique_ptr<Group>> groups;
-    int32_t next_id = 1;
     DevBuf tmp;                     // the scans' tile partials
     DevBuf sort_buf;                // sort_pairs' ping-pong pairs and digit counts
     unsigned long long* scan_st = nullptr;   // k_scan_one's tile states (zeroed when allocated)
     uint32_t* scan_ticket = nullptr;
     int64_t scan_cap = 0;
     uint32_t scan_epoch = 0;
+    void* h_pinned = nullptr;       // small pinned scratch for scalar readbacks
+};
+
+struct cc_ctx {
+    int device = 0;
+    // The running call's lane and error block (enter / pass_enter bind them): every launch, fill, copy
+    // and memset of the call goes to `stream`, every kernel's err / cnt argument is d_err / d_cnt.
+    Lane lanes[CC_MAX_LANES];
+    Lane* lane = nullptr;
+    hipStream_t stream = nullptr;
+    int n_lanes = 1;                // lanes in use by the last call (a change waits for every lane)
+    int next_lane = 0;              // round-robin of new groups
+    bool loose = false;             // a call outside the passes may have left work on lane 0 since loose_ev
+    hipEvent_t loose_ev = nullptr;  // lane 0 after such calls; loose_wait: the lanes that have not waited for it yet
+    bool loose_wait[CC_MAX_LANES] = {false, false, false, false};
+    std::map<int32_t, Touch> table_touch;
+    std::string err;
+    EngineSwitches sw;              // as the entry point now running read them (enter), not kept across calls
+    std::map<int32_t, DevTable> tables;
+    std::map<int32_t, std::vector<void*>> table_allocs;
+    std::map<int32_t, std::unique_ptr<Group>> groups;
+    int32_t next_id = 1;
     uint32_t scan_spin_max = 1u << 22;   // k_scan_one's look-back polls of one state (CC_SCAN_SPIN_MAX)
     bool scan_two = false;          // every scan as reduce-then-scan (the re-run after EB_SCANWAIT)
     std::unordered_set<int32_t> full_qhash;   // tables whose qname digests collided: full seeded hash
     int64_t scan_retries = 0;       // passes re-run after EB_SCANWAIT
     int64_t guard_reruns = 0;       // planned passes re-run after a guarded index (EB_GUARD)
-    uint32_t* d_err = nullptr;      // device error word
+    uint32_t* d_err = nullptr;      // the bound group's error block and counters
     unsigned long long* d_cnt = nullptr;
-    void* h_pinned = nullptr;       // small pinned scratch for scalar readbacks
+    void* h_pinned = nullptr;       // the bound lane's pinned scratch
     std::atomic<bool> profiling{false};   // (the BGZF encoder reads it from the writers' threads)
     std::unordered_set<std::string> prof_only;   // when non-empty, the only scopes timed
     struct Prof { double ms = 0; int64_t n = 0; };
@@ -5518,10 +5562,122 @@ namespace {
 
 // The prologue of every entry point that enqueues work: the context's device made current and the
 // engine switches read (per call: a test changes them between runs on one live engine).
+// The lanes a call may use: the switch, or one while every scope is timed (a scope's events then
+// bracket its own kernels only).  A change of the count waits for every lane first, so that work
+// enqueued under the old count is ordered before the new one's.
+int wait_lanes(cc_ctx* ctx) {
+    for (Lane& l : ctx->lanes) HIPCHK(hipStreamSynchronize(l.stream));
+    return 0;
+}
+int lanes_in_use(cc_ctx* ctx) {
+    const int n = ctx->profiling && ctx->prof_only.empty() ? 1 : ctx->sw.lanes;
+    if (n != ctx->n_lanes) {
+        RC(wait_lanes(ctx));
+        ctx->n_lanes = n;
+    }
+    return 0;
+}
+void bind(cc_ctx* ctx, int lane, Group& g) {
+    ctx->lane = &ctx->lanes[lane];
+    ctx->stream = ctx->lane->stream;
+    ctx->h_pinned = ctx->lane->h_pinned;
+    ctx->d_err = g.d_err;
+    ctx->d_cnt = g.d_cnt;
+    // the guards of every kernel launched from here on report to g (tables go to kernels by value)
+    for (auto& t : ctx->tables) t.second.guard = g.d_err + ERR_GUARD;
+}
+// Entry points outside the stage passes (uploads, fetches, the function-level calls, the test hooks,
+// the output paths): they may read any group or table, so they wait for every lane, then run on
+// lane 0 with the scratch group's error block.
 int enter(cc_ctx* ctx) {
     HIPCHK(hipSetDevice(ctx->device));
     ctx->sw = read_switches();
+    RC(lanes_in_use(ctx));
+    if (ctx->n_lanes > 1) RC(wait_lanes(ctx));
+    bind(ctx, 0, *ctx->scratch);
+    ctx->loose = true;
     return 0;
+}
+
+// A stage pass's entry (cc_read_bam and its re-run, cc_consensus_maker, cc_duplex_consensus,
+// cc_singleton_correction): bound to the lane of the group it writes.  Its lane first waits for the
+// last call on another lane that touched what this one touches -- its group, the group it joins
+// (`other`) and their tables; when the call ends, its own end is recorded as their last touch.
+// Work that calls outside the passes left on lane 0 (they record no touch) is ordered before the
+// next pass of every other lane by an event on lane 0.  Nothing here waits on the host.
+struct PassScope {
+    cc_ctx* ctx = nullptr;
+    int lane = 0;
+    Touch* t[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~PassScope() {
+        if (!ctx || ctx->n_lanes <= 1) return;
+        for (Touch* x : t) {
+            if (!x) continue;
+            if (!x->ev && hipEventCreateWithFlags(&x->ev, hipEventDisableTiming) != hipSuccess) {
+                // no event to wait on: the lane itself is waited for, and nothing is outstanding
+                (void)hipStreamSynchronize(ctx->lanes[lane].stream);
+                x->ev = nullptr;
+                x->lane = -1;
+                continue;
+            }
+            (void)hipEventRecord(x->ev, ctx->lanes[lane].stream);
+            x->lane = lane;
+        }
+    }
+};
+int pass_enter(cc_ctx* ctx, PassScope& ps, Group& g, Group* other) {
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->sw = read_switches();
+    RC(lanes_in_use(ctx));
+    const int lane = g.lane % ctx->n_lanes;
+    if (ctx->loose && ctx->n_lanes > 1) {
+        if (!ctx->loose_ev) HIPCHK(hipEventCreateWithFlags(&ctx->loose_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ctx->loose_ev, ctx->lanes[0].stream));
+        for (int l = 1; l < CC_MAX_LANES; ++l) ctx->loose_wait[l] = true;
+    }
+    ctx->loose = false;
+    bind(ctx, lane, g);
+    if (ctx->loose_wait[lane]) {
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->loose_ev, 0));
+        ctx->loose_wait[lane] = false;
+    }
+    ps.ctx = ctx;
+    ps.lane = lane;
+    ps.t[0] = &g.touch;
+    ps.t[1] = &ctx->table_touch[g.table];
+    if (other && other != &g) {
+        ps.t[2] = &other->touch;
+        if (other->table != g.table) ps.t[3] = &ctx->table_touch[other->table];
+    }
+    for (Touch* x : ps.t)
+        if (x && x->ev && x->lane >= 0 && x->lane != lane) {
+            HIPCHK(hipStreamWaitEvent(ctx->stream, x->ev, 0));
+            ++g.lane_waits;
+        }
+    return 0;
+}
+
+// a group with its error block and counters (zeroed); null with ctx->err set when the allocation failed
+Group* new_group(cc_ctx* ctx) {
+    std::unique_ptr<Group> g(new Group());
+    const size_t cb = sizeof(unsigned long long) * CC_NUM_COUNTERS * CNT_STRIPES;
+    if (hipMalloc((void**)&g->d_err, sizeof(uint32_t) * ERR_WORDS) != hipSuccess ||
+        hipMalloc((void**)&g->d_cnt, cb) != hipSuccess ||
+        hipMemset(g->d_err, 0, sizeof(uint32_t) * ERR_WORDS) != hipSuccess || hipMemset(g->d_cnt, 0, cb) != hipSuccess) {
+        if (g->d_err) (void)hipFree(g->d_err);
+        if (g->d_cnt) (void)hipFree(g->d_cnt);
+        ctx->err = "hipMalloc failed for a group's error block";
+        return nullptr;
+    }
+    g->lane = ctx->next_lane++ % CC_MAX_LANES;
+    return g.release();
+}
+void free_group(Group& g) {
+    for (DevBuf& b : g.buf)
+        if (b.p) (void)hipFree(b.p);
+    if (g.d_err) (void)hipFree(g.d_err);
+    if (g.d_cnt) (void)hipFree(g.d_cnt);
+    if (g.touch.ev) (void)hipEventDestroy(g.touch.ev);
 }
 
 inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
@@ -5585,19 +5741,19 @@ BufT<id>* gbuf(cc_ctx* ctx, Group& g, int64_t count, int* rc) {
 }
 
 void* tmp_storage(cc_ctx* ctx, size_t bytes, int* rc) {
-    if (ctx->tmp.bytes < bytes) {
-        if (ctx->tmp.p) (void)hipFree(ctx->tmp.p);
-        ctx->tmp.p = nullptr;
+    if (ctx->lane->tmp.bytes < bytes) {
+        if (ctx->lane->tmp.p) (void)hipFree(ctx->lane->tmp.p);
+        ctx->lane->tmp.p = nullptr;
         size_t nb = bytes + bytes / 4 + 4096;
-        if (hipMalloc(&ctx->tmp.p, nb) != hipSuccess) {
+        if (hipMalloc(&ctx->lane->tmp.p, nb) != hipSuccess) {
             ctx->err = "hipMalloc temp storage failed";
             *rc = CC_E_HIP;
-            ctx->tmp.bytes = 0;
+            ctx->lane->tmp.bytes = 0;
             return nullptr;
         }
-        ctx->tmp.bytes = nb;
+        ctx->lane->tmp.bytes = nb;
     }
-    return ctx->tmp.p;
+    return ctx->lane->tmp.p;
 }
 
 struct ProfScope {
@@ -5639,7 +5795,7 @@ inline void klaunch(cc_ctx* ctx, const char* scope, void (*kernel)(P...), dim3 g
 
 void flush_prof(cc_ctx* ctx) {
     if (ctx->pending.empty()) return;
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)wait_lanes(ctx);   // (scope events are recorded on the launching lane)
     for (auto& p : ctx->pending) {
         float ms = 0;
         (void)hipEventElapsedTime(&ms, p.second.first, p.second.second);
@@ -5669,18 +5825,18 @@ int sort_pairs(cc_ctx* ctx, const uint64_t* kin, uint64_t* kout, const uint32_t*
     const int passes = end_bit > begin_bit ? (int)((end_bit - begin_bit + 7) / 8) : 0;
     const int64_t nt = (n + RS_TILE - 1) / RS_TILE;
     const size_t need = (size_t)n * 12 + 2 * sizeof(uint32_t) * (size_t)RS_BINS * (size_t)nt + 256;
-    if (ctx->sort_buf.bytes < need) {
-        if (ctx->sort_buf.p) {
+    if (ctx->lane->sort_buf.bytes < need) {
+        if (ctx->lane->sort_buf.p) {
             HIPCHK(hipStreamSynchronize(ctx->stream));   // earlier sorts may still use it
-            (void)hipFree(ctx->sort_buf.p);
+            (void)hipFree(ctx->lane->sort_buf.p);
         }
-        ctx->sort_buf.p = nullptr;
-        ctx->sort_buf.bytes = 0;
+        ctx->lane->sort_buf.p = nullptr;
+        ctx->lane->sort_buf.bytes = 0;
         const size_t nb = need + need / 4;
-        HIPCHK(hipMalloc(&ctx->sort_buf.p, nb));
-        ctx->sort_buf.bytes = nb;
+        HIPCHK(hipMalloc(&ctx->lane->sort_buf.p, nb));
+        ctx->lane->sort_buf.bytes = nb;
     }
-    uint8_t* sb = (uint8_t*)ctx->sort_buf.p;
+    uint8_t* sb = (uint8_t*)ctx->lane->sort_buf.p;
     uint64_t* tk = (uint64_t*)sb;
     uint32_t* tv = (uint32_t*)(sb + (size_t)n * 8);
     uint32_t* hist = (uint32_t*)(sb + (((size_t)n * 12 + 127) & ~(size_t)127));
@@ -5723,25 +5879,25 @@ int scan_launch(cc_ctx* ctx, const TIn* in, int64_t n, uint32_t* d_tot, const ch
     if (al & 15u) { ctx->err = "scan operands must be 16-B aligned"; return CC_E_INVALID; }
     const bool one = !ctx->scan_two && (ctx->sw.scan1 >= 0 ? ctx->sw.scan1 == 1 : nb <= SCAN_ONE_MAX);
     if (one && nb > 0) {
-        if (nb > ctx->scan_cap) {
+        if (nb > ctx->lane->scan_cap) {
             const int64_t cap = std::max<int64_t>(nb, 1 << 14);
-            if (ctx->scan_st) {
+            if (ctx->lane->scan_st) {
                 HIPCHK(hipStreamSynchronize(ctx->stream));   // earlier scans may still read the states
-                (void)hipFree(ctx->scan_st);
+                (void)hipFree(ctx->lane->scan_st);
             }
-            ctx->scan_st = nullptr;
-            ctx->scan_cap = 0;
-            HIPCHK(hipMalloc((void**)&ctx->scan_st, sizeof(unsigned long long) * cap + 64));
-            HIPCHK(hipMemsetAsync(ctx->scan_st, 0, sizeof(unsigned long long) * cap + 64, ctx->stream));
-            ctx->scan_ticket = reinterpret_cast<uint32_t*>(ctx->scan_st + cap);   // (zeroed with the states)
-            ctx->scan_cap = cap;
-            ctx->scan_epoch = 0;
+            ctx->lane->scan_st = nullptr;
+            ctx->lane->scan_cap = 0;
+            HIPCHK(hipMalloc((void**)&ctx->lane->scan_st, sizeof(unsigned long long) * cap + 64));
+            HIPCHK(hipMemsetAsync(ctx->lane->scan_st, 0, sizeof(unsigned long long) * cap + 64, ctx->stream));
+            ctx->lane->scan_ticket = reinterpret_cast<uint32_t*>(ctx->lane->scan_st + cap);   // (zeroed with the states)
+            ctx->lane->scan_cap = cap;
+            ctx->lane->scan_epoch = 0;
         }
-        if (++ctx->scan_epoch >= (1u << 30)) {   // epochs exhausted: clear the states and restart
-            HIPCHK(hipMemsetAsync(ctx->scan_st, 0, sizeof(unsigned long long) * ctx->scan_cap, ctx->stream));
-            ctx->scan_epoch = 1;
+        if (++ctx->lane->scan_epoch >= (1u << 30)) {   // epochs exhausted: clear the states and restart
+            HIPCHK(hipMemsetAsync(ctx->lane->scan_st, 0, sizeof(unsigned long long) * ctx->lane->scan_cap, ctx->stream));
+            ctx->lane->scan_epoch = 1;
         }
-        const ScanLB lb{ctx->scan_st, ctx->scan_ticket, ctx->scan_epoch, ctx->d_err, ctx->scan_spin_max};
+        const ScanLB lb{ctx->lane->scan_st, ctx->lane->scan_ticket, ctx->lane->scan_epoch, ctx->d_err, ctx->scan_spin_max};
         klaunch(ctx, name, k_scan_one<Emit, TIn>, (unsigned)nb, SCAN_T, in, n, nb, d_tot, em, lb);
         return 0;
     }
@@ -5900,7 +6056,10 @@ int finish_pass(cc_ctx* ctx, Group& g, uint32_t* bits, bool counters, bool* plan
     HIPCHK(stream_wait(ctx));
     RC(dbg_fault(ctx));
     *bits = *(uint32_t*)(h + 16);
-    if ((*bits & EB_GUARD) && g.fast) ++ctx->guard_reruns;
+    if ((*bits & EB_GUARD) && g.fast) {
+        ++ctx->guard_reruns;
+        ++g.guard_reruns;
+    }
     // a guarded index outside its array in a planned pass: a plan that did not hold (re-run exactly)
     const bool cap_over = (*bits & EB_PLAN) != 0 || (g.fast && (*bits & EB_GUARD) != 0);
     *bits &= g.fast ? ~(EB_PLAN | EB_GUARD) : ~EB_PLAN;
@@ -5932,6 +6091,7 @@ int run_planned(cc_ctx* ctx, Group& g, Stage stage, Pass pass) {
         g.fast = false;
     }
     if (rc == CC_E_PLAN) {
+        if (g.planned[stage]) ++g.reruns;   // (a planned pass that did not hold, not a first pass)
         g.verify.clear();
         rc = pass();
     }
@@ -6161,10 +6321,16 @@ int cc_create(int device_id, cc_ctx** out) {
     cc_ctx* ctx = c.get();
     ctx->device = device_id;
     HIPCHK(hipSetDevice(device_id));
-    HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc((void**)&ctx->d_err, 64));
-    HIPCHK(hipMalloc((void**)&ctx->d_cnt, sizeof(unsigned long long) * CC_NUM_COUNTERS * CNT_STRIPES));
-    HIPCHK(hipHostMalloc(&ctx->h_pinned, 1024 + sizeof(unsigned long long) * CC_NUM_COUNTERS * CNT_STRIPES));
+    // a fixed set of lanes (never sized from the environment's queue count)
+    for (Lane& l : ctx->lanes) {
+        HIPCHK(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
+        HIPCHK(hipHostMalloc(&l.h_pinned, 1024 + sizeof(unsigned long long) * CC_NUM_COUNTERS * CNT_STRIPES));
+    }
+    ctx->scratch.reset(new_group(ctx));   // (before any group: the scratch group is not part of the round-robin)
+    if (!ctx->scratch) return CC_E_HIP;
+    ctx->next_lane = 0;
+    ctx->scratch->lane = 0;
+    bind(ctx, 0, *ctx->scratch);
     if (const char* sm = getenv("CC_SCAN_SPIN_MAX")) ctx->scan_spin_max = (uint32_t)strtoul(sm, nullptr, 10);
     *out = c.release();
     return 0;
@@ -6173,19 +6339,14 @@ int cc_create(int device_id, cc_ctx** out) {
 int cc_destroy(cc_ctx* ctx) {
     if (!ctx) return CC_E_INVALID;
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)wait_lanes(ctx);
     bgzf_free(ctx);
-    for (auto& g : ctx->groups)
-        for (DevBuf& b : g.second->buf)
-            if (b.p) (void)hipFree(b.p);
+    for (auto& g : ctx->groups) free_group(*g.second);
     for (auto& t : ctx->table_allocs)
         for (void* p : t.second) (void)hipFree(p);
-    if (ctx->scratch)
-        for (DevBuf& b : ctx->scratch->buf)
-            if (b.p) (void)hipFree(b.p);
-    if (ctx->tmp.p) (void)hipFree(ctx->tmp.p);
-    if (ctx->sort_buf.p) (void)hipFree(ctx->sort_buf.p);
-    if (ctx->scan_st) (void)hipFree(ctx->scan_st);
+    for (auto& t : ctx->table_touch)
+        if (t.second.ev) (void)hipEventDestroy(t.second.ev);
+    if (ctx->scratch) free_group(*ctx->scratch);
     if (ctx->names_buf) (void)hipFree(ctx->names_buf);
     if (ctx->names_off) (void)hipFree(ctx->names_off);
     for (auto& s : ctx->name_sets) {
@@ -6194,11 +6355,15 @@ int cc_destroy(cc_ctx* ctx) {
     }
     flush_prof(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-    (void)hipFree(ctx->d_err);
-    (void)hipFree(ctx->d_cnt);
-    (void)hipHostFree(ctx->h_pinned);
     if (ctx->h_defer) (void)hipHostFree(ctx->h_defer);
-    (void)hipStreamDestroy(ctx->stream);
+    if (ctx->loose_ev) (void)hipEventDestroy(ctx->loose_ev);
+    for (Lane& l : ctx->lanes) {
+        if (l.tmp.p) (void)hipFree(l.tmp.p);
+        if (l.sort_buf.p) (void)hipFree(l.sort_buf.p);
+        if (l.scan_st) (void)hipFree(l.scan_st);
+        if (l.h_pinned) (void)hipHostFree(l.h_pinned);
+        if (l.stream) (void)hipStreamDestroy(l.stream);
+    }
     delete ctx;
     return 0;
 }
@@ -6311,7 +6476,11 @@ int cc_defer(cc_ctx* ctx, int on) {
 int cc_commit(cc_ctx* ctx) {
     if (!ctx) return CC_E_INVALID;
     if (ctx->deferred.empty()) return 0;
-    HIPCHK(stream_wait(ctx));
+    for (Lane& l : ctx->lanes) {   // every lane a deferred pass ran on (polled: see stream_wait)
+        ctx->stream = l.stream;
+        HIPCHK(stream_wait(ctx));
+    }
+    ctx->stream = ctx->lane->stream;
     if (const int rc = dbg_fault(ctx)) { ctx->deferred.clear(); return rc; }
     bool ok = true;
     for (const DeferredCheck& d : ctx->deferred) {
@@ -6489,7 +6658,7 @@ int cc_debug_sort_pairs(cc_ctx* ctx, int32_t engine, const uint64_t* keys, const
 
 int cc_synchronize(cc_ctx* ctx) {
     if (!ctx) return CC_E_INVALID;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    RC(wait_lanes(ctx));
     flush_prof(ctx);
     return dbg_fault(ctx);
 }
@@ -6505,6 +6674,15 @@ int cc_debug_build(void) {
 int64_t cc_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }
 
 int64_t cc_guard_reruns(cc_ctx* ctx) { return ctx ? ctx->guard_reruns : CC_E_INVALID; }
+
+int cc_group_reruns(cc_ctx* ctx, int32_t group_id, int64_t* out) {
+    if (!ctx || !out || !ctx->groups.count(group_id)) return CC_E_INVALID;
+    const Group& g = *ctx->groups[group_id];
+    out[0] = g.reruns;
+    out[1] = g.guard_reruns;
+    out[2] = g.lane_waits;
+    return 0;
+}
 
 }  // extern "C"
 namespace {
@@ -6535,9 +6713,13 @@ extern "C" {
 int cc_table_derive(cc_ctx* ctx, int32_t table_id) {
     if (!ctx || !ctx->tables.count(table_id)) return CC_E_INVALID;
     if (ctx->tables[table_id].host_layout) return 0;   // its derived columns are part of its input
-    RC(enter(ctx));
-    if (ctx->sw.derive_separate) return derive_table(ctx, ctx->tables[table_id]);
-    ctx->tables[table_id].derive_pending = true;   // (built by the next read_bam pass on the table)
+    // (no wait for the lanes here: a step's passes go on overlapping across its derive calls)
+    ctx->sw = read_switches();
+    if (ctx->sw.derive_separate) {
+        RC(enter(ctx));
+        return derive_table(ctx, ctx->tables[table_id]);
+    }
+    ctx->tables[table_id].derive_pending = true;   // (built by the next read_bam pass on the table: no work here)
     return 0;
 }
 
@@ -6547,6 +6729,7 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
     int32_t id = ctx->next_id++;
     std::vector<void*>& al = ctx->table_allocs[id];
     DevTable T;
+    T.guard = ctx->d_err + ERR_GUARD;
     T.n = r->n;
     T.max_len = max_len;
     RC(upload(ctx, al, &T.tid, r->tid, r->n));
@@ -6677,10 +6860,12 @@ extern "C" {
 
 int cc_table_free(cc_ctx* ctx, int32_t id) {
     if (!ctx || !ctx->tables.count(id)) return CC_E_INVALID;
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)wait_lanes(ctx);   // a pass on any lane may still read it
     for (void* p : ctx->table_allocs[id]) (void)hipFree(p);
     ctx->table_allocs.erase(id);
     ctx->tables.erase(id);
+    if (ctx->table_touch.count(id) && ctx->table_touch[id].ev) (void)hipEventDestroy(ctx->table_touch[id].ev);
+    ctx->table_touch.erase(id);
     return 0;
 }
 
@@ -7510,11 +7695,21 @@ extern "C" {
 int cc_read_bam(cc_ctx* ctx, int32_t table_id, int64_t S, const int32_t* stream_rec, const int32_t* stream_region,
                 int32_t n_regions, const int32_t* region_run, const cc_read_bam_params* prm, int32_t* group_id) {
     if (!ctx || !prm || !group_id || !ctx->tables.count(table_id) || S < 0 || S >= INT32_MAX / 2) return CC_E_INVALID;
-    RC(enter(ctx));
+    HIPCHK(hipSetDevice(ctx->device));   // (before the group's allocations)
+    Group* ng = new_group(ctx);
+    if (!ng) return CC_E_HIP;
+    ng->table = table_id;
+    PassScope scope;
+    if (const int erc = pass_enter(ctx, scope, *ng, nullptr)) {
+        scope.ctx = nullptr;   // (nothing was enqueued: no touch to record)
+        bind(ctx, 0, *ctx->scratch);
+        free_group(*ng);
+        delete ng;
+        return erc;
+    }
     int32_t gid = ctx->next_id++;
-    ctx->groups[gid].reset(new Group());
+    ctx->groups[gid].reset(ng);
     Group& g = *ctx->groups[gid];
-    g.table = table_id;
     g.seed = prm->seed;
     g.scoped = prm->scope_by_run;
     g.delim_filter = prm->delim_filter;
@@ -7553,7 +7748,8 @@ int cc_read_bam(cc_ctx* ctx, int32_t table_id, int64_t S, const int32_t* stream_
 // Re-run read_bam on a group whose stream is already resident (bench steps), with a new seed.
 int cc_read_bam_rerun(cc_ctx* ctx, int32_t group_id, uint64_t seed) {
     if (!ctx || !ctx->groups.count(group_id)) return CC_E_INVALID;
-    RC(enter(ctx));
+    PassScope scope;
+    RC(pass_enter(ctx, scope, *ctx->groups[group_id], nullptr));
     ctx->groups[group_id]->seed = seed;
     return read_bam_run(ctx, group_id);
 }
@@ -7566,7 +7762,7 @@ int cc_group_counters(cc_ctx* ctx, int32_t group_id, int64_t* counters) {
 
 int cc_group_free(cc_ctx* ctx, int32_t group_id) {
     if (!ctx || !ctx->groups.count(group_id)) return CC_E_INVALID;
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)wait_lanes(ctx);   // another group's join on its own lane may still read it
     {
         Group* gp = ctx->groups[group_id].get();
         std::vector<DeferredCheck> keep;
@@ -7574,8 +7770,8 @@ int cc_group_free(cc_ctx* ctx, int32_t group_id) {
             if (d.g != gp) keep.push_back(d);
         ctx->deferred.swap(keep);
     }
-    for (DevBuf& b : ctx->groups[group_id]->buf)
-        if (b.p) (void)hipFree(b.p);
+    if (ctx->d_err == ctx->groups[group_id]->d_err) bind(ctx, 0, *ctx->scratch);
+    free_group(*ctx->groups[group_id]);
     ctx->groups.erase(group_id);
     return 0;
 }
@@ -7584,8 +7780,9 @@ int cc_group_free(cc_ctx* ctx, int32_t group_id) {
 // both families; size 1 -> singleton record renamed, else consensus_maker.
 int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_out) {
     if (!ctx || !ctx->groups.count(group_id)) return CC_E_INVALID;
-    RC(enter(ctx));
     Group& g = *ctx->groups[group_id];
+    PassScope scope;
+    RC(pass_enter(ctx, scope, g, nullptr));
     auto pass = [&]() -> int {
         RC(flush_derive(ctx, g.table));
         const DevTable& T = ctx->tables[g.table];
@@ -7644,8 +7841,9 @@ int cc_consensus_maker(cc_ctx* ctx, int32_t group_id, double cutoff, int64_t* n_
 
 int cc_duplex_consensus(cc_ctx* ctx, int32_t group_id, const int32_t* bc_swap, int32_t n_bc, int64_t* n_out) {
     if (!ctx || !ctx->groups.count(group_id) || (!bc_swap && n_bc > 0)) return CC_E_INVALID;
-    RC(enter(ctx));
     Group& g = *ctx->groups[group_id];
+    PassScope scope;
+    RC(pass_enter(ctx, scope, g, nullptr));
     auto pass = [&]() -> int {
         RC(flush_derive(ctx, g.table));
         const DevTable& T = ctx->tables[g.table];
@@ -7682,9 +7880,10 @@ int cc_singleton_correction(cc_ctx* ctx, int32_t sgroup, int32_t ssgroup, const 
                             int64_t* n_out) {
     if (!ctx || !ctx->groups.count(sgroup) || !ctx->groups.count(ssgroup) || (!bc_swap && n_bc > 0))
         return CC_E_INVALID;
-    RC(enter(ctx));
     Group& g = *ctx->groups[sgroup];
     Group& s = *ctx->groups[ssgroup];
+    PassScope scope;
+    RC(pass_enter(ctx, scope, g, &s));   // (the join reads the SSCS side's grouping and builds its tags and buckets)
     auto pass = [&]() -> int {
         RC(flush_derive(ctx, g.table));
         RC(flush_derive(ctx, s.table));
@@ -7779,7 +7978,6 @@ int function_prep(cc_ctx* ctx, const DevTable& T) {
 }
 
 Group& scratch_group(cc_ctx* ctx, int32_t table) {
-    if (!ctx->scratch) ctx->scratch.reset(new Group());
     Group& g = *ctx->scratch;
     g.table = table;
     g.fast = false;
@@ -8752,7 +8950,6 @@ int cc_reduce_stats(cc_ctx* ctx, cc_comm* comm, int64_t* counters, int32_t n_cou
     const int64_t nsum = (int64_t)n_counters + fam_len, ntot = nsum + fam_len;
     if (ntot == 0) return 0;
     int brc = 0;
-    if (!ctx->scratch) ctx->scratch.reset(new Group());
     Group& g = *ctx->scratch;
     int64_t* d = GB(reduce_buf, ntot);
     std::vector<int64_t> h((size_t)ntot);
@@ -8789,7 +8986,6 @@ int cc_allreduce_max(cc_ctx* ctx, cc_comm* comm, int64_t* v, int32_t n) {
     if (!r) return CC_E_UNSUPPORTED;
     RC(enter(ctx));
     int brc = 0;
-    if (!ctx->scratch) ctx->scratch.reset(new Group());
     Group& g = *ctx->scratch;
     int64_t* d = GB(reduce_max, n);
     HIPCHK(hipMemcpyAsync(d, v, sizeof(int64_t) * n, hipMemcpyHostToDevice, ctx->stream));

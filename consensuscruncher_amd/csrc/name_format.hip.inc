@@ -167,9 +167,9 @@ __global__ __launch_bounds__(NM_T) void k_name_write_csn(Src src, int64_t n, nmc
     const uint32_t j = threadIdx.x % NM_LANES;
     if (i >= n) return;
     const int32_t* f = src.fields(i);
-    (void)CC_IDX(f[0], bc.n, DS_REC);
-    (void)CC_IDX(f[5], cg.n, DS_REC);
-    (void)CC_IDX(f[6], cg.n, DS_REC);
+    (void)CC_IDXG(f[0], bc.n, DS_REC, &st->guard);
+    (void)CC_IDXG(f[5], cg.n, DS_REC, &st->guard);
+    (void)CC_IDXG(f[6], cg.n, DS_REC, &st->guard);
     nmc::CsnLay y;
     const uint32_t e = nmc::csn_layout(f, src.suf(i), bc, cg, y);
     const uint64_t off = off32[i];
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(NM_T) void k_name_write_dcs(NameTab T, const int64_
     const int64_t i = (int64_t)blockIdx.x * (NM_T / NM_LANES) + (threadIdx.x / NM_LANES);
     const uint32_t j = threadIdx.x % NM_LANES;
     if (i >= n) return;
-    const int64_t rt = CC_IDX(rec_tag[i], T.n, DS_REC), rd = CC_IDX(rec_ds[i], T.n, DS_REC);
+    const int64_t rt = CC_IDXG(rec_tag[i], T.n, DS_REC, &st->guard), rd = CC_IDXG(rec_ds[i], T.n, DS_REC, &st->guard);
     uint64_t ta, da;
     uint32_t tl, dl;
     const bool ok = name_slots(T, rt, rd, &ta, &tl, &da, &dl);

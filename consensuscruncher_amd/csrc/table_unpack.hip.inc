@@ -207,6 +207,7 @@ int table_unpack(cc_ctx* ctx, const uint8_t* recs, const uint8_t* resident, uint
     std::vector<void*>& al = ctx->table_allocs[id];
     UnpackGuard guard{ctx, id};
     DevTable T{};
+    T.guard = ctx->d_err + ERR_GUARD;
     T.n = n;
     RC(dev_alloc(ctx, al, &T.tid, n));
     RC(dev_alloc(ctx, al, &T.pos, n));

@@ -271,6 +271,7 @@ AMD_SIGS = {
     "cc_table_derive": (C.c_int, [P, C.c_int32]),
     "cc_table_fetch": (C.c_int64, [P, C.c_int32, C.c_char_p, P, C.c_int64]),
     "cc_guard_reruns": (C.c_int64, [P]),
+    "cc_group_reruns": (C.c_int, [P, C.c_int32, i64p]),
     "cc_debug_poison": (C.c_int, [P, C.c_int32, C.c_char_p, C.c_int64, C.c_int32]),
     "cc_debug_scan": (C.c_int, [P, C.c_int32, C.c_int32, P, C.c_int64, P, P, P, i64p]),
     "cc_debug_sort_pairs": (C.c_int, [P, C.c_int32, P, P, C.c_int64, C.c_uint32, C.c_uint32, P, P]),

@@ -637,6 +637,9 @@ int64_t cc_launch_count(void);
  * release build's containment: an index read from a slot no kernel of the pass wrote is replaced by 0
  * and the pass re-runs exactly instead of faulting) */
 int64_t cc_guard_reruns(cc_ctx *ctx);
+/* the same per group: out[0] its planned passes re-run exactly because a plan did not hold, out[1] those
+ * of them after a guarded index, out[2] the events of other lanes its calls made their lane wait for */
+int cc_group_reruns(cc_ctx *ctx, int32_t group_id, int64_t *out);
 /* test hook: group buffer `name` grown to at least `bytes` and every byte set to `value` */
 int cc_debug_poison(cc_ctx *ctx, int32_t group_id, const char *name, int64_t bytes, int32_t value);
 /* test hook: the engine's prefix scan (scan_launch: k_scan_reduce + k_scan_down, or the single-launch
