@@ -81,6 +81,24 @@ __global__ __launch_bounds__(ASM_T) void k_asm_gather(const uint32_t* __restrict
     ssz[i] = sz[CC_IDXG(s, n, DS_REC, &st->guard)];
 }
 
+// Lane j's (of ASM_LANES) part of one output record of `size` bytes at d, whose stream offset's low
+// bits are off_lo: the head up to the stream's next 16-byte line and the tail behind the last whole
+// line as single bytes, the lines between as aligned 16-byte stores; no lane writes a byte outside
+// d[0, size).  w16(a, valid): the record's bytes [a, a + valid), zero from `valid` on.  (k_asm_copy's
+// and k_merge_copy's body.)
+template <class W16Of>
+__device__ __forceinline__ void asm_copy_record(uint8_t* d, uint32_t off_lo, uint32_t size, uint32_t j, W16Of w16) {
+    const uint32_t head = min(size, (16u - (off_lo & 15u)) & 15u);
+    const uint32_t lines = (size - head) >> 4, tail_at = head + (lines << 4);
+    if (j < head) d[j] = (uint8_t)w16(j, 1u).w[0];
+    uint4* dl = reinterpret_cast<uint4*>(d + head);
+    for (uint32_t c = j; c < lines; c += ASM_LANES) {
+        const upk::W16 w = w16(head + (c << 4), 16u);
+        dl[c] = make_uint4(w.w[0], w.w[1], w.w[2], w.w[3]);
+    }
+    if (tail_at + j < size) d[tail_at + j] = (uint8_t)w16(tail_at + j, 1u).w[0];
+}
+
 // Output records [o0, o0 + cnt): record o0 + i goes to out[base + off32[i] ...).  Every spec was accepted
 // by k_asm_sizes and off32 is the scan of the sizes it wrote, so each record lies inside out[0, total).
 __global__ __launch_bounds__(ASM_T) void k_asm_copy(asmb::Tables T, const asmb::Spec* __restrict__ spec,
@@ -104,16 +122,8 @@ __global__ __launch_bounds__(ASM_T) void k_asm_copy(asmb::Tables T, const asmb::
         at[o] = off;
         if (o == n - 1) at[n] = off + y.size;
     }
-    uint8_t* d = out + off;
-    const uint32_t head = min(y.size, (16u - ((uint32_t)off & 15u)) & 15u);
-    const uint32_t lines = (y.size - head) >> 4, tail_at = head + (lines << 4);
-    if (j < head) d[j] = (uint8_t)asmb::out16<DevFetch>(y, T, j, 1u).w[0];
-    uint4* dl = reinterpret_cast<uint4*>(d + head);
-    for (uint32_t c = j; c < lines; c += ASM_LANES) {
-        const upk::W16 w = asmb::out16<DevFetch>(y, T, head + (c << 4), 16u);
-        dl[c] = make_uint4(w.w[0], w.w[1], w.w[2], w.w[3]);
-    }
-    if (tail_at + j < y.size) d[tail_at + j] = (uint8_t)asmb::out16<DevFetch>(y, T, tail_at + j, 1u).w[0];
+    asm_copy_record(out + off, (uint32_t)off, y.size, j,
+                    [&](uint32_t a, uint32_t valid) { return asmb::out16<DevFetch>(y, T, a, valid); });
 }
 
 struct AsmGuard {

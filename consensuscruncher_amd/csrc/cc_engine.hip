@@ -6839,6 +6839,7 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
 
 #include "table_unpack.hip.inc"
 #include "bam_assemble.hip.inc"
+#include "bam_merge.hip.inc"
 #include "name_format.hip.inc"
 #include "bam_index.hip.inc"
 

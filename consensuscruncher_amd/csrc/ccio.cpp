@@ -424,6 +424,11 @@ void* g_asm_user = nullptr;
 bool g_outres_on = false;
 ccio_out_resident g_outres_cb = {};
 void* g_outres_user = nullptr;
+// An alternative merger for ccio_merge_handles (ccio_set_merge_hooks, hook_merge below): the device
+// merge of libccamd, or any functions with its contract.
+ccio_merge_fn g_mrg_fn = nullptr;
+ccio_merge_keep_fn g_mrg_keep_fn = nullptr;
+void* g_mrg_user = nullptr;
 
 // a stream the resident set holds, as the writers below see it
 struct ResSrc {
@@ -858,6 +863,14 @@ void ccio_set_out_resident(const ccio_out_resident* cb, void* user) {
     g_outres_on = cb && cb->assemble_keep && cb->fetch && cb->release;
     g_outres_cb = g_outres_on ? *cb : ccio_out_resident{};
     g_outres_user = g_outres_on ? user : nullptr;
+}
+
+// ccio_merge_handles' merges go to these first from now on (hook_merge; NULL: the host merge alone)
+void ccio_set_merge_hooks(ccio_merge_fn merge, ccio_merge_keep_fn keep, void* user) {
+    std::lock_guard<std::mutex> lk(g_hook_mu);
+    g_mrg_fn = merge;
+    g_mrg_keep_fn = keep;
+    g_mrg_user = (merge || keep) ? user : nullptr;
 }
 
 void ccio_set_inflate_hook(ccio_inflate_fn fn, void* user) {
@@ -2202,6 +2215,43 @@ uint8_t* asm_alloc(void* actx, uint64_t total) {
     return b->data();
 }
 
+// b as a source of the assemble and merge hooks: true with s (and the records' offsets in o, which s
+// points into) when b holds its records in place and in order in its own stream; false for a view
+// (ccio_bam_combine / ccio_bam_route).  A resident copy ccio_bam_resident names is passed through.
+bool hook_source(ccio_bam* b, int T, cc_asm_src& s, std::vector<uint64_t>& o) {
+    if (!b || !b->data) return false;
+    const int64_t nr = (int64_t)b->rec.size();
+    const uint8_t* lo = b->data->data();
+    const uint8_t* hi = lo + b->data->size();
+    s = cc_asm_src{lo, 0, 0, 0, nullptr, nr};
+    if (nr == 0) return true;
+    const uint8_t* first = b->rec[0];
+    if (first < lo || first >= hi) return false;
+    o.resize((size_t)nr);
+    std::atomic<bool> bad(false);
+    parallel_chunks(nr, T, 65536, [&](int64_t s0, int64_t e0) {
+        for (int64_t i = s0; i < e0; ++i) {
+            const uint8_t* r = b->rec[i];
+            if (r < first || r + 4 > hi) { bad = true; return; }
+            const uint8_t* end = r + 4 + (uint64_t)(uint32_t)rd32(r);
+            if (end > hi || (i + 1 < nr && b->rec[i + 1] != end)) { bad = true; return; }
+            o[(size_t)i] = (uint64_t)(r - first);
+        }
+    });
+    if (bad) return false;
+    const uint8_t* last = b->rec[nr - 1];
+    s.stream = first;
+    s.bytes = (uint64_t)(last + 4 + (uint64_t)(uint32_t)rd32(last) - first);
+    s.rec_off = o.data();
+    int64_t tok = 0;
+    uint64_t base = 0;
+    if (ccio_bam_resident(b, &tok, &base)) {
+        s.resident_id = tok;
+        s.base = base;
+    }
+    return true;
+}
+
 // ccio_write_bam_ex's records through the hook: true with the stream in `all` and its offsets in `at`
 // when a hook is set, every source's records lie in place and in order in its own stream, the hook
 // returned 0 and its result passed the checks; anything else leaves the write to the host.
@@ -2226,41 +2276,8 @@ bool hook_assemble(const ccio_bam* tmpl, ccio_interner* it, int64_t n, const cc_
     if (!fn && !ro) return false;
     std::vector<cc_asm_src> ss((size_t)nsrc);
     std::vector<std::vector<uint64_t>> offs((size_t)nsrc);
-    for (int f = 0; f < nsrc; ++f) {
-        ccio_bam* b = srcs[f];
-        if (!b || !b->data) return false;   // a view (ccio_bam_combine / ccio_bam_route)
-        const int64_t nr = (int64_t)b->rec.size();
-        const uint8_t* lo = b->data->data();
-        const uint8_t* hi = lo + b->data->size();
-        cc_asm_src& s = ss[(size_t)f];
-        s = cc_asm_src{lo, 0, 0, 0, nullptr, nr};
-        if (nr == 0) continue;
-        const uint8_t* first = b->rec[0];
-        if (first < lo || first >= hi) return false;
-        std::vector<uint64_t>& o = offs[(size_t)f];
-        o.resize((size_t)nr);
-        std::atomic<bool> bad(false);
-        parallel_chunks(nr, T, 65536, [&](int64_t s0, int64_t e0) {
-            for (int64_t i = s0; i < e0; ++i) {
-                const uint8_t* r = b->rec[i];
-                if (r < first || r + 4 > hi) { bad = true; return; }
-                const uint8_t* end = r + 4 + (uint64_t)(uint32_t)rd32(r);
-                if (end > hi || (i + 1 < nr && b->rec[i + 1] != end)) { bad = true; return; }
-                o[(size_t)i] = (uint64_t)(r - first);
-            }
-        });
-        if (bad) return false;
-        const uint8_t* last = b->rec[nr - 1];
-        s.stream = first;
-        s.bytes = (uint64_t)(last + 4 + (uint64_t)(uint32_t)rd32(last) - first);
-        s.rec_off = o.data();
-        int64_t tok = 0;
-        uint64_t base = 0;
-        if (ccio_bam_resident(b, &tok, &base)) {
-            s.resident_id = tok;
-            s.base = base;
-        }
-    }
+    for (int f = 0; f < nsrc; ++f)
+        if (!hook_source(srcs[f], T, ss[(size_t)f], offs[(size_t)f])) return false;
     // the extents the specs use of the caller's arrays (the host writer reads them without any)
     int64_t n_names = 0, name_end = 0, cq = 0, cs = 0;
     bool neg = false;
@@ -2369,6 +2386,145 @@ bool hook_assemble(const ccio_bam* tmpl, ccio_interner* it, int64_t n, const cc_
         }
     });
     return !bad;
+}
+
+// ccio_merge_handles' inputs as the merge hooks take them
+struct MergeIn {
+    std::vector<cc_asm_src> ss;
+    std::vector<std::vector<uint64_t>> offs;
+    std::vector<int64_t> first;   // input s holds the concatenation's records [first[s], first[s + 1])
+    int64_t n = 0;
+    const uint8_t* rec(ccio_bam* const* ins, int64_t g) const {
+        int s = 0;
+        while (g >= first[(size_t)s + 1]) ++s;
+        return ins[s]->rec[(size_t)(g - first[(size_t)s])];
+    }
+};
+
+// true when a merge hook may take the merge: a hook is set, at most 8 inputs, every input holds its
+// records in place and in order in its own stream and is in key order (an unsorted input leaves the
+// whole merge to the host's sort)
+bool merge_inputs(ccio_bam* const* ins, int nin, int T, MergeIn& in) {
+    {
+        std::lock_guard<std::mutex> lk(g_hook_mu);
+        if (!g_mrg_fn && !g_mrg_keep_fn) return false;
+    }
+    if (nin > 8) return false;
+    in.ss.resize((size_t)nin);
+    in.offs.resize((size_t)nin);
+    in.first.assign((size_t)nin + 1, 0);
+    for (int f = 0; f < nin; ++f) {
+        if (!hook_source(ins[f], T, in.ss[(size_t)f], in.offs[(size_t)f])) return false;
+        if (!src_sorted(RecSrc{ins[f]->rec.data(), (int64_t)ins[f]->rec.size()}, 1, T)) return false;
+        in.first[(size_t)f + 1] = in.first[(size_t)f] + (int64_t)ins[f]->rec.size();
+    }
+    in.n = in.first[(size_t)nin];
+    return in.n <= (int64_t)INT32_MAX;
+}
+
+// The merge through a hook: true with the offsets in `at` and the stream in `all` (the plain hook), or
+// (ro: the keep hook, tried only while the resident output set is installed) with the set under
+// ro->rs.token and `all` holding the stream only when ro->have_host.  What the hook returned passed
+// the checks of ccio_set_merge_hooks' contract; a false return has released the token.
+bool hook_merge(ccio_bam* const* ins, int nin, const MergeIn& in, int T, Bytes& all, std::vector<uint64_t>& at,
+                ResOut* ro = nullptr) {
+    ccio_merge_fn fn;
+    ccio_merge_keep_fn kfn;
+    void* user;
+    {
+        std::lock_guard<std::mutex> lk(g_hook_mu);
+        fn = g_mrg_fn;
+        kfn = g_mrg_keep_fn;
+        user = g_mrg_user;
+        if (ro) {
+            if (!g_outres_on) return false;
+            ro->rs.cb = g_outres_cb;
+            ro->rs.user = g_outres_user;
+        }
+    }
+    if (ro ? !kfn : !fn) return false;
+    const std::vector<uint8_t>& hdr = ins[0]->header_raw;
+    const int64_t n = in.n;
+    at.assign((size_t)n + 1, 0);
+    std::vector<uint32_t> org((size_t)std::max<int64_t>(n, 1), 0);
+    uint64_t total = 0;
+    auto fail = [&]() {
+        if (ro && ro->rs.token) ro->rs.cb.release(ro->rs.user, ro->rs.token);
+        if (ro) ro->rs.token = 0;
+        return false;
+    };
+    int rc;
+    if (ro)
+        rc = kfn(user, hdr.data(), (uint64_t)hdr.size(), in.ss.data(), nin, asm_alloc, &all, ro->need_host ? 1 : 0, at.data(),
+                 org.data(), &total, &ro->rs.token);
+    else
+        rc = fn(user, hdr.data(), (uint64_t)hdr.size(), in.ss.data(), nin, asm_alloc, &all, at.data(), org.data(), &total);
+    if (rc != 0 || (ro && ro->rs.token == 0)) return fail();
+    const bool have_host = ro ? ro->need_host : true;
+    if (at[0] != hdr.size() || at[(size_t)n] != total || total < hdr.size() || (have_host && total != all.size())) return fail();
+    if (have_host && memcmp(all.data(), hdr.data(), hdr.size()) != 0) return fail();
+    {   // one pass over the host records: offsets, permutation, order, sizes (and the stream's block_size words)
+        std::vector<uint8_t> seen((size_t)n, 0);
+        std::atomic<bool> bad(false);
+        parallel_chunks(n, T, 65536, [&](int64_t s0, int64_t e0) {
+            for (int64_t i = s0; i < e0; ++i) {
+                const uint64_t a = at[(size_t)i], e = at[(size_t)i + 1];
+                const uint32_t g = org[(size_t)i];
+                if (e <= a || e > total || (int64_t)g >= n) { bad = true; return; }
+                if (__atomic_fetch_add(&seen[g], (uint8_t)1, __ATOMIC_RELAXED) != 0) { bad = true; return; }
+                const uint8_t* r = in.rec(ins, g);
+                if ((uint64_t)(uint32_t)rd32(r) + 4 != e - a) { bad = true; return; }
+                if (have_host && rd32(all.data() + a) != rd32(r)) { bad = true; return; }
+                if (i > 0) {
+                    const uint32_t pg = org[(size_t)i - 1];
+                    if ((int64_t)pg >= n) { bad = true; return; }
+                    const uint64_t pk = coord_key(in.rec(ins, pg) + 4), k = coord_key(r + 4);
+                    if (pk > k || (pk == k && pg >= g)) { bad = true; return; }
+                }
+            }
+        });
+        if (bad) return fail();
+    }
+    if (!ro) return true;
+    ResSrc& rs = ro->rs;
+    ro->total = total;
+    ro->have_host = ro->need_host;
+    if (!ro->have_host) {   // the header where the stream lies
+        std::vector<uint8_t> got(hdr.size());
+        if (!hdr.empty() && (rs.cb.fetch(rs.user, rs.token, 0, (uint64_t)hdr.size(), got.data()) != 0 || got != hdr)) return fail();
+    }
+    if (n > 0 && rs.cb.index_fields) {
+        ro->fields.assign((size_t)n, cc_index_field{0, 0, 0, 0});
+        if (rs.cb.index_fields(rs.user, rs.token, at.data(), n, ro->fields.data()) == 0) {
+            std::atomic<bool> bad(false);
+            parallel_chunks(n, T, 65536, [&](int64_t s0, int64_t e0) {
+                for (int64_t i = s0; i < e0; ++i)
+                    if ((uint64_t)ro->fields[(size_t)i].block_size + 4 != at[(size_t)i + 1] - at[(size_t)i]) { bad = true; return; }
+            });
+            if (bad) return fail();
+            ro->have_fields = true;
+        } else {
+            ro->fields.clear();
+        }
+    } else if (n == 0) {
+        ro->have_fields = true;
+    }
+    if (!ro->have_fields && !ro->have_host) {   // no fields to check the records by: the stream itself
+        try {
+            all.resize((size_t)total);
+        } catch (...) {
+            return fail();
+        }
+        if (rs.cb.fetch(rs.user, rs.token, 0, total, all.data()) != 0) return fail();
+        ro->have_host = true;
+        std::atomic<bool> bad(false);
+        parallel_chunks(n, T, 65536, [&](int64_t s0, int64_t e0) {
+            for (int64_t i = s0; i < e0; ++i)
+                if ((uint64_t)(uint32_t)rd32(all.data() + at[(size_t)i]) + 4 != at[(size_t)i + 1] - at[(size_t)i]) { bad = true; return; }
+        });
+        if (bad) return fail();
+    }
+    return true;
 }
 
 }  // namespace
@@ -2595,6 +2751,28 @@ int ccio_merge_handles(const char* out_path, ccio_bam* const* ins, int nin, int 
     if (keep) *keep = nullptr;
     if (nin < 1) { set_err("merge: no input"); return -1; }
     const int T = hw_threads(nthreads);
+    flags &= CCIO_W_INDEX | CCIO_W_ASYNC | CCIO_W_MEMORY;
+    MergeIn in;
+    if (merge_inputs(ins, nin, T, in)) {   // the merge hooks (ccio_set_merge_hooks); whatever they refuse is merged below
+        PhaseTimer pt;
+        {
+            // the keep hook first, while the resident set is installed: the stream stays where it was built
+            Bytes rall;
+            std::vector<uint64_t> rat;
+            ResOut ro;
+            ro.need_host = keep != nullptr || (flags & CCIO_W_MEMORY) != 0;
+            if (hook_merge(ins, nin, in, T, rall, rat, &ro)) {
+                pt.lap("merge: resident hook");
+                return finish_resident(out_path, ins[0], std::move(rall), std::move(rat), std::move(ro), level, T, flags, keep);
+            }
+        }
+        Bytes hall;
+        std::vector<uint64_t> hat;
+        if (hook_merge(ins, nin, in, T, hall, hat)) {
+            pt.lap("merge: hook");
+            return finish_stream(out_path, ins[0], std::move(hall), hat, level, T, flags, keep);
+        }
+    }
     std::vector<const ccio_bam*> bs(ins, ins + nin);
     const std::vector<const uint8_t*> recs = merge_order(bs, T);
     return finish_output(out_path, bs[0], recs, level, T, flags & (CCIO_W_INDEX | CCIO_W_ASYNC | CCIO_W_MEMORY), keep);

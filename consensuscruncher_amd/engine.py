@@ -346,6 +346,7 @@ _INFLATE_OWNER = None   # likewise for the inflate hook
 _KEEP_OWNER = None   # and for the inflate hook that keeps resident streams
 _ASSEMBLE_OWNER = None   # and for the assemble hook
 _OUT_RESIDENT_OWNER = None   # and for the resident output set
+_MERGE_OWNER = None   # and for the merge hooks
 
 
 class Engine(object):
@@ -367,6 +368,7 @@ class Engine(object):
         self._keep_wired = False
         self.crc_device = False
         self.assemble_device = False
+        self.merge_device = False
         self.out_resident_device = False   # the resident output set is wired (device_out_resident)
         self._out_resident_want = os.environ.get("CC_OUT_RESIDENT_DEVICE") == "1"
         self.names_device = os.environ.get("CC_NAMES_DEVICE") == "1"
@@ -385,6 +387,8 @@ class Engine(object):
             self.device_decode(True)
         if os.environ.get("CC_ASSEMBLE_DEVICE") == "1":
             self.device_assemble(True)
+        if os.environ.get("CC_MERGE_DEVICE") == "1":
+            self.device_merge(True)
         self._sync_out_resident()
 
     def device_decode(self, on):
@@ -576,6 +580,37 @@ class Engine(object):
         _ASSEMBLE_OWNER = None
         self.assemble_device = False
         self._sync_out_resident()
+        return was
+
+    def device_merge(self, on):
+        """Wires (or unwires) this context's device merge into libccio's merges (cc_bam_merge_hooks ->
+        ccio_set_merge_hooks): every merge_kept from now on whose inputs hold their records in place,
+        are at most 8 and are each in key order is built by k_merge_keys / k_merge_rank / k_merge_copy
+        (with the resident output path on, the stream stays on the device for the encoder and the
+        index); libccio checks the result and merges whatever the device refused on the host, so the
+        files are the same either way.  The hooks are one pair per process, with device_assemble's
+        ownership rules: the last engine to wire them serves the merges, and the engine it took them
+        from reads merge_device False from then on.  The merge is synchronous, so there is nothing to
+        wait for.  Returns the previous state."""
+        global _MERGE_OWNER
+        was = self.merge_device
+        on = bool(on)
+        if on == was:
+            return was
+        io = N.io()
+        if on:
+            fn, keep, user = N.P(), N.P(), N.P()
+            self._check(self.lib.cc_bam_merge_hooks(self.h, C.byref(fn), C.byref(keep), C.byref(user)))
+            prev = _MERGE_OWNER
+            if prev is not None and prev is not self:
+                prev.merge_device = False
+            io.ccio_set_merge_hooks(fn, keep, user)
+            _MERGE_OWNER = self
+            self.merge_device = True
+            return was
+        io.ccio_set_merge_hooks(None, None, None)
+        _MERGE_OWNER = None
+        self.merge_device = False
         return was
 
     def device_out_resident(self, on):
@@ -820,11 +855,9 @@ class Engine(object):
         return self._assemble(header, sources, specs, names, name_off, cons_seq, cons_qual, group, rg_values, sort, keep,
                               False)
 
-    def _assemble(self, header, sources, specs, names, name_off, cons_seq, cons_qual, group, rg_values, sort, keep,
-                  in_set):
-        header = np.frombuffer(bytes(header), np.uint8)
-        specs = np.ascontiguousarray(specs, N.OUT_SPEC_DTYPE)
-        n = len(specs)
+    @staticmethod
+    def _asm_sources(sources):
+        """assemble's / merge's sources as a cc_asm_src array, and the arrays it points into."""
         arr = (N.cc_asm_src * max(len(sources), 1))()
         hold = []
         for f, src in enumerate(sources):
@@ -837,6 +870,40 @@ class Engine(object):
                     np.ascontiguousarray(src[0], np.uint8)
                 hold.append(st)
                 arr[f] = N.cc_asm_src(st.ctypes.data if len(st) else None, len(st), 0, 0, off.ctypes.data, len(off))
+        return arr, hold
+
+    def merge(self, header, sources, keep=False):
+        """cc_bam_merge: the merge of `sources` (assemble's sources, at most 8, each in key order) as
+        (stream bytes, at, org): the header's bytes then every record in key order, ties to the earlier
+        source then the earlier record; at the n + 1 record offsets (uint64), org each output record's
+        index in the concatenation of the sources (uint32).  keep=True is cc_bam_merge_keep without a
+        download: (at, org, token), the stream left on the device as resident stream `token`
+        (resident_fetch, bgzf_deflate_resident, index_fields; resident_free when done)."""
+        header = np.frombuffer(bytes(header), np.uint8)
+        arr, hold = self._asm_sources(sources)
+        n = sum(len(src[1]) for src in sources)
+        at = np.zeros(n + 1, np.uint64)
+        org = np.zeros(max(n, 1), np.uint32)
+        total = C.c_uint64()
+        hp = N.ptr(header) if len(header) else None
+        if keep:
+            rid = C.c_int64(0)
+            self._check(self.lib.cc_bam_merge_keep(self.h, hp, len(header), arr, len(sources), None, 0, N.ptr(at),
+                                                   N.ptr(org), C.byref(total), C.byref(rid)))
+            return at, org[:n], int(rid.value)
+        self._check(self.lib.cc_bam_merge(self.h, hp, len(header), arr, len(sources), None, 0, None, None,
+                                          C.byref(total)))
+        out = np.zeros(max(int(total.value), 1), np.uint8)
+        self._check(self.lib.cc_bam_merge(self.h, hp, len(header), arr, len(sources), N.ptr(out), int(total.value),
+                                          N.ptr(at), N.ptr(org), C.byref(total)))
+        return out[:int(total.value)].tobytes(), at, org[:n]
+
+    def _assemble(self, header, sources, specs, names, name_off, cons_seq, cons_qual, group, rg_values, sort, keep,
+                  in_set):
+        header = np.frombuffer(bytes(header), np.uint8)
+        specs = np.ascontiguousarray(specs, N.OUT_SPEC_DTYPE)
+        n = len(specs)
+        arr, hold = self._asm_sources(sources)
         names = np.zeros(0, np.uint8) if names is None else np.ascontiguousarray(names).view(np.uint8)
         name_off = np.zeros(1, np.int64) if name_off is None else np.ascontiguousarray(name_off, np.int64)
         names_bytes = int(name_off[-1]) if in_set else len(names)   # (a set: the bytes its first n_names names take)
@@ -1006,6 +1073,7 @@ class Engine(object):
                 self.device_inflate(False)    # that are left go with it (cc_destroy)
                 self.device_bgzf(False)
                 self.device_assemble(False)   # (the resident output set goes with either of the two)
+                self.device_merge(False)
             finally:
                 self.lib.cc_destroy(self.h)
                 self.h = None

@@ -107,7 +107,12 @@ ASM_ALLOC_FN = C.CFUNCTYPE(P, P, C.c_uint64)
 ASSEMBLE_FN = C.CFUNCTYPE(C.c_int, P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, P, C.c_int64, P, P, C.c_int64,
                           C.c_uint64, P, C.c_uint64, P, C.c_uint64, P, P, C.c_int32, C.c_int, ASM_ALLOC_FN, P,
                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
-
+# ccio_merge_fn: user, header, header_bytes, srcs, nsrc, alloc, actx, at, org, total; ccio_merge_keep_fn: the
+# same with need_host before at and token at the end
+MERGE_FN = C.CFUNCTYPE(C.c_int, P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, ASM_ALLOC_FN, P,
+                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64))
+MERGE_KEEP_FN = C.CFUNCTYPE(C.c_int, P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, ASM_ALLOC_FN, P, C.c_int,
+                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64))
 
 
 class cc_index_field(C.Structure):
@@ -145,6 +150,7 @@ IO_SIGS = {
     "ccio_flush": (C.c_int, []),
     "ccio_set_deflate_hook": (None, [P, P]),
     "ccio_set_assemble_hook": (None, [P, P]),
+    "ccio_set_merge_hooks": (None, [P, P, P]),
     "ccio_set_inflate_hook": (None, [P, P]),
     "ccio_set_inflate_keep_hook": (None, [P, P, P]),
     "ccio_set_inflate_crc_hook": (None, [P, P]),
@@ -254,6 +260,11 @@ AMD_SIGS = {
                                        C.c_int64, C.c_uint64, P, C.c_uint64, P, C.c_uint64, C.c_int32, P, P, C.c_int32,
                                        C.c_int, P, C.c_uint64, P, C.POINTER(C.c_uint64), i64p]),
     "cc_out_resident_hooks": (C.c_int, [P, C.POINTER(ccio_out_resident), C.POINTER(P)]),
+    "cc_bam_merge": (C.c_int, [P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, P, C.c_uint64, P, P,
+                               C.POINTER(C.c_uint64)]),
+    "cc_bam_merge_keep": (C.c_int, [P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, P, C.c_uint64, P, P,
+                                    C.POINTER(C.c_uint64), i64p]),
+    "cc_bam_merge_hooks": (C.c_int, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "cc_bgzf_deflate_resident": (C.c_int64, [P, C.c_int64, C.c_uint64, C.c_uint64, P, C.c_uint64, P, C.c_int64]),
     "cc_index_fields": (C.c_int, [P, C.c_int64, P, C.c_int64, P]),
     "cc_resident_put": (C.c_int, [P, P, C.c_uint64, i64p]),

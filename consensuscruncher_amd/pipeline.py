@@ -8,6 +8,7 @@ coordinate sort, file-ordered merge and BAI writer (ConsensusCruncher.py:10-34,
 (:325-346), and the legacy shell pipeline's all.unique.sscs product
 (test/bash_scripts/ConsensusCruncher.sh:261-265), on request.
 """
+import contextlib
 import os
 import time
 
@@ -53,8 +54,11 @@ def cleanup(sd, identifier, scorrect):
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
                        bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host", crc="host",
-                       assemble="host", names="host", out_resident="host", names_resident="host"):
-    """names_resident: "host" (the default) or "device" (Engine.device_names_resident: a stage's formatted
+                       assemble="host", names="host", out_resident="host", names_resident="host", merge="host"):
+    """merge: "host" (libccio merges the sorted stage outputs, the default) or "device" (Engine.device_merge:
+    sscs.sc, all.unique.dcs and all.unique.sscs are merged by the engine's merge kernels, and with the
+    resident output path on the merged stream stays on the device for the encoder and the index and each
+    merge input is uploaded once for the merges that read it: the same files).  names_resident: "host" (the default) or "device" (Engine.device_names_resident: a stage's formatted
     names stay on the device as a name set the assembler reads in place, and the SSCS names are formatted
     from the group's own buffers: the same files); it engages only with names="device" and
     assemble="device" and is otherwise without effect.  out_resident: "host" (the default) or "device" (Engine.device_out_resident: each stage output's
@@ -78,6 +82,17 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
     come from the device; same bytes read, same files written); it engages only with inflate="device"
     or bgzf="device" and is otherwise without effect.  Each option is wired for this call only; see
     _consensus_pipeline."""
+    if merge not in ("host", "device"):
+        raise ValueError('merge must be "host" or "device"')
+    if merge == "device":
+        engine = engine or get_engine()
+        was_mrg = engine.device_merge(True)
+        try:
+            return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                      cleanup_files, all_unique_sscs, bgzf, inflate, decode, bgzf_effort, resident, crc,
+                                      assemble, names, out_resident, names_resident)
+        finally:
+            engine.device_merge(was_mrg)
     if names_resident not in ("host", "device"):
         raise ValueError('names_resident must be "host" or "device"')
     if names_resident == "device":
@@ -276,26 +291,34 @@ def _stages(bam, c_output, bed, cutoff, bdelim, scorrect, engine, verbose, level
             os.rename(srt(path) + '.bai', dst + '.bai')
             moved[name] = dst
             mh[name] = sink.take(srt(path))
-        sscs_sc = srt('{}/sscs_sc/{}.sscs.sc.bam'.format(sd, identifier))
-        sscs_sc_h = merge_kept(sscs_sc, [sscs_h, mh["sscs.correction"], mh["singleton.correction"]], level,
-                               async_writes=True)
-        os.makedirs(sd + '/dcs_sc', exist_ok=True)
-        os.rename('{}/sscs/{}.stats.txt'.format(sd, identifier), '{}/dcs_sc/{}.stats.txt'.format(sd, identifier))
-        os.rename('{}/sscs/{}.time_tracker.txt'.format(sd, identifier),
-                  '{}/dcs_sc/{}.time_tracker.txt'.format(sd, identifier))
-        run_dcs(sscs_sc, dcs_sc, bedfile=bed, engine=engine, verbose=verbose, level=level, sink=sink, bam=sscs_sc_h)
-        sscs_sc_h = None
-        dcs_sc, sscs_sc_sing = srt(dcs_sc), srt(sscs_sc_sing)
-        all_unique = srt('{}/dcs_sc/{}.all.unique.dcs.bam'.format(sd, identifier))
-        merge_kept(all_unique, [sink.take(dcs_sc), sink.take(sscs_sc_sing), mh["uncorrected"]], level, keep=False,
-                   async_writes=True)
-        if all_unique_sscs:
-            # legacy shell pipeline (test/bash_scripts/ConsensusCruncher.sh:261-265): SSCS + corrected
-            # singletons + uncorrected singletons
-            aus = srt('{}/sscs_sc/{}.all.unique.sscs.bam'.format(sd, identifier))
-            merge_kept(aus, [sscs_h, mh["sscs.correction"], mh["singleton.correction"], mh["uncorrected"]], level,
-                       keep=False, async_writes=True)
-            out["all_unique_sscs"] = aus
+        # the device merge with the resident output path: each input of the merges below is uploaded once
+        # for all of them (sscs_h and the correction handles feed two), and freed after the last
+        pins = contextlib.ExitStack()
+        eng = engine or get_engine()
+        if eng.merge_device and eng.out_resident_device:
+            for h in [sscs_h] + [mh[name] for name in corr]:
+                pins.enter_context(eng.pin_source(h))
+        with pins:
+            sscs_sc = srt('{}/sscs_sc/{}.sscs.sc.bam'.format(sd, identifier))
+            sscs_sc_h = merge_kept(sscs_sc, [sscs_h, mh["sscs.correction"], mh["singleton.correction"]], level,
+                                   async_writes=True)
+            os.makedirs(sd + '/dcs_sc', exist_ok=True)
+            os.rename('{}/sscs/{}.stats.txt'.format(sd, identifier), '{}/dcs_sc/{}.stats.txt'.format(sd, identifier))
+            os.rename('{}/sscs/{}.time_tracker.txt'.format(sd, identifier),
+                      '{}/dcs_sc/{}.time_tracker.txt'.format(sd, identifier))
+            run_dcs(sscs_sc, dcs_sc, bedfile=bed, engine=engine, verbose=verbose, level=level, sink=sink, bam=sscs_sc_h)
+            sscs_sc_h = None
+            dcs_sc, sscs_sc_sing = srt(dcs_sc), srt(sscs_sc_sing)
+            all_unique = srt('{}/dcs_sc/{}.all.unique.dcs.bam'.format(sd, identifier))
+            merge_kept(all_unique, [sink.take(dcs_sc), sink.take(sscs_sc_sing), mh["uncorrected"]], level, keep=False,
+                       async_writes=True)
+            if all_unique_sscs:
+                # legacy shell pipeline (test/bash_scripts/ConsensusCruncher.sh:261-265): SSCS + corrected
+                # singletons + uncorrected singletons
+                aus = srt('{}/sscs_sc/{}.all.unique.sscs.bam'.format(sd, identifier))
+                merge_kept(aus, [sscs_h, mh["sscs.correction"], mh["singleton.correction"], mh["uncorrected"]], level,
+                           keep=False, async_writes=True)
+                out["all_unique_sscs"] = aus
         mh = None
         os.rename('{}/dcs_sc/{}.stats.txt'.format(sd, identifier), '{}/{}.stats.txt'.format(sd, identifier))
         os.rename('{}/dcs_sc/{}.time_tracker.txt'.format(sd, identifier),

@@ -622,8 +622,12 @@ def to_owners(comm, geo, parts):
 def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|", scorrect="True", level=6,
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
                      cuts=None, bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host",
-                     crc="host", assemble="host", names="host", out_resident="host", names_resident="host"):
-    """names_resident: "host" (the default) or "device": this rank's formatted names stay on the device
+                     crc="host", assemble="host", names="host", out_resident="host", names_resident="host",
+                     merge="host"):
+    """merge: "host" (the default) or "device": this rank's merges of sorted record sets go to the engine's
+    merge kernels where every input holds its records in place (Engine.device_merge; merges of combined
+    and routed views, and of more than 8 inputs, stay on the host as before).
+    names_resident: "host" (the default) or "device": this rank's formatted names stay on the device
     for the assembler and its SSCS names come from the group's own buffers (Engine.device_names_resident;
     only with names="device" and assemble="device"; a rank's combined and routed views take the fetched
     blob as before).
@@ -643,6 +647,16 @@ def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|
     uploaded as before).  crc: "host" (the default) or "device": this rank's device inflater and encoder
     take their CRC32s from the device (Engine.device_crc; only with inflate="device" or bgzf="device").
     These are pipeline.consensus_pipeline's options; see _sharded_pipeline."""
+    if merge not in ("host", "device"):
+        raise ValueError('merge must be "host" or "device"')
+    if merge == "device":
+        was_mrg = engine.device_merge(True)
+        try:
+            return sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                    blocks, held, refs, keep, finalize, timings, cuts, bgzf, inflate, decode,
+                                    bgzf_effort, resident, crc, assemble, names, out_resident, names_resident)
+        finally:
+            engine.device_merge(was_mrg)
     if names_resident not in ("host", "device"):
         raise ValueError('names_resident must be "host" or "device"')
     if names_resident == "device":

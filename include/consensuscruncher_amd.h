@@ -381,6 +381,31 @@ int ccio_sort_bam_ex(const char *in_path, const char *out_path, int level, int n
 /* samtools merge of coordinate-sorted record sets held in memory (ties keep input order) */
 int ccio_merge_handles(const char *out_path, ccio_bam *const *ins, int nin, int level, int nthreads, int flags,
                        ccio_bam **keep);
+/* An alternative merger for ccio_merge_handles (the device merge: cc_bam_merge_hooks below, or any
+ * functions with its contract).  merge receives the header, the inputs as cc_asm_src (as the assemble
+ * hook receives its sources) and alloc / actx for the stream; it fills at[n + 1] (the output records'
+ * offsets, n the inputs' records together), org[n] (each output record's index in the concatenation
+ * of the inputs) and *total.  keep is the same plus need_host and *token: the stream stays in a place
+ * of its own named by *token (> 0), which then belongs to the resident output set's deflate,
+ * index_fields, fetch and release (ccio_set_out_resident); alloc is called only when need_host is 1.
+ * ccio_merge_handles goes to the hooks only when every input holds its records in place and in
+ * order in its own stream (views from ccio_bam_combine / ccio_bam_route never do), there are at most
+ * 8 inputs and every input is in key order; it tries keep first when the resident output set is
+ * installed, then merge, then merges on the host as without hooks.  What a hook returns is checked
+ * against the host records in one parallel pass: at[0] is the header's size, at is strictly
+ * increasing and at[n] == total; org is a permutation of 0..n-1; along the output the keys are
+ * non-decreasing and equal keys have increasing org (input order, then record order);
+ * at[i + 1] - at[i] is 4 + block_size of record org[i]; with a host copy the header's bytes and every
+ * record's block_size word are compared, without one the fetched header bytes and the index_fields
+ * block sizes.  The first failure releases the token (if any) and the merge goes on to the next
+ * path: a file is never lost.  NULL unsets a hook. */
+typedef int (*ccio_merge_fn)(void *user, const uint8_t *header, uint64_t header_bytes, const cc_asm_src *srcs,
+                             int32_t nsrc, cc_asm_alloc_fn alloc, void *actx, uint64_t *at, uint32_t *org,
+                             uint64_t *total);
+typedef int (*ccio_merge_keep_fn)(void *user, const uint8_t *header, uint64_t header_bytes, const cc_asm_src *srcs,
+                                  int32_t nsrc, cc_asm_alloc_fn alloc, void *actx, int need_host, uint64_t *at,
+                                  uint32_t *org, uint64_t *total, int64_t *token);
+void ccio_set_merge_hooks(ccio_merge_fn merge, ccio_merge_keep_fn keep, void *user);
 /* records of the inputs in file order, one file after the other (sharded stage parts, rank order) */
 int ccio_concat_bams(const char *out_path, const char *const *in_paths, int nin, int level, int nthreads);
 /* <path>.bai for a coordinate-sorted BAM (samtools index, ConsensusCruncher.py:10-34) */
@@ -731,6 +756,26 @@ int cc_bam_assemble_keep(cc_ctx *ctx, const uint8_t *header, uint64_t header_byt
 /* the set to hand to ccio_set_out_resident (assemble-keep, resident deflate, index fields, fetch and
  * release over this context); unset it before cc_destroy */
 int cc_out_resident_hooks(cc_ctx *ctx, ccio_out_resident *cb, void **user);
+/* The merge of nsrc (at most 8) coordinate-sorted record sets built on the device, byte for byte what
+ * ccio_merge_handles gathers on the host (csrc/merge_core.h, bam_merge.hip.inc): the header's bytes,
+ * then every source's records in key order, ties to the earlier source, then the earlier record.
+ * srcs as for cc_bam_assemble.  With n the sources' records together: at[n + 1] receives the output
+ * records' offsets, org[n] (may be NULL) each output record's index in the concatenation of the
+ * sources, *total the stream's size; out NULL is a size query (only *total is written).
+ * CC_E_INVALID, with a message naming the source and the record, for a record whose offset lies
+ * outside its source, with fewer than 4 bytes left, with block_size < 32 or running past the source's
+ * bytes, and for a source that is not in key order; CC_E_UNSUPPORTED for more than 8 sources or more
+ * than 2^31 - 1 records.  Nothing is read through a record's length before every record was accepted. */
+int cc_bam_merge(cc_ctx *ctx, const uint8_t *header, uint64_t header_bytes, const cc_asm_src *srcs, int32_t nsrc,
+                 uint8_t *out, uint64_t cap, uint64_t *at, uint32_t *org, uint64_t *total);
+/* cc_bam_merge that leaves the stream on the device as resident stream *resident_id (> 0), with the
+ * resident streams' padding (cc_bgzf_deflate_resident, cc_index_fields, cc_resident_fetch and
+ * cc_resident_free serve it).  at and total are required; the stream is downloaded only when out is
+ * non-NULL.  After any error *resident_id = 0 and nothing stays resident. */
+int cc_bam_merge_keep(cc_ctx *ctx, const uint8_t *header, uint64_t header_bytes, const cc_asm_src *srcs, int32_t nsrc,
+                      uint8_t *out, uint64_t cap, uint64_t *at, uint32_t *org, uint64_t *total, int64_t *resident_id);
+/* the functions to hand to ccio_set_merge_hooks; unset them before cc_destroy */
+int cc_bam_merge_hooks(cc_ctx *ctx, ccio_merge_fn *merge, ccio_merge_keep_fn *keep, void **user);
 /* the group whose consensus buffers the hook's next call uses when libccio passes it no arrays (that
  * call consumes it); -1 clears it */
 int cc_bam_assemble_group(cc_ctx *ctx, int32_t group_id);
