@@ -5541,6 +5541,7 @@ struct cc_ctx {
     int64_t names_n = 0;
     std::map<int64_t, NameSet> name_sets; // cc_names_keep's sets by id
     int64_t asm_names = 0;                // cc_bam_assemble_names: the set the assembler reads (0: none; not consumed)
+    int ids_hash_bits = 64;               // cc_debug_ids_hash_bits: the bits cc_table_ids keeps of a key's hash
 };
 
 namespace {
@@ -6838,6 +6839,7 @@ int cc_table_upload(cc_ctx* ctx, const cc_records* r, int32_t max_len, int32_t* 
 }  // extern "C"
 
 #include "table_unpack.hip.inc"
+#include "table_ids.hip.inc"
 #include "bam_assemble.hip.inc"
 #include "bam_merge.hip.inc"
 #include "name_format.hip.inc"

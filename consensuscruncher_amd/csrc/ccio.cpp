@@ -39,6 +39,7 @@
 
 #include "../../include/consensuscruncher_amd.h"
 #include "unpack_core.h"
+#include "intern_core.h"
 #include "index_core.h"
 
 namespace {
@@ -1478,6 +1479,181 @@ int ccio_bam_decode_ids(ccio_bam* b, ccio_interner* it, int mode, const char* de
     *stream_bytes = base[T];
     *max_len = 0;
     for (int t = 0; t < T; ++t) *max_len = std::max(*max_len, ml[t]);
+    return 0;
+}
+
+// ccio_bam_decode_ids without the string pass (the device interner's front: cc_table_ids gives the
+// ids and the string-derived flags): the fixed-width columns, rec_off, the stream (packed for a view),
+// max_len, and rflags with the parser's bit (CC_RF_QUAL_MISSING) only.  cigar_id, bc_id and rg_id of o
+// are not touched.  -1 for a record the shared parser refuses.
+int ccio_bam_decode_cols(ccio_bam* b, cc_records* o, int nthreads, const uint8_t** stream, uint64_t* stream_bytes,
+                         uint64_t* rec_off, int32_t* max_len) {
+    const int64_t n = (int64_t)b->rec.size();
+    const int T = hw_threads(nthreads);
+    std::vector<uint64_t> base(T + 1, 0);
+    std::vector<int32_t> ml(T, 0);
+    std::vector<const uint8_t*> first(T, nullptr), last_end(T, nullptr);
+    std::vector<char> contig(T, 1);
+    std::atomic<int64_t> bad{-1};
+    parallel_for(n, T, [&](int64_t s, int64_t e, int t) {
+        uint64_t sum = 0;
+        int32_t m = 0;
+        bool cg = true;
+        for (int64_t i = s; i < e; ++i) {
+            const uint8_t* rec = b->rec[i];
+            upk::Rec f;
+            if (!upk::parse(rec, 4 + (uint64_t)(uint32_t)rd32(rec), f)) {
+                int64_t was = -1;
+                bad.compare_exchange_strong(was, i);
+                return;
+            }
+            if (i > s && rec != b->rec[i - 1] + 4 + rd32(b->rec[i - 1])) cg = false;
+            rec_off[i] = sum;   // (within the chunk: its base is added below)
+            sum += 4 + (uint64_t)f.bs;
+            m = std::max(m, f.lseq);
+            o->tid[i] = f.tid;
+            o->pos[i] = f.pos;
+            o->mtid[i] = f.mtid;
+            o->mpos[i] = f.mpos;
+            o->tlen[i] = f.tlen;
+            o->flag[i] = (uint16_t)f.flag;
+            o->mapq[i] = (uint8_t)f.mapq;
+            o->lseq[i] = f.lseq;
+            o->qlen[i] = f.qlen;
+            o->qn_len[i] = (uint16_t)f.qn_len;
+            o->rflags[i] = f.rflags;
+        }
+        base[t + 1] = sum;
+        ml[t] = m;
+        contig[t] = cg;
+        if (e > s) {
+            first[t] = b->rec[s];
+            last_end[t] = b->rec[e - 1] + 4 + rd32(b->rec[e - 1]);
+        }
+    });
+    if (bad >= 0) { set_err("decode_cols: record " + std::to_string((long long)bad.load()) + " is malformed"); return -1; }
+    for (int t = 0; t < T; ++t) base[t + 1] += base[t];
+    bool one = true;
+    const uint8_t* prev_end = nullptr;
+    for (int t = 0; t < T; ++t) {
+        if (!first[t]) continue;
+        if (!contig[t] || (prev_end && first[t] != prev_end)) one = false;
+        prev_end = last_end[t];
+    }
+    b->packed.reset();
+    if (!one) {
+        b->packed = std::make_shared<Bytes>();
+        b->packed->resize((size_t)base[T]);
+    }
+    uint8_t* pk = one ? nullptr : b->packed->data();
+    parallel_for(n, T, [&](int64_t s, int64_t e, int t) {
+        for (int64_t i = s; i < e; ++i) {
+            rec_off[i] += base[t];
+            if (pk) memcpy(pk + rec_off[i], b->rec[i], 4 + (size_t)rd32(b->rec[i]));
+        }
+    });
+    o->n = n;
+    *stream = n == 0 ? nullptr : (one ? b->rec[0] : pk);
+    *stream_bytes = base[T];
+    *max_len = 0;
+    for (int t = 0; t < T; ++t) *max_len = std::max(*max_len, ml[t]);
+    return 0;
+}
+
+// The host's part of the device interner.  Per table k (0 barcode, 1 cigar, 2 RG), in local-id order:
+// the string of record first[k][j] by the host's own code (StringPass::one on that one record) goes
+// through the interner (new strings take the next ids, in order of first occurrence; strings it holds
+// keep theirs), then the three shared-id columns are written, local < 0 ? -1 : the shared id.
+// -1 (ccio_last_error says which): a first record outside the handle or one the parser refuses, a
+// first record for which the host finds no string, a local id outside [0, nd[k]).
+int ccio_intern_first(ccio_bam* b, ccio_interner* it, int mode, const char* delim, const int32_t* const* first,
+                      const int32_t* nd, const int32_t* const* local, int64_t n, int32_t* bc_id, int32_t* cigar_id,
+                      int32_t* rg_id, int nthreads) {
+    if (!b || !it || !first || !nd || !local || n != (int64_t)b->rec.size()) {
+        set_err("intern_first: arguments");
+        return -1;
+    }
+    const std::string dl = delim ? delim : "|";
+    static const char* const kTable[3] = {"barcode", "cigar", "RG"};
+    std::vector<int32_t> remap[3];
+    {
+        StringPass sp;
+        sp.start(1);
+        std::lock_guard<std::mutex> g(it->mu);
+        for (int k = 0; k < 3; ++k) {
+            if (nd[k] < 0 || nd[k] > n) { set_err("intern_first: a count of distinct keys outside [0, n]"); return -1; }
+            remap[k].resize((size_t)nd[k]);
+            for (int32_t j = 0; j < nd[k]; ++j) {
+                const int64_t r = first[k][j];
+                upk::Rec f;
+                if (r < 0 || r >= n || !upk::parse(b->rec[r], 4 + (uint64_t)(uint32_t)rd32(b->rec[r]), f)) {
+                    set_err(std::string("intern_first: ") + kTable[k] + " first record " + std::to_string((long long)r) +
+                            " is outside the handle or malformed");
+                    return -1;
+                }
+                sp.one(0, b->rec[r] + 4, f.bs, (uint32_t)f.l_read_name, (size_t)f.qn_len, (uint32_t)f.n_cigar, f.lseq, mode,
+                       dl);
+                const int32_t lid = sp.ids[k][0];
+                if (lid < 0) {
+                    set_err(std::string("intern_first: the host finds no ") + kTable[k] + " in first record " +
+                            std::to_string((long long)r));
+                    return -1;
+                }
+                remap[k][(size_t)j] = it->t[k].get(sp.t[k].strs[(size_t)lid]);
+            }
+        }
+    }
+    int32_t* const out[3] = {bc_id, cigar_id, rg_id};
+    std::atomic<int> bad{-1};
+    parallel_for(n, hw_threads(nthreads), [&](int64_t s, int64_t e, int) {
+        for (int k = 0; k < 3; ++k) {
+            const int32_t* L = local[k];
+            const int32_t* R = remap[k].data();
+            const int32_t m = nd[k];
+            for (int64_t i = s; i < e; ++i) {
+                const int32_t v = L[i];
+                if (v >= m) { bad = k; out[k][i] = -1; continue; }
+                out[k][i] = v < 0 ? -1 : R[v];
+            }
+        }
+    });
+    if (bad >= 0) {
+        set_err(std::string("intern_first: a local ") + kTable[bad.load()] + " id outside [0, nd)");
+        return -1;
+    }
+    return 0;
+}
+
+// test entry: the shared key finders (intern_core.h, what k_ids_keys runs) on the host over b's n
+// records.  Table k's record r at k * n + r: off / len / none; flags[r] the string-derived flag bits;
+// refuse[r] 1 for a record the parser or the finders refuse (its other outputs are zero).
+int ccio_intern_keys(ccio_bam* b, int mode, const char* delim, uint32_t* off, uint32_t* len, uint8_t* none,
+                     uint8_t* flags, uint8_t* refuse) {
+    const std::string dl = delim ? delim : "|";
+    if (!b || dl.size() > (size_t)itn::DELIM_MAX) { set_err("intern_keys: a delimiter of more than 16 bytes"); return -1; }
+    itn::Delim d{};
+    memcpy(d.b, dl.data(), dl.size());
+    d.len = (int32_t)dl.size();
+    const int64_t n = (int64_t)b->rec.size();
+    for (int64_t r = 0; r < n; ++r) {
+        const uint8_t* rec = b->rec[r];
+        upk::Rec f;
+        itn::Key key[3] = {};
+        bool ok = upk::parse(rec, 4 + (uint64_t)(uint32_t)rd32(rec), f);
+        if (ok) {
+            key[0] = itn::barcode_key(rec, f, mode, d);
+            key[1] = itn::cigar_key(rec, f);
+            key[2] = itn::rg_key(rec, f);
+            ok = !key[2].refuse;
+        }
+        refuse[r] = ok ? 0 : 1;
+        flags[r] = ok ? (uint8_t)(key[0].flags | key[2].flags) : 0;
+        for (int k = 0; k < 3; ++k) {
+            off[k * n + r] = ok ? key[k].off : 0;
+            len[k * n + r] = ok ? key[k].len : 0;
+            none[k * n + r] = ok ? (uint8_t)key[k].none : 1;
+        }
+    }
     return 0;
 }
 

@@ -283,6 +283,56 @@ class Bam(object):
             stream = np.zeros(0, np.uint8)
         return rec, stream, off[:self.n]
 
+    def decode_cols(self, nthreads=0):
+        """decode_ids without the string pass (ccio_bam_decode_cols), in front of the device interner:
+        (records, stream, rec_off) as decode_ids gives them, but the records' cigar_id, bc_id and rg_id
+        are unset and rflags holds the parser's bit (CC_RF_QUAL_MISSING) only."""
+        rec = Records(self.n, 0, 0, 0, nref=len(self.refs), derived=False)
+        off = np.zeros(max(self.n, 1), np.uint64)
+        sp, sb, ml = N.P(), C.c_uint64(), C.c_int32()
+        rc = N.io().ccio_bam_decode_cols(self.h, C.byref(rec.struct), nthreads, C.byref(sp), C.byref(sb), N.ptr(off),
+                                         C.byref(ml))
+        if rc != 0:
+            raise IOError(N.io_error())
+        rec.max_len = int(ml.value)
+        if sb.value:
+            stream = np.ctypeslib.as_array(C.cast(sp, C.POINTER(C.c_uint8)), shape=(int(sb.value),))
+        else:
+            stream = np.zeros(0, np.uint8)
+        return rec, stream, off[:self.n]
+
+    def intern_first(self, interner, mode, delim, local, first, nthreads=0, out=None):
+        """The device interner's local ids turned into the interner's (ccio_intern_first).  local: the
+        three int32[n] local-id columns (barcode, cigar, RG; -1: none), first: per table the record of
+        each local id's first occurrence.  Returns (bc_id, cigar_id, rg_id) as decode_ids gives them
+        (written into out's three int32 arrays when given)."""
+        n = self.n
+        local = [np.ascontiguousarray(a, np.int32) for a in local]
+        first = [np.ascontiguousarray(a, np.int32) for a in first]
+        assert all(len(a) == n for a in local)
+        out = out or [np.zeros(max(n, 1), np.int32) for _ in range(3)]
+        assert all(a.dtype == np.int32 and a.flags.c_contiguous and len(a) >= n for a in out)
+        nd = np.array([len(a) for a in first], np.int32)
+        lp = (N.P * 3)(*[N.ptr(a) for a in local])
+        fp = (N.P * 3)(*[N.ptr(a) if len(a) else None for a in first])
+        rc = N.io().ccio_intern_first(self.h, interner.h, mode, (delim or "|").encode(), fp, N.ptr(nd), lp, n,
+                                      N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), nthreads)
+        if rc != 0:
+            raise IOError(N.io_error())
+        return out[0][:n], out[1][:n], out[2][:n]
+
+    def intern_keys(self, mode, delim="|"):
+        """Test entry (ccio_intern_keys): the device interner's key finders run on the host.  Returns
+        (off[3, n], len[3, n], none[3, n], flags[n], refuse[n]); rows: barcode, cigar, RG."""
+        n = self.n
+        off, ln = np.zeros((3, max(n, 1)), np.uint32), np.zeros((3, max(n, 1)), np.uint32)
+        none, flags, refuse = np.zeros((3, max(n, 1)), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        if n:
+            if N.io().ccio_intern_keys(self.h, mode, (delim or "|").encode(), N.ptr(off), N.ptr(ln), N.ptr(none),
+                                       N.ptr(flags), N.ptr(refuse)) != 0:
+                raise IOError(N.io_error())
+        return off[:, :n], ln[:, :n], none[:, :n], flags[:n], refuse[:n]
+
 
 class Stream(object):
     """The order in which read_bam sees records: whole file (until_eof) or the bed
@@ -365,6 +415,7 @@ class Engine(object):
         self.inflate_device = False
         self.decode_device = False
         self.resident_device = False
+        self.ids_device = False
         self._keep_wired = False
         self.crc_device = False
         self.assemble_device = False
@@ -385,6 +436,8 @@ class Engine(object):
             self.device_inflate(True)
         if os.environ.get("CC_DECODE_DEVICE") == "1":
             self.device_decode(True)
+        if os.environ.get("CC_IDS_DEVICE") == "1":
+            self.device_ids(True)
         if os.environ.get("CC_ASSEMBLE_DEVICE") == "1":
             self.device_assemble(True)
         if os.environ.get("CC_MERGE_DEVICE") == "1":
@@ -399,6 +452,17 @@ class Engine(object):
         was = self.decode_device
         self.decode_device = bool(on)
         self._sync_keep()
+        return was
+
+    def device_ids(self, on):
+        """Switches unpack between libccio's string pass (Bam.decode_ids, the default) and the device
+        interner: Bam.decode_cols, cc_table_ids over the raw records (the resident stream when there is
+        one) and Bam.intern_first for the distinct strings only.  It has effect only while
+        device_decode is on.  A file the device interner refuses (CC_E_INVALID, CC_E_COLLISION,
+        CC_E_UNSUPPORTED) goes through the host pass.  The ids, the tables and every file written from
+        them are the same either way.  Returns the previous state."""
+        was = self.ids_device
+        self.ids_device = bool(on)
         return was
 
     def device_resident(self, on):
@@ -1165,6 +1229,57 @@ class Engine(object):
                                                       N.ptr(cols[2]), N.ptr(cols[3]), C.byref(ml), C.byref(tid)))
         return tid.value, ml.value
 
+    def _table_ids(self, call, n, mode, delim):
+        local = [np.zeros(max(n, 1), np.int32) for _ in range(3)]
+        first = [np.zeros(max(n, 1), np.int32) for _ in range(3)]
+        rflags, nd = np.zeros(max(n, 1), np.uint8), np.zeros(3, np.int32)
+        self._check(call(mode, (delim or "|").encode(), N.ptr(local[0]), N.ptr(local[1]), N.ptr(local[2]), N.ptr(rflags),
+                         N.ptr(first[0]), N.ptr(first[1]), N.ptr(first[2]), N.ptr(nd)))
+        return [a[:n] for a in local], rflags[:n], [a[:int(k)] for a, k in zip(first, nd)]
+
+    def table_ids(self, stream, rec_off, mode, delim="|"):
+        """cc_table_ids on a host stream: (local, rflags, first).  local: the three int32[n] columns
+        (barcode, cigar, RG) of local ids in order of first occurrence, -1 for none; rflags: all three
+        bits; first: per table the record of each local id's first occurrence."""
+        stream = np.ascontiguousarray(stream, np.uint8)
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        n = len(off)
+        return self._table_ids(lambda *a: self.lib.cc_table_ids(self.h, N.ptr(stream) if stream.size else None, stream.size,
+                                                                N.ptr(off) if n else None, n, *a), n, mode, delim)
+
+    def table_ids_resident(self, rid, base, nbytes, rec_off, mode, delim="|"):
+        """cc_table_ids_resident: table_ids with the records read from bytes [base, base + nbytes) of
+        resident stream rid.  The stream is not freed."""
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        n = len(off)
+        return self._table_ids(lambda *a: self.lib.cc_table_ids_resident(self.h, int(rid), int(base), int(nbytes),
+                                                                         N.ptr(off) if n else None, n, *a), n, mode, delim)
+
+    def debug_ids_hash_bits(self, bits):
+        """Test hook (cc_debug_ids_hash_bits): table_ids keeps the low `bits` bits of a key's hash."""
+        self._check(self.lib.cc_debug_ids_hash_bits(self.h, int(bits)))
+
+    def _decode_ids_device(self, bam, interner, mode, delim):
+        """Bam.decode_ids' result by the device interner, or None where it refuses the file (the host
+        pass decides it then)."""
+        rec, stream, off = bam.decode_cols()
+        res = bam.resident()
+        try:
+            if res is not None and res[0] is self:
+                local, rflags, first = self.table_ids_resident(res[1], res[2], stream.size, off, mode, delim)
+            else:
+                local, rflags, first = self.table_ids(stream, off, mode, delim)
+        except N.CCError as e:
+            if e.code not in (N.CC_E_INVALID, N.CC_E_COLLISION, N.CC_E_UNSUPPORTED):
+                raise
+            return None
+        n = rec.n
+        if n and ((rflags ^ rec.rflags[:n]) & 2).any():
+            raise N.CCError(-1, "device and host disagree on CC_RF_QUAL_MISSING")
+        bam.intern_first(interner, mode, delim, local, first, out=(rec.bc_id, rec.cigar_id, rec.rg_id))
+        rec.rflags[:n] = rflags
+        return rec, stream, off
+
     def unpack(self, bam, interner, mode, delim="|"):
         """The device decode of bam: (records, table).  libccio's slim pass (Bam.decode_ids) keeps the
         string work (interned cigar, barcode and RG ids, the string-derived record flags); the raw
@@ -1174,7 +1289,8 @@ class Engine(object):
         bam.resident) the records are read there (cc_table_unpack_resident) and the resident stream
         is freed, whether the unpack succeeds or not; an id the engine does not know falls back to the
         upload."""
-        rec, stream, off = bam.decode_ids(interner, mode, delim)
+        got_ids = self._decode_ids_device(bam, interner, mode, delim) if self.ids_device else None
+        rec, stream, off = got_ids or bam.decode_ids(interner, mode, delim)
         res = bam.resident()
         got = None
         if res is not None and res[0] is self:

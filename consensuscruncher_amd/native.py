@@ -176,6 +176,9 @@ IO_SIGS = {
     "ccio_bam_decode": (C.c_int, [P, P, C.c_int, C.c_char_p, C.POINTER(cc_records), C.c_int]),
     "ccio_bam_decode_ids": (C.c_int, [P, P, C.c_int, C.c_char_p, C.POINTER(cc_records), C.c_int, C.POINTER(P),
                                       C.POINTER(C.c_uint64), P, i32p]),
+    "ccio_bam_decode_cols": (C.c_int, [P, C.POINTER(cc_records), C.c_int, C.POINTER(P), C.POINTER(C.c_uint64), P, i32p]),
+    "ccio_intern_first": (C.c_int, [P, P, C.c_int, C.c_char_p, P, P, P, C.c_int64, P, P, P, C.c_int]),
+    "ccio_intern_keys": (C.c_int, [P, C.c_int, C.c_char_p, P, P, P, P, P]),
     "ccio_format_csn_names": (C.c_int64, [P, C.c_int64, P, P, P, C.c_int64, P]),
     "ccio_dcs_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
     "ccio_duplex_tag": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
@@ -252,6 +255,10 @@ AMD_SIGS = {
     "cc_table_unpack": (C.c_int, [P, P, C.c_uint64, P, C.c_int64, P, P, P, P, i32p, i32p]),
     "cc_table_unpack_resident": (C.c_int, [P, C.c_int64, C.c_uint64, C.c_uint64, P, C.c_int64, P, P, P, P, i32p,
                                            i32p]),
+    "cc_table_ids": (C.c_int, [P, P, C.c_uint64, P, C.c_int64, C.c_int, C.c_char_p, P, P, P, P, P, P, P, P]),
+    "cc_table_ids_resident": (C.c_int, [P, C.c_int64, C.c_uint64, C.c_uint64, P, C.c_int64, C.c_int, C.c_char_p, P, P, P,
+                                        P, P, P, P, P]),
+    "cc_debug_ids_hash_bits": (C.c_int, [P, C.c_int32]),
     "cc_bam_assemble": (C.c_int, [P, P, C.c_uint64, C.POINTER(cc_asm_src), C.c_int32, P, C.c_int64, P, P, C.c_int64,
                                   C.c_uint64, P, C.c_uint64, P, C.c_uint64, C.c_int32, P, P, C.c_int32, C.c_int, P,
                                   C.c_uint64, P, C.POINTER(C.c_uint64)]),

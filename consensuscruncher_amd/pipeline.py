@@ -54,8 +54,12 @@ def cleanup(sd, identifier, scorrect):
 def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", scorrect="True", engine=None,
                        verbose=False, level=6, genome=None, cleanup_files="False", all_unique_sscs=False,
                        bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host", crc="host",
-                       assemble="host", names="host", out_resident="host", names_resident="host", merge="host"):
-    """merge: "host" (libccio merges the sorted stage outputs, the default) or "device" (Engine.device_merge:
+                       assemble="host", names="host", out_resident="host", names_resident="host", merge="host",
+                       ids="host"):
+    """ids: "host" (libccio's string pass interns the cigar, barcode and RG ids, the default) or "device"
+    (Engine.device_ids: the record unpacker's id columns and record flags come from the engine's interner
+    kernels and the host interns the distinct strings only: the same ids, so the same files); it engages
+    only with decode="device" and is otherwise without effect.  merge: "host" (libccio merges the sorted stage outputs, the default) or "device" (Engine.device_merge:
     sscs.sc, all.unique.dcs and all.unique.sscs are merged by the engine's merge kernels, and with the
     resident output path on the merged stream stays on the device for the encoder and the index and each
     merge input is uploaded once for the merges that read it: the same files).  names_resident: "host" (the default) or "device" (Engine.device_names_resident: a stage's formatted
@@ -82,6 +86,17 @@ def consensus_pipeline(bam, c_output, bedfile="False", cutoff=0.7, bdelim="|", s
     come from the device; same bytes read, same files written); it engages only with inflate="device"
     or bgzf="device" and is otherwise without effect.  Each option is wired for this call only; see
     _consensus_pipeline."""
+    if ids not in ("host", "device"):
+        raise ValueError('ids must be "host" or "device"')
+    if ids == "device":
+        engine = engine or get_engine()
+        was_ids = engine.device_ids(True)
+        try:
+            return consensus_pipeline(bam, c_output, bedfile, cutoff, bdelim, scorrect, engine, verbose, level, genome,
+                                      cleanup_files, all_unique_sscs, bgzf, inflate, decode, bgzf_effort, resident, crc,
+                                      assemble, names, out_resident, names_resident, merge)
+        finally:
+            engine.device_ids(was_ids)
     if merge not in ("host", "device"):
         raise ValueError('merge must be "host" or "device"')
     if merge == "device":

@@ -623,8 +623,10 @@ def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|
                      verbose=False, blocks=None, held=None, refs=None, keep=None, finalize=True, timings=None,
                      cuts=None, bgzf="host", inflate="host", decode="host", bgzf_effort=1, resident="host",
                      crc="host", assemble="host", names="host", out_resident="host", names_resident="host",
-                     merge="host"):
-    """merge: "host" (the default) or "device": this rank's merges of sorted record sets go to the engine's
+                     merge="host", ids="host"):
+    """ids: "host" (the default) or "device": this rank's record unpacker takes its id columns and record
+    flags from the engine's interner kernels (Engine.device_ids; only with decode="device").
+    merge: "host" (the default) or "device": this rank's merges of sorted record sets go to the engine's
     merge kernels where every input holds its records in place (Engine.device_merge; merges of combined
     and routed views, and of more than 8 inputs, stay on the host as before).
     names_resident: "host" (the default) or "device": this rank's formatted names stay on the device
@@ -647,6 +649,16 @@ def sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff=0.7, bdelim="|
     uploaded as before).  crc: "host" (the default) or "device": this rank's device inflater and encoder
     take their CRC32s from the device (Engine.device_crc; only with inflate="device" or bgzf="device").
     These are pipeline.consensus_pipeline's options; see _sharded_pipeline."""
+    if ids not in ("host", "device"):
+        raise ValueError('ids must be "host" or "device"')
+    if ids == "device":
+        was_ids = engine.device_ids(True)
+        try:
+            return sharded_pipeline(bam, c_output, bedfile, comm, engine, cutoff, bdelim, scorrect, level, verbose,
+                                    blocks, held, refs, keep, finalize, timings, cuts, bgzf, inflate, decode,
+                                    bgzf_effort, resident, crc, assemble, names, out_resident, names_resident, merge)
+        finally:
+            engine.device_ids(was_ids)
     if merge not in ("host", "device"):
         raise ValueError('merge must be "host" or "device"')
     if merge == "device":

@@ -162,6 +162,27 @@ int ccio_bam_decode(ccio_bam *b, ccio_interner *it, int mode, const char *delim,
  * block_size (csrc/unpack_core.h's refusals). */
 int ccio_bam_decode_ids(ccio_bam *b, ccio_interner *it, int mode, const char *delim, cc_records *out, int nthreads,
                         const uint8_t **stream, uint64_t *stream_bytes, uint64_t *rec_off, int32_t *max_len);
+/* ccio_bam_decode_ids without the string pass, in front of the device interner (cc_table_ids): the
+ * same columns, stream, rec_off and max_len, but cigar_id / bc_id / rg_id are not touched and rflags
+ * holds the parser's bit (CC_RF_QUAL_MISSING) only. */
+int ccio_bam_decode_cols(ccio_bam *b, cc_records *out, int nthreads, const uint8_t **stream, uint64_t *stream_bytes,
+                         uint64_t *rec_off, int32_t *max_len);
+/* The host's part of the device interner: cc_table_ids' local ids turned into the interner's.  Per
+ * table k (0 barcode, 1 cigar, 2 RG), in local-id order, the string of record first[k][j] (j < nd[k])
+ * is extracted by ccio_bam_decode's own code and interned (under the interner's mutex): new strings
+ * take the next ids in order of first occurrence, as ccio_bam_decode_ids gives them; then
+ * bc_id / cigar_id / rg_id[n] = local[k][i] < 0 ? -1 : that string's id.  -1 (ccio_last_error) for a
+ * first record outside the handle, one in which the host finds no string, or a local id outside
+ * [0, nd[k]). */
+int ccio_intern_first(ccio_bam *b, ccio_interner *it, int mode, const char *delim, const int32_t *const *first,
+                      const int32_t *nd, const int32_t *const *local, int64_t n, int32_t *bc_id, int32_t *cigar_id,
+                      int32_t *rg_id, int nthreads);
+/* test entry: the device interner's key finders (csrc/intern_core.h) run on the host over b's n
+ * records.  Table k's record r at [k * n + r]: the key's offset from the record's block_size word,
+ * its length, and none (no key: id -1); flags[n]: CC_RF_BAD_SPACER | CC_RF_RG_UNSUPPORTED as they
+ * apply; refuse[n]: 1 for a record the finders refuse.  -1 for a delimiter of more than 16 bytes. */
+int ccio_intern_keys(ccio_bam *b, int mode, const char *delim, uint32_t *off, uint32_t *len, uint8_t *none,
+                     uint8_t *flags, uint8_t *refuse);
 
 /* sscs_qname fields (9 int32 per name: bc, tidLo, posLo, tidHi, posHi, cigA, cigB,
  * strand(0 pos/1 neg/2 None), |tlen|) + ':' + suffix.  blob NULL = size query. */
@@ -847,6 +868,35 @@ int64_t cc_names_count(cc_ctx *ctx);
 int cc_table_unpack_resident(cc_ctx *ctx, int64_t id, uint64_t base, uint64_t bytes, const uint64_t *rec_off,
                              int64_t n, const int32_t *cigar_id, const int32_t *bc_id, const int32_t *rg_id,
                              const uint8_t *rflags, int32_t *max_len, int32_t *table_id);
+/* The device interner: the three interned-id columns of the records recs[0 .. bytes) (rec_off[n] as
+ * cc_table_unpack takes them) as local ids, and rflags with all three bits, by kernels over the raw
+ * records (csrc/table_ids.hip.inc, the rules of csrc/intern_core.h: ccio_bam_decode's modes and
+ * delimiter rules).  local_bc / local_cigar / local_rg[n]: each record's key as its rank among the
+ * table's distinct keys in order of first occurrence in record order, -1 for a record without one;
+ * first_bc / first_cigar / first_rg (capacity n): the record of each local id's first occurrence,
+ * nd[k] of them (k: 0 barcode, 1 cigar, 2 RG).  The cigar's key is the raw cigar bytes, so two local
+ * ids may print one string; ccio_intern_first turns the local ids into the interner's.
+ * A record the shared parser refuses, or whose aux fields hold a value that does not lie whole inside
+ * the record (a B header or array cut by the record's end, a negative B count, a fixed-width value
+ * past the end: where the host's walk would read outside the record), is CC_E_INVALID and
+ * cc_last_error names the first such record.  A delimiter of more than 16 bytes or more than
+ * 2^31 - 1 records is CC_E_UNSUPPORTED (before any launch).  Keys are compared byte for byte within
+ * a run of equal 64-bit hashes: a collision runs the call again under another seed, and under the
+ * fourth is CC_E_COLLISION.  After any error nothing stays allocated and the outputs hold nothing of
+ * use.  Profile scopes: ids_stream_upload, ids_keys, ids_sort, ids_heads, ids_scan, ids_assign,
+ * ids_download. */
+int cc_table_ids(cc_ctx *ctx, const uint8_t *recs, uint64_t bytes, const uint64_t *rec_off, int64_t n, int mode,
+                 const char *delim, int32_t *local_bc, int32_t *local_cigar, int32_t *local_rg, uint8_t *rflags,
+                 int32_t *first_bc, int32_t *first_cigar, int32_t *first_rg, int32_t nd[3]);
+/* cc_table_ids with the records read in place from resident stream id's bytes [base, base + bytes), as
+ * cc_table_unpack_resident reads them: it waits for the inflater's streams first, uploads only rec_off
+ * and does not free the stream. */
+int cc_table_ids_resident(cc_ctx *ctx, int64_t id, uint64_t base, uint64_t bytes, const uint64_t *rec_off, int64_t n,
+                          int mode, const char *delim, int32_t *local_bc, int32_t *local_cigar, int32_t *local_rg,
+                          uint8_t *rflags, int32_t *first_bc, int32_t *first_cigar, int32_t *first_rg, int32_t nd[3]);
+/* test hook: cc_table_ids keeps only the low `bits` bits (1 .. 64; 64 is the default) of a key's hash,
+ * so that small inputs collide */
+int cc_debug_ids_hash_bits(cc_ctx *ctx, int32_t bits);
 int cc_table_free(cc_ctx *ctx, int32_t table_id);
 /* the table's derived columns (member records, position keys, qname digests, record cores and deep
  * bits, the deep-group list) built again from its record columns, on the context's stream without a
